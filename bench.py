@@ -19,7 +19,13 @@ Two launch styles, the same data path:
                                                  group, which is otherwise only used for barriers)
 
 Prints ONE JSON line on rank 0.  `value` = forest-build vectors/s with the data resident in
-HBM; the kNN queries/s and recall@10 of the same run are in `knn` / `recall_at_10`.
+HBM, `ms_per_step` = milliseconds of one timed build.  A plain run does only that: inputs,
+--warmup untimed builds, --steps timed builds, the line.  --full adds everything else to the
+same line: the kNN leg's queries/s and recall@10 (`knn` / `recall_at_10`), the other projection
+mode, rooflines, PCIe-inclusive rates, the CPU baseline, the one-rank exchange, other_configs and
+shard_sweep.
+
+--dump-outputs DIR writes what the last timed build returned to its caller (see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -49,6 +55,33 @@ MFMA_F32_PEAK_TF = 157.3   # MI355X_MICROARCH.md: FP32 matrix = FP32 vector rate
 MFMA_BF16_PEAK_TF = 2500.0  # MI355X_MICROARCH.md: ~2.5 PF dense bf16 (no sparsity)
 PMC_FILES = ("r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json",
              "r01_pmc_traffic.json")   # newest first
+DUMP_PERM_MAX = 1 << 22     # float64 entries: 32 MB of perm, 8 MB of each node array, 56 MB in all
+DUMP_NODES_MAX = 1 << 20
+
+
+def _columns(a, cap, seed):
+    """a, or the same seeded sample of sorted column indices of every row when a has more than
+    cap entries"""
+    rows, cols = a.shape
+    m = max(1, cap // max(rows, 1))
+    if m >= cols:
+        return a
+    return a[:, np.sort(np.random.default_rng(seed).choice(cols, m, replace=False))]
+
+
+def dump_outputs(out_dir, forest, nlocal):
+    """DIR/{perm,thr,mglo,mghi}.npy, float64: the forest the last timed build handed its caller,
+    the trees of this process's devices in tree order.  perm is T x N positions (leaf ranges
+    of tree t = topology offsets into perm[t]); thr / mglo / mghi are T x (2^maxDepth - 1) nodes
+    in heap order, NaN where a node does not exist.  An array above its cap keeps the columns
+    of a fixed seeded sample (_columns), so that the four files stay under 64 MB."""
+    locs = [forest.local(g)[0] for g in range(nlocal)]
+    os.makedirs(out_dir, exist_ok=True)
+    perm = np.concatenate([f.perm for f in locs])
+    np.save(os.path.join(out_dir, "perm.npy"), _columns(perm, DUMP_PERM_MAX, 0).astype(np.float64))
+    for name in ("thr", "mglo", "mghi"):
+        a = np.concatenate([getattr(f, name) for f in locs])
+        np.save(os.path.join(out_dir, name + ".npy"), _columns(a, DUMP_NODES_MAX, 1))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -627,6 +660,12 @@ def main():
                     help="projection kernel of the timed build: mfma = the north-star MFMA tile "
                          "kernel (values within 1e-5*|x||r|), exact = reference summation order "
                          "(bit-identical leaf assignment); the other mode is timed as a side leg")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the forest of the last one as DIR/*.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the kNN leg, the other projection mode, rooflines, "
+                         "PCIe-inclusive rates, the CPU baseline, the one-rank exchange, other_configs and "
+                         "shard_sweep; the three options below apply to --full only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--other-configs", default="c3,c4,c5",
                     help="comma list of the other BASELINE configurations to time after C2 at N = 1 "
@@ -663,6 +702,8 @@ def main():
     world = args.gpus
     if world < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     # stdout carries exactly ONE line, the JSON result: native libraries (RCCL prints a version
     # banner on stdout when its first communicator is made) and stray prints go to stderr
@@ -712,14 +753,17 @@ def main():
     # ---- synthetic inputs (SplitMix64 streams, seeds 1234 / 4321 / 1235137), drawn on
     # the device and resident in HBM before any timed region ----
     X0 = gen.normal_dense2_torch(1234, N, d, devs[0])
-    Q0 = gen.normal_dense2_torch(4321, nq, d, devs[0])
     Xs = [X0] + [X0.to(dv) for dv in devs[1:]]           # replicas over xGMI
-    Qs = [Q0] + [Q0.to(dv) for dv in devs[1:]]
+    if args.full:                                        # the queries: only --full answers them
+        Q0 = gen.normal_dense2_torch(4321, nq, d, devs[0])
+        Qs = [Q0] + [Q0.to(dv) for dv in devs[1:]]
     for dv in devs:
         torch.cuda.synchronize(dv)
     dss = [rp.Dataset.from_torch(c, x) for c, x in zip(ctxs, Xs)]
-    qss = [rp.Dataset.from_torch(c, q) for c, q in zip(ctxs, Qs)]
-    ds, qs, X, Q = dss[0], qss[0], X0, Q0
+    ds, X = dss[0], X0
+    if args.full:
+        qss = [rp.Dataset.from_torch(c, q) for c, q in zip(ctxs, Qs)]
+        qs, Q = qss[0], Q0
     _, R = gen.forest_hyperplanes(1235137, T, maxd, pnz, d)          # host, Batch.hs:59-61
 
     def barrier():
@@ -732,14 +776,15 @@ def main():
     def build(m=mode):
         return sharded.ShardedForest(comm, dss, R, maxd, args.min_leaf, m)
 
-    outs = [(torch.empty((nq, k), dtype=torch.int32, device=dv),
-             torch.empty((nq, k), dtype=torch.float64, device=dv),
-             torch.empty((nq,), dtype=torch.int32, device=dv)) for dv in devs]
-    for dv in devs:
-        torch.cuda.synchronize(dv)
-    o_ids = [o[0].data_ptr() for o in outs]
-    o_dist = [o[1].data_ptr() for o in outs]
-    o_cnt = [o[2].data_ptr() for o in outs]
+    if args.full:
+        outs = [(torch.empty((nq, k), dtype=torch.int32, device=dv),
+                 torch.empty((nq, k), dtype=torch.float64, device=dv),
+                 torch.empty((nq,), dtype=torch.int32, device=dv)) for dv in devs]
+        for dv in devs:
+            torch.cuda.synchronize(dv)
+        o_ids = [o[0].data_ptr() for o in outs]
+        o_dist = [o[1].data_ptr() for o in outs]
+        o_cnt = [o[2].data_ptr() for o in outs]
 
     def knn(forest, flags):
         """kernels -> ONE ncclAllGather -> merge, all enqueued on the ctx streams; one host
@@ -754,7 +799,8 @@ def main():
         if forest is not None:
             forest.close()
         forest = build()
-        knn(forest, rp.RPT_KNN_KEEP_DUPLICATES)
+        if args.full:
+            knn(forest, rp.RPT_KNN_KEEP_DUPLICATES)
     if forest is None:
         forest = build()
 
@@ -767,9 +813,52 @@ def main():
             out[name] = (ms.value, cnt.value)
         return out
 
+    def max_over_ranks(*ts):
+        if not launcher:
+            return ts
+        tt = torch.tensor(ts, dtype=torch.float64)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        return tuple(float(t) for t in tt)
+
+    def headline(t_build):
+        return {
+            "metric": "forest-build vectors/s (%d x %d dense f64, %d trees; projection mode %s = "
+                      "RPT_PROJ_%s, the API default RPT_PROJ_AUTO on f64 data is the exact-order "
+                      "kernel timed in `other_projection_mode`); kNN queries/s and recall@%d in "
+                      "`knn` / `recall_at_10`" % (N, d, T, args.mode, args.mode.upper(), k),
+            "value": N * args.steps / t_build,
+            "unit": "vectors/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": t_build / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": "C2: %d x %d f64 two-Gaussian mixture, %d-tree forest, minLeaf %d, "
+                                   "maxDepth %d, pnz %.4f, k=%d, %d queries; trees sharded %d/GPU, "
+                                   "X replicated" % (N, d, T, args.min_leaf, maxd, pnz, k, nq, Tl),
+                       "projection_mode": args.mode,
+                       "generator": "SplitMix64 streams of SURVEY 8(d) (data 1234, queries 4321, "
+                                    "forest 1235137), drawn on the device"},
+            "launch": launch,
+            "rccl_ranks": comm.nranks,
+        }
+
+    def finish():
+        forest.close()
+        if launcher:
+            dist.barrier()
+        comm.close()
+        if launcher:
+            dist.destroy_process_group()
+
     # ---- timed region 1: K forest builds ----
-    _lib.check(L_.rpt_prof_reset(ctx._h))
-    _lib.check(L_.rpt_prof_enable(ctx._h, 1))
+    if args.full:        # HIP events around every launch: roofline and build_breakdown_ms
+        _lib.check(L_.rpt_prof_reset(ctx._h))
+        _lib.check(L_.rpt_prof_enable(ctx._h, 1))
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -778,6 +867,15 @@ def main():
         forest = build()
     barrier()
     t_build = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, forest, nloc)
+    if not args.full:
+        t_build, = max_over_ranks(t_build)
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(headline(t_build)) + "\n").encode())
+        finish()
+        return
     prof = read_prof()                       # projection / split spans of the build region only
     _lib.check(L_.rpt_prof_reset(ctx._h))
 
@@ -873,10 +971,7 @@ def main():
                              "8.19 GFLOP); HIP events around every launch; profiles/r04_narrow_* hold the "
                              "rocprofv3 kernel trace and FETCH/WRITE of the same launches")
 
-    if launcher:
-        tt = torch.tensor([t_build, t_knn], dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        t_build, t_knn = float(tt[0]), float(tt[1])
+    t_build, t_knn = max_over_ranks(t_build, t_knn)
 
     prof["knn_plan"], prof["knn_topk"] = prof_q["knn_plan"], prof_q["knn_topk"]
     cand_total = C.c_int64()
@@ -1199,30 +1294,8 @@ def main():
                                      "rows), k' = %d" % (sb, kp) if pre32 else
                                      "nq x candidates x d x 8 B (SURVEY 8d)",
                     "candidates_per_query": cand_q}
-        out = {
-            "metric": "forest-build vectors/s (%d x %d dense f64, %d trees; projection mode %s = "
-                      "RPT_PROJ_%s, the API default RPT_PROJ_AUTO on f64 data is the exact-order "
-                      "kernel timed in `other_projection_mode`); kNN queries/s and recall@%d in "
-                      "`knn` / `recall_at_10`" % (N, d, T, args.mode, args.mode.upper(), k),
-            "value": N * args.steps / t_build,
-            "unit": "vectors/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": t_build / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "C2: %d x %d f64 two-Gaussian mixture, %d-tree forest, minLeaf %d, "
-                                   "maxDepth %d, pnz %.4f, k=%d, %d queries; trees sharded %d/GPU, "
-                                   "X replicated" % (N, d, T, args.min_leaf, maxd, pnz, k, nq, Tl),
-                       "projection_mode": args.mode,
-                       "generator": "SplitMix64 streams of SURVEY 8(d) (data 1234, queries 4321, "
-                                    "forest 1235137), drawn on the device"},
-            "launch": launch,
-            "rccl_ranks": comm.nranks,
+        out = headline(t_build)
+        out.update({
             "roofline": roof,
             "roofline_knn": roof_knn,
             "cpu_baseline": cpu,
@@ -1263,15 +1336,10 @@ def main():
             "other_configs": other,
             "shard_sweep": sweep,
             "roofline_per_level": per_level,
-        }
+        })
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
-    forest.close()
-    if launcher:
-        dist.barrier()
-    comm.close()
-    if launcher:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

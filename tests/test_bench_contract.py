@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                           "--npoints", "200000", "--trees", "8", "--nq", "1000", "--no-cpu-baseline",
                           "--other-configs", "none"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -38,6 +38,50 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     ex = j["knn"]["exchange_one_rank"]          # record -> ncclAllGather -> merge really ran
     assert "error" not in ex and ex["trees"] == 1 and ex["knn_ms_with_forced_exchange"] > 0
     assert j["other_configs"] is None
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_only_the_build_and_dumps_its_forest(tmp_path, oracle):
+    """Without --full the line holds the headline alone.  --dump-outputs writes the forest of the
+    last timed build: in exact mode the oracle's forest bit for bit, and the same arrays again in
+    a second run with the same arguments."""
+    import numpy as np
+    import torch
+    import rptree_amd as rp
+    from rptree_amd import gen
+    N, d, T, min_leaf = 200000, 128, 8, 128
+
+    def run(mode, dump):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+                              "--npoints", str(N), "--trees", str(T), "--mode", mode, "--dump-outputs", str(dump)],
+                             cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["dtype"] == "f64" and j["unit"] == "vectors/s"
+        assert j["higher_is_better"] is True and j["metric"].startswith("forest-build vectors/s")
+        assert abs(j["value"] - N / (j["ms_per_step"] * 1e-3)) / j["value"] < 1e-6
+        for key in ("knn", "roofline", "cpu_baseline", "other_configs", "shard_sweep"):
+            assert key not in j, key
+        files = sorted(os.listdir(dump))
+        assert files == ["mghi.npy", "mglo.npy", "perm.npy", "thr.npy"]
+        assert sum(os.path.getsize(os.path.join(dump, f)) for f in files) <= 64 << 20
+        got = {f[:-4]: np.load(os.path.join(dump, f)) for f in files}
+        assert all(a.dtype == np.float64 for a in got.values())
+        return got
+
+    cfg = rp.rpTreeCfg(min_leaf, N, d)
+    X = gen.normal_dense2_torch(1234, N, d, torch.device("cuda", 0)).cpu().numpy()
+    _, R = gen.forest_hyperplanes(1235137, T, cfg.fpMaxTreeDepth, cfg.fpProjNzDensity, d)
+    fo = oracle.forest_build_dense(X, R, min_leaf, threads=T)
+    ex = run("exact", tmp_path / "exact")
+    assert np.array_equal(ex["perm"], fo.perm)
+    for name in ("thr", "mglo", "mghi"):
+        assert np.array_equal(ex[name], getattr(fo, name), equal_nan=True), name
+    a, b = run("mfma", tmp_path / "a"), run("mfma", tmp_path / "b")
+    for name in a:
+        assert np.array_equal(a[name], b[name], equal_nan=True), name
 
 
 @pytest.mark.gpu
