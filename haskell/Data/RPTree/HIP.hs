@@ -7,7 +7,8 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, ProjMode(..), FlatForest(..), DeviceForest(..), DeviceData(..)) where
+                        withDeviceForestOn, knnHIP, knnMetricHIP, Metric(..), ProjMode(..), FlatForest(..),
+                        DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
 import Control.Monad (when)
@@ -205,7 +206,22 @@ withDeviceForest seed maxd minl ntrees pnz dim src act =
 
 -- | 'knn metricL2 k' (RPTree.hs:168-176) for a batch of dense queries: ids and distances.
 knnHIP :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int -> Int -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
-knnHIP ctx f ds qs nq k = do
+knnHIP ctx f ds qs nq k = knnMetricHIP MetricL2 ctx f ds qs nq k
+
+-- | The distances the device can rank by.  A Haskell closure cannot run on the device, so 'knn''s
+-- distf is one of these: 'MetricL2' = metricL2; 'MetricCosine' = @\x q -> 1 - inner x q / (sqrt (inner x x)
+-- * sqrt (inner q q))@; 'MetricInner' = @\x q -> negate (inner x q)@ — with inner = innerDD's left
+-- fold in Double (Internal.hs:384-385), bit for bit (RPT_KNN_METRIC_COSINE / _INNER).
+data Metric = MetricL2 | MetricCosine | MetricInner deriving (Eq, Show)
+
+metricFlag :: Metric -> Int32
+metricFlag MetricL2 = 0
+metricFlag MetricCosine = 33554432   -- RPT_KNN_METRIC_COSINE (1 << 25)
+metricFlag MetricInner = 67108864    -- RPT_KNN_METRIC_INNER (1 << 26)
+
+-- | 'knn distf k' (RPTree.hs:168-176) under one of the device metrics, for a batch of dense queries.
+knnMetricHIP :: Metric -> Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int -> Int -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnMetricHIP m ctx f ds qs nq k = do
   ids <- VSM.new (nq * k); dist <- VSM.new (nq * k); cnt <- VSM.new nq
-  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_host ctx f ds qs (fromIntegral k) 0 a b))) >>= check
+  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_host ctx f ds qs (fromIntegral k) (metricFlag m) a b))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt

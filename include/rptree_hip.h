@@ -84,6 +84,27 @@ extern "C" {
  * (left fold in merge order); one thread per candidate, general query path.  Ignored for dense
  * data (metricDDL2 is what they get anyway). */
 #define RPT_KNN_METRIC_REFERENCE (1 << 24)
+/* Cosine and inner-product distances (the reference's `knn distf` with another distf, RPTree.hs:
+ * 168-176; the forest only decides which points are candidates, the metric only ranks them).  Dense
+ * data (f64, f32, bf16 rows); every quantity in double, f32 / bf16 elements widened exactly; with
+ * dot(x, q) = innerDD (Internal.hs:384-385), the left fold ((0 + x0 q0) + x1 q1) + ... from +0.0,
+ * every product and sum rounded on its own (no FMA):
+ *   RPT_KNN_METRIC_INNER : dist = -dot(x, q)                          (maximum inner product)
+ *   RPT_KNN_METRIC_COSINE: dist = 1 - dot(x, q) / (sqrt(dot(x, x)) * sqrt(dot(q, q)))
+ * with correctly rounded sqrt and division; smaller is nearer; a zero row or query gives NaN, and
+ * NaN ranks behind every number, NaNs among themselves by candidate position.  Selection, the
+ * duplicate rules and the returned bits are as for L2 on f64 rows: candidates are RANKED on a
+ * lane-parallel f64 dot, the best k + 8 are evaluated again as the fold and the k best of those
+ * by (distance, candidate position) are returned — more than 8 DIFFERENT rows within a few ulp of
+ * the k-th distance would be needed to change the membership.  Unlike L2 on f32 / bf16 rows the
+ * values are f64 for every dtype.  Or-ed into the knn flags; at most one of the two, not with
+ * RPT_KNN_METRIC_REFERENCE (RPT_E_ARG); CSR data and RPT_KNN_VOTE: RPT_E_UNSUPPORTED.  Not for
+ * knnH (rpt_knnh_host has no flags).
+ * Memory note: the first cosine call on a dataset caches its rows' dot(x, x) on the device, 8 bytes
+ * per row, freed with the dataset (a dataset borrowed with rpt_dataset_dense_dev must not change
+ * while the library holds it). */
+#define RPT_KNN_METRIC_COSINE (1 << 25)
+#define RPT_KNN_METRIC_INNER (1 << 26)
 
 typedef struct rpt_ctx rpt_ctx;
 typedef struct rpt_dataset rpt_dataset;
@@ -391,6 +412,11 @@ int32_t rpt_knn_sharded(rpt_comm* comm, rpt_sharded_forest* sf, const rpt_datase
 /* brute-force exact kNN on the device (evaluation of recall; ties by ascending id) */
 int32_t rpt_brute_knn_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
                            int32_t k, int32_t* ids_host, double* dist_host);
+/* ... under the metric of `flags`: 0 (L2, as rpt_brute_knn_host), RPT_KNN_METRIC_COSINE or
+ * RPT_KNN_METRIC_INNER (the distances defined with those flags; ties by ascending id) */
+int32_t rpt_brute_knn_metric_host(rpt_ctx* ctx, const rpt_dataset* data,
+                                  const rpt_dataset* queries, int32_t k, int32_t flags,
+                                  int32_t* ids_host, double* dist_host);
 
 #ifdef __cplusplus
 }

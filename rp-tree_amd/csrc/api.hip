@@ -634,6 +634,7 @@ int32_t rpt_dataset_free(rpt_dataset* ds) {
     if (ds->shadow32) dev_free(ds->shadow32);
     if (ds->shadow16) dev_free(ds->shadow16);
     if (ds->shadow8) dev_free(ds->shadow8);
+    if (ds->sqnorm) dev_free(ds->sqnorm);
     if (ds->shadow_col16) dev_free(ds->shadow_col16);
     if (ds->shadow_ell) dev_free(ds->shadow_ell);
     if (ds->csr_split) dev_free(ds->csr_split);
@@ -1002,6 +1003,26 @@ int32_t rpt_knnh_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
   });
 }
 
+}  // extern "C"
+
+namespace {
+// the knn flags: dedup rule (0 .. 2), RPT_KNN_VOTE(v), RPT_KNN_METRIC_REFERENCE, one of
+// RPT_KNN_METRIC_COSINE / _INNER (not with the reference metric)
+int32_t check_knn_flags(int32_t flags) {
+  const int32_t metric = flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER);
+  RPT_ARG(flags >= 0 && (flags & ~(0x1ffff03 | RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)) == 0 &&
+              (flags & 3) != 3,
+          "unknown knn flags");
+  RPT_ARG(metric != (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER),
+          "RPT_KNN_METRIC_COSINE and RPT_KNN_METRIC_INNER are exclusive");
+  RPT_ARG(!metric || !(flags & RPT_KNN_METRIC_REFERENCE),
+          "RPT_KNN_METRIC_REFERENCE is an L2 metric: not with RPT_KNN_METRIC_COSINE / _INNER");
+  return RPT_OK;
+}
+}  // namespace
+
+extern "C" {
+
 int32_t rpt_knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
                     const rpt_dataset* queries, int32_t k, int32_t flags, int32_t* ids_dev,
                     double* dist_dev, int32_t* count_dev) {
@@ -1012,7 +1033,7 @@ int32_t rpt_knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
     RPT_ARG(data->n == f->n && data->d == f->d, "data shape differs from the forest's");
     RPT_ARG(data->csr == queries->csr, "data and queries must both be dense or both CSR");
     RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
-    RPT_ARG(flags >= 0 && (flags & ~0x1ffff03) == 0 && (flags & 3) != 3, "unknown knn flags");
+    RPT_TRY(check_knn_flags(flags));
     RPT_ARG(ids_dev && dist_dev && count_dev, "NULL output");
     return knn_dev(ctx, f, data, queries, k, flags, ids_dev, dist_dev, count_dev);
   });
@@ -1026,7 +1047,7 @@ int32_t rpt_knn_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
     RPT_TRY(check_query(ctx, f, queries));
     RPT_ARG(ids_host && dist_host && count_host, "NULL output");
     RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
-    RPT_ARG(flags >= 0 && (flags & ~0x1ffff03) == 0 && (flags & 3) != 3, "unknown knn flags");
+    RPT_TRY(check_knn_flags(flags));
     int64_t nq = queries->n;
     DevBuf<int32_t> ids, cnt;
     DevBuf<double> dist;
@@ -1148,6 +1169,23 @@ int32_t rpt_brute_knn_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_data
     RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
     RPT_HIP(hipSetDevice(ctx->device));
     return brute_knn(ctx, data, queries, k, ids_host, dist_host);
+  });
+}
+
+int32_t rpt_brute_knn_metric_host(rpt_ctx* ctx, const rpt_dataset* data,
+                                  const rpt_dataset* queries, int32_t k, int32_t flags,
+                                  int32_t* ids_host, double* dist_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ctx && data && queries && ids_host && dist_host, "NULL argument");
+    RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
+    RPT_ARG(flags == 0 || flags == RPT_KNN_METRIC_COSINE || flags == RPT_KNN_METRIC_INNER,
+            "flags must be 0, RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER");
+    RPT_ARG(!data->csr && !queries->csr, "brute-force kNN supports dense data only");
+    RPT_ARG(data->d == queries->d && data->dtype == queries->dtype, "shape/dtype mismatch");
+    RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
+    RPT_HIP(hipSetDevice(ctx->device));
+    return brute_knn_metric(ctx, data, queries, k, flags, ids_host, dist_host);
   });
 }
 

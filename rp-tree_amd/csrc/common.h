@@ -272,6 +272,9 @@ struct rpt_dataset {
   mutable int ell_w = 0;
   mutable int ell_state = 0;
   mutable double max_norm = -1.0;
+  // lazily built by the first cosine-metric kNN call on dense data: dot(x, x) of every row as the
+  // reference's left fold (innerDD), [n] doubles
+  mutable double* sqnorm = nullptr;
   // lazily built by the first projection of a CSR dataset whose hyperplane tile does not fit LDS
   // whole: index of every row's first nonzero with column >= csr_split_k (project.hip)
   mutable int64_t* csr_split = nullptr;
@@ -360,6 +363,9 @@ int32_t knn_merge_dev(rpt_ctx* ctx, const int32_t* ids_dev, const double* dist_d
                       int32_t* out_count);
 int32_t brute_knn(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
                   int32_t* ids_host, double* dist_host);
+// metric: 0 = L2 (brute_knn), RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER
+int32_t brute_knn_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
+                         int32_t metric, int32_t* ids_host, double* dist_host);
 int32_t knn_h(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
               int32_t k, int64_t* off_host, int32_t* ids_host, double* dist_host, int64_t cap,
               int64_t* total);

@@ -414,7 +414,18 @@ struct Entry {
 __device__ inline bool entry_less(const Entry& a, const Entry& b) {
   return a.dist < b.dist || (a.dist == b.dist && a.pos < b.pos);
 }
+// The total order of the metric kernels and of the multi-GPU merge, whatever the values are:
+// numbers by (distance, position), then NaN distances by position (the rule finalize_leftfold
+// applies), then unused slots (id -1) by position.  entry_less leaves NaN unordered.
+__device__ inline int entry_class(const Entry& e) { return e.id < 0 ? 2 : (e.dist != e.dist ? 1 : 0); }
+__device__ inline bool entry_less_total(const Entry& a, const Entry& b) {
+  const int ca = entry_class(a), cb = entry_class(b);
+  if (ca != cb) return ca < cb;
+  if (ca == 0 && a.dist != b.dist) return a.dist < b.dist;
+  return a.pos < b.pos;
+}
 
+template <bool TOTAL = false>
 __device__ inline void bitonic_entries(Entry* e, int np) {
   for (int k = 2; k <= np; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
@@ -423,7 +434,12 @@ __device__ inline void bitonic_entries(Entry* e, int np) {
         const int hi = lo | j;
         const bool up = (lo & k) == 0;
         const Entry a = e[lo], b = e[hi];
-        if (up ? entry_less(b, a) : entry_less(a, b)) {
+        if constexpr (TOTAL) {
+          if (up ? entry_less_total(b, a) : entry_less_total(a, b)) {
+            e[lo] = b;
+            e[hi] = a;
+          }
+        } else if (up ? entry_less(b, a) : entry_less(a, b)) {
           e[lo] = b;
           e[hi] = a;
         }
@@ -435,13 +451,16 @@ __device__ inline void bitonic_entries(Entry* e, int np) {
 // Merge step: sort buf[0, np) and keep the best k (optionally unique ids) at the front.
 // Returns the number of valid best entries.  All threads call; `scratch` is int[kBuf].
 // dedup: 0 keep duplicates (knn), 1 each id once, 2 each DISTANCE once (knnPQ's `nub`)
+// TOTAL: order by entry_less_total (NaN distances last); under dedup 1 two NaN distances of one id
+// are one entry, under dedup 2 NaN equals nothing (`nub` compares with ==)
+template <bool TOTAL = false>
 __device__ int merge_best(Entry* buf, int filled, int k, int dedup, int* scratch) {
   int np = 1;
   while (np < filled) np <<= 1;
   for (int i = filled + threadIdx.x; i < np; i += blockDim.x)
     buf[i] = Entry{__longlong_as_double(0x7ff0000000000000LL), 0x7fffffff, -1};
   __syncthreads();
-  bitonic_entries(buf, np);
+  bitonic_entries<TOTAL>(buf, np);
   if (!dedup) return filled < k ? filled : k;
   // same id => same distance (deterministic distance function): a duplicate sits in the run
   // of equal distances before it
@@ -450,11 +469,20 @@ __device__ int merge_best(Entry* buf, int filled, int k, int dedup, int* scratch
     if (dedup == 2) {
       dup = i > 0 && buf[i - 1].dist == buf[i].dist;
     } else {
-      for (int j = i - 1; j >= 0 && buf[j].dist == buf[i].dist; --j)
-        if (buf[j].id == buf[i].id) {
-          dup = 1;
-          break;
-        }
+      if constexpr (TOTAL) {
+        const double di = buf[i].dist;
+        for (int j = i - 1; j >= 0 && (buf[j].dist == di || (di != di && buf[j].dist != buf[j].dist)); --j)
+          if (buf[j].id == buf[i].id) {
+            dup = 1;
+            break;
+          }
+      } else {
+        for (int j = i - 1; j >= 0 && buf[j].dist == buf[i].dist; --j)
+          if (buf[j].id == buf[i].id) {
+            dup = 1;
+            break;
+          }
+      }
     }
     scratch[i] = dup;
   }
@@ -534,17 +562,70 @@ __device__ inline double leftfold_distance(const double* __restrict__ x, const d
 // path certifies its cut per query instead.
 constexpr int kLfMargin = 8;
 
+// ---- cosine and inner-product metrics (RPT_KNN_METRIC_COSINE / _INNER) ----
+// The reference's knn takes the distance as an argument (RPTree.hs:168-176); these two are
+//     inner :  -dot(x, q)                                   knn (\x q -> negate (inner x q))
+//     cosine:  1 - dot(x, q) / (sqrt(dot(x, x)) * sqrt(dot(q, q)))
+// with dot = innerDD (Internal.hs:384-385), the left fold ((0 + x0 q0) + x1 q1) + ... in Double over
+// the exactly widened elements, every product and sum rounded on its own (no FMA).  A zero row or
+// query has cosine NaN.  Smaller is nearer for both.
+constexpr int kMetricL2 = 0, kMetricCosine = 1, kMetricInner = 2;
+
+template <int METRIC>
+__device__ __forceinline__ double metric_value(double dot, double xx, double qq) {
+  if constexpr (METRIC == kMetricInner) return -dot;
+  else return 1.0 - dot / (sqrt(xx) * sqrt(qq));
+}
+
+// innerDD as the reference folds it, one thread per row: eight 16-byte loads in flight, the sum a
+// left fold whatever the grouping of the loads.  SELF: dot(x, x) (qs unused).
+template <class TD, bool SELF = false>
+__device__ inline double leftfold_dot(const TD* __restrict__ x, const double* qs, int d) {
+  constexpr int V = 16 / (int)sizeof(TD);
+  double acc = 0.0;
+  int j = 0;
+  if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+    struct alignas(16) Raw { TD v[V]; };
+    for (; j + 8 * V <= d; j += 8 * V) {
+      Raw r[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) r[u] = *reinterpret_cast<const Raw*>(x + j + u * V);
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const double xv = (double)ld<TD>(&r[u].v[v]);
+          acc = acc + xv * (SELF ? xv : qs[j + u * V + v]);
+        }
+    }
+  }
+  for (; j < d; ++j) {
+    const double xv = (double)ld<TD>(x + j);
+    acc = acc + xv * (SELF ? xv : qs[j]);
+  }
+  return acc;
+}
+
 // Final stage of those paths: m kept entries (ids / positions in bid / bpos, m <= capacity of lf
 // and order) -> left-fold distances, order by (distance, position), the duplicate rule on the
 // FINAL values (dedup 2 = knnPQ's nub: one entry per distance; dedup 1: the kept ids are distinct
 // already), the first k written.  tid / nthr / sync: the threads that share the arrays.
-template <class Sync>
-__device__ inline void finalize_leftfold(const double* __restrict__ X, int d, const double* qs, int m,
+// METRIC != L2: the rows are TX (f64 / f32 / bf16), the values metric_value of the left-fold dot,
+// rn the rows' dot(x, x) (cosine), qq the query's.
+template <int METRIC = kMetricL2, class TX = double, class Sync>
+__device__ inline void finalize_leftfold(const TX* __restrict__ X, int d, const double* qs, int m,
                                          int k, int dedup, double* lf, int* order, const int* bid,
                                          const int* bpos, int tid, int nthr, Sync sync, int64_t q,
                                          int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
-                                         int32_t* __restrict__ out_cnt) {
-  for (int i = tid; i < m; i += nthr) lf[i] = leftfold_distance(X + (int64_t)bid[i] * d, qs, d);
+                                         int32_t* __restrict__ out_cnt,
+                                         const double* __restrict__ rn = nullptr, double qq = 0.0) {
+  for (int i = tid; i < m; i += nthr) {
+    if constexpr (METRIC == kMetricL2)
+      lf[i] = leftfold_distance(X + (int64_t)bid[i] * d, qs, d);
+    else
+      lf[i] = metric_value<METRIC>(leftfold_dot<TX>(X + (int64_t)bid[i] * d, qs, d),
+                                   METRIC == kMetricCosine ? rn[bid[i]] : 0.0, qq);
+  }
   sync();
   for (int i = tid; i < m; i += nthr) {
     const double di = lf[i];
@@ -683,9 +764,11 @@ __global__ __launch_bounds__(256) void topk_dense_kernel(
 // written to cdist.  The waves taking part are numbered slot = 0 .. nslots-1; every row is
 // reduced by the same fixed butterfly whichever wave handles it, so the value does not depend
 // on the kernel variant.  Each wave keeps EIGHT load instructions in flight.
+// DOT (the cosine / inner-product kernel): the row's inner product with the query, sum of x * q,
+// instead of its squared distance (use with SQRT = false); the loads and the reduction are the same.
 template <class TD, class TA, int INFL = 8 /* load instructions in flight per wave */,
           bool SQRT = true /* false: leave the squared distance (a TA value) in cdist */,
-          class TO = double /* element type of the batch values */>
+          class TO = double /* element type of the batch values */, bool DOT = false>
 __device__ __forceinline__ void batch_distances(const TD* __restrict__ X, int d, const int* cid,
                                        TO* cdist, const TA* qs, int first, int fill, int slot,
                                        int nslots, int lane) {
@@ -708,8 +791,12 @@ __device__ __forceinline__ void batch_distances(const TD* __restrict__ X, int d,
         s[u] = (TA)0;
 #pragma unroll
         for (int v = 0; v < VV; ++v) {
-          const TA df = ld<TD>(&x[u].v[v]) - qs[jl + v];
-          s[u] += df * df;
+          if constexpr (DOT) {
+            s[u] += ld<TD>(&x[u].v[v]) * qs[jl + v];
+          } else {
+            const TA df = ld<TD>(&x[u].v[v]) - qs[jl + v];
+            s[u] += df * df;
+          }
         }
         for (int o = lpr >> 1; o > 0; o >>= 1) s[u] += __shfl_xor(s[u], o);  // fixed butterfly
         const int i = i0 + u * rpw + sub;
@@ -744,7 +831,7 @@ __device__ __forceinline__ void batch_distances(const TD* __restrict__ X, int d,
 #pragma unroll
         for (int u = 0; u < 8; ++u) raw[u] = *reinterpret_cast<const u32x4*>(rows[u] + j);
         __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);          // eight VMEM reads ...
-        __builtin_amdgcn_sched_group_barrier(0x002, 8 * V * 3, 0);  // ... then the VALU work on them
+        __builtin_amdgcn_sched_group_barrier(0x002, 8 * V * (DOT ? 2 : 3), 0);  // ... then the VALU work on them
         Raw x[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) __builtin_memcpy(&x[u], &raw[u], 16);
@@ -752,8 +839,12 @@ __device__ __forceinline__ void batch_distances(const TD* __restrict__ X, int d,
         for (int u = 0; u < 8; ++u)
 #pragma unroll
           for (int v = 0; v < V; ++v) {
-            const TA df = ld<TD>(&x[u].v[v]) - qs[j + v];
-            s[u] += df * df;
+            if constexpr (DOT) {
+              s[u] += ld<TD>(&x[u].v[v]) * qs[j + v];
+            } else {
+              const TA df = ld<TD>(&x[u].v[v]) - qs[j + v];
+              s[u] += df * df;
+            }
           }
       }
     } else {
@@ -761,8 +852,12 @@ __device__ __forceinline__ void batch_distances(const TD* __restrict__ X, int d,
         const TA qj = qs[j];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-          const TA df = ld<TD>(rows[u] + j) - qj;
-          s[u] += df * df;
+          if constexpr (DOT) {
+            s[u] += ld<TD>(rows[u] + j) * qj;
+          } else {
+            const TA df = ld<TD>(rows[u] + j) - qj;
+            s[u] += df * df;
+          }
         }
       }
     }
@@ -772,6 +867,118 @@ __device__ __forceinline__ void batch_distances(const TD* __restrict__ X, int d,
       if (lane == 0 && i0 + u < fill) cdist[i0 + u] = SQRT ? (TO)sqrt((double)tot) : (TO)tot;
     }
   }
+}
+
+// ---- cosine / inner-product kernel ---------------------------------------------------------
+constexpr int kMB = 512;  // candidates per batch of knn_metric_kernel
+constexpr int kMW = 64;   // leaf ranges it holds in LDS at a time
+
+// dot(x, x) of every row as the left fold (the cosine metric's row norms, cached on the dataset)
+template <class TD>
+__global__ __launch_bounds__(256) void row_sqnorm_kernel(const TD* __restrict__ X, int64_t n, int d,
+                                                         double* __restrict__ rn) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r < n) rn[r] = leftfold_dot<TD, true>(X + r * d, nullptr, d);
+}
+
+// knn under the cosine or inner-product metric, dense rows of any dtype, values in f64.  One
+// workgroup (four waves) per query over the plan's leaf ranges in candidate order (or, identity:
+// the whole dataset in id order, the brute force).  Batches of kMB candidates: ids and positions
+// gathered across ranges, dots by batch_distances (the butterfly f64 sum, 16-byte row loads, the
+// short-row layout up to 512-byte rows), the metric value, and only the entries that beat the
+// current (k + kLfMargin)-th best in the total order appended to buf; merge_best<true> keeps the
+// best when the next batch might not fit.  The kept entries are evaluated again as the left fold and
+// selected in the finalize_leftfold order (NaN last, by position).  LDS: buf [nbuf] entries (a power
+// of two >= kk + kMB), scratch [nbuf] ints, the batch (kMB x 16 B), the query [d] doubles.
+template <class TD, int METRIC>
+__global__ __launch_bounds__(256) void knn_metric_kernel(
+    const TD* __restrict__ X, int d, const TD* __restrict__ Q, const int32_t* __restrict__ perm,
+    const Range* __restrict__ ranges, const int64_t* __restrict__ rng_off, int T, int64_t N,
+    int identity, int nbuf, int k, int dedup, const double* __restrict__ rn,
+    int32_t* __restrict__ out_ids, double* __restrict__ out_dist, int32_t* __restrict__ out_cnt) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  Entry* buf = reinterpret_cast<Entry*>(smem);                      // [nbuf]
+  int* scratch = reinterpret_cast<int*>(smem + sizeof(Entry) * nbuf);  // [nbuf]
+  double* cd = reinterpret_cast<double*>(scratch + nbuf);           // [kMB]
+  int* cid = reinterpret_cast<int*>(cd + kMB);                      // [kMB]
+  int* cpos = cid + kMB;                                            // [kMB]
+  double* qs = reinterpret_cast<double*>(cpos + kMB);               // [d]
+  __shared__ Range s_rng[kMW];
+  __shared__ int s_fill;
+  __shared__ double s_qq;
+  const int64_t q = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int j = threadIdx.x; j < d; j += blockDim.x) qs[j] = (double)ld<TD>(Q + q * d + j);
+  if (threadIdx.x == 0) s_fill = 0;
+  __syncthreads();
+  // dot(q, q) (read after the first batch's barriers); the elements in LDS are the widened query
+  if (METRIC == kMetricCosine && threadIdx.x == 0) s_qq = leftfold_dot<double, true>(qs, nullptr, d);
+
+  const int kk = k + kLfMargin < nbuf / 2 ? k + kLfMargin : nbuf / 2;
+  int best = 0;
+  Entry thr{0.0, 0, -1};  // the kk-th best so far; id -1: none yet, every entry enters
+  const int64_t r0 = identity ? 0 : rng_off[q * T];
+  const int64_t r1 = identity ? 1 : rng_off[(q + 1) * T];
+  int64_t r = r0, w0 = r0, w1 = r0;  // next range; ranges [w0, w1) are in s_rng
+  int done = 0;                      // candidates of range r already taken
+  while (r < r1) {
+    int nb = 0;
+    while (nb < kMB && r < r1) {  // block-uniform
+      if (r == w1) {
+        __syncthreads();
+        w0 = r;
+        w1 = r + kMW < r1 ? r + kMW : r1;
+        for (int i = threadIdx.x; i < w1 - w0; i += blockDim.x)
+          s_rng[i] = identity ? Range{0, (int32_t)N, 0} : ranges[w0 + i];
+        __syncthreads();
+      }
+      const Range rg = s_rng[r - w0];
+      int take = rg.n - done;
+      if (take > kMB - nb) take = kMB - nb;
+      for (int i = threadIdx.x; i < take; i += blockDim.x) {
+        const int c = done + i;
+        cid[nb + i] = identity ? c : perm[rg.poff + c];
+        cpos[nb + i] = rg.pos + c;
+      }
+      nb += take;
+      done += take;
+      if (done == rg.n) {
+        ++r;
+        done = 0;
+      }
+    }
+    __syncthreads();
+    batch_distances<TD, double, 8, false, double, true>(X, d, cid, cd, qs, 0, nb, wave, 4, lane);
+    __syncthreads();
+    const double qq = METRIC == kMetricCosine ? s_qq : 0.0;
+    // the order inside buf does not matter (merge_best sorts by value and position)
+    for (int i = threadIdx.x; i < nb; i += blockDim.x) {
+      const Entry e{metric_value<METRIC>(cd[i], METRIC == kMetricCosine ? rn[cid[i]] : 0.0, qq), cpos[i],
+                    cid[i]};
+      if (entry_less_total(e, thr)) buf[atomicAdd(&s_fill, 1)] = e;
+    }
+    __syncthreads();
+    const int filled = s_fill;
+    if (filled + kMB > nbuf || r >= r1) {
+      best = merge_best<true>(buf, filled, kk, dedup, scratch);
+      if (best == kk) thr = buf[kk - 1];
+      __syncthreads();
+      if (threadIdx.x == 0) s_fill = best;
+      __syncthreads();
+    }
+  }
+  double* lf = reinterpret_cast<double*>(scratch);        // nbuf / 2 doubles >= kk
+  int* ids2 = reinterpret_cast<int*>(buf + nbuf / 2);     // the upper half of buf is free now:
+  int* pos2 = ids2 + nbuf / 2;                            // 3 x nbuf / 2 ints fit its 8 x nbuf bytes
+  int* order = pos2 + nbuf / 2;
+  for (int i = threadIdx.x; i < best; i += blockDim.x) {
+    ids2[i] = buf[i].id;
+    pos2[i] = buf[i].pos;
+  }
+  __syncthreads();
+  finalize_leftfold<METRIC>(X, d, qs, best, k, dedup, lf, order, ids2, pos2, (int)threadIdx.x,
+                            (int)blockDim.x, [] { __syncthreads(); }, q, out_ids, out_dist, out_cnt, rn,
+                            METRIC == kMetricCosine ? s_qq : 0.0);
 }
 
 // ---- int8 ranking tier (round 3) ----------------------------------------------------------
@@ -3167,7 +3374,10 @@ __global__ __launch_bounds__(256) void merge_kernel(const int32_t* __restrict__ 
   __syncthreads();
   int valid = 0;
   for (int g = 0; g < G; ++g) valid += shard_cnt(g);
-  int best = merge_best(buf, total, k, dedup, scratch);
+  // the total order: NaN distances (a NaN query, a zero row under the cosine metric) rank behind
+  // every number and among themselves by shard position, as on one device; negative distances
+  // (the inner-product metric) are ordinary numbers
+  int best = merge_best<true>(buf, total, k, dedup, scratch);
   // merge_best counted +inf padding as entries: clamp to the valid ones (dedup can only
   // shrink further; invalid entries have id -1 and sort last)
   __syncthreads();
@@ -3534,6 +3744,98 @@ static int32_t ensure_shadow8(rpt_ctx* ctx, const rpt_dataset* data) {
   data->shadow8_state = 1;
   if (ctx->opt.debug_host)
     fprintf(stderr, "int8 shadow: scale %.6g (max |x| %.6g), max row error %.6g\n", s, mabs, data->s8_emax);
+  return RPT_OK;
+}
+
+// The cosine metric's row norms dot(x, x), once per dataset (8 bytes per row, freed with it).  Unlike
+// the shadows this is not optional: without it the metric cannot be evaluated.
+static int32_t ensure_sqnorm(rpt_ctx* ctx, const rpt_dataset* data) {
+  if (data->sqnorm) return RPT_OK;
+  DevBuf<double> rn;
+  RPT_TRY(rn.alloc((size_t)data->n + 1));
+  const unsigned blocks = (unsigned)((data->n + 255) / 256);
+  if (blocks > 0) {
+    if (data->dtype == RPT_F64)
+      hipLaunchKernelGGL(row_sqnorm_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream,
+                         (const double*)data->X, data->n, data->d, rn.p);
+    else if (data->dtype == RPT_F32)
+      hipLaunchKernelGGL(row_sqnorm_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream,
+                         (const float*)data->X, data->n, data->d, rn.p);
+    else
+      hipLaunchKernelGGL(row_sqnorm_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, ctx->stream,
+                         (const __hip_bfloat16*)data->X, data->n, data->d, rn.p);
+    RPT_HIP(hipGetLastError());
+  }
+  data->sqnorm = rn.p;
+  rn.p = nullptr;  // owned by the dataset now
+  return RPT_OK;
+}
+
+static size_t metric_smem(int nbuf, int d) {
+  return (sizeof(Entry) + 4) * (size_t)nbuf + (size_t)kMB * 16 + (size_t)d * 8;
+}
+
+template <class TD, int METRIC>
+static int32_t launch_metric_t(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
+                               const int32_t* perm, const Range* ranges, const int64_t* rng_off, int T,
+                               int identity, int k, int dedup, int32_t* ids, double* dist, int32_t* cnt) {
+  // buf holds the kept kk = k + kLfMargin (at most nbuf / 2) and one batch
+  const int nbuf = k + kLfMargin + kMB <= 1024 ? 1024 : kBuf;
+  const size_t smem = metric_smem(nbuf, data->d);
+  RPT_ARG(smem <= 150 * 1024, "d too large");
+  if (smem > 64 * 1024)
+    RPT_HIP(hipFuncSetAttribute((const void*)knn_metric_kernel<TD, METRIC>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
+  hipLaunchKernelGGL((knn_metric_kernel<TD, METRIC>), dim3((unsigned)q->n), dim3(256), smem, ctx->stream,
+                     (const TD*)data->X, data->d, (const TD*)q->X, perm, ranges, rng_off, T, data->n,
+                     identity, nbuf, k, dedup, (const double*)data->sqnorm, ids, dist, cnt);
+  RPT_HIP(hipGetLastError());
+  return RPT_OK;
+}
+
+template <class TD>
+static int32_t launch_metric_td(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
+                                const int32_t* perm, const Range* ranges, const int64_t* rng_off, int T,
+                                int identity, int k, int dedup, int metric, int32_t* ids, double* dist,
+                                int32_t* cnt) {
+  if (metric == RPT_KNN_METRIC_COSINE)
+    return launch_metric_t<TD, kMetricCosine>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup,
+                                              ids, dist, cnt);
+  return launch_metric_t<TD, kMetricInner>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, ids,
+                                           dist, cnt);
+}
+
+// the cosine / inner-product kernel over the query plan (batch and streamed forests alike) or, with
+// identity, over the whole dataset (brute force; ties by id)
+static int32_t launch_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
+                             const int32_t* perm, const Range* ranges, const int64_t* rng_off, int T,
+                             int identity, int k, int dedup, int metric, int32_t* ids, double* dist,
+                             int32_t* cnt) {
+  if (metric == RPT_KNN_METRIC_COSINE) RPT_TRY(ensure_sqnorm(ctx, data));
+  if (data->dtype == RPT_F64)
+    return launch_metric_td<double>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, metric, ids,
+                                    dist, cnt);
+  if (data->dtype == RPT_F32)
+    return launch_metric_td<float>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, metric, ids,
+                                   dist, cnt);
+  return launch_metric_td<__hip_bfloat16>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup,
+                                          metric, ids, dist, cnt);
+}
+
+static int32_t knn_metric(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                          int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  ctx->last_uncertified = 0;
+  ctx->last_retries = 0;
+  ctx->last_tier = 0;
+  QueryPlan pl;
+  RPT_TRY(make_plan(ctx, f, q, pl));
+  ctx->last_candidates = pl.total_cand;
+  if (q->n == 0) return RPT_OK;
+  RPT_TRY(launch_metric(ctx, data, q, f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, 0, k, flags & 3,
+                        flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER), ids_dev, dist_dev,
+                        count_dev));
+  RPT_HIP(stream_sync(ctx->stream));  // the plan's buffers are released on return
   return RPT_OK;
 }
 
@@ -3998,6 +4300,12 @@ int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_
   RPT_ARG(proj_dtype(q->dtype) == f->pdtype,
           "query dtype must have the forest's projection type (f64 vs f32/bf16)");
   const int vote = (flags >> 8) & 0xffff;  // RPT_KNN_VOTE(v)
+  if (flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)) {
+    if (data->csr)
+      return fail(RPT_E_UNSUPPORTED, "RPT_KNN_METRIC_COSINE / _INNER: dense data only");
+    if (vote > 0) return fail(RPT_E_UNSUPPORTED, "RPT_KNN_METRIC_COSINE / _INNER: no voting (RPT_KNN_VOTE)");
+    return knn_metric(ctx, f, data, q, k, flags, ids_dev, dist_dev, count_dev);
+  }
   // (the fused kernels walk the implicit batch topology: streamed forests take the general path;
   // so do SVector rows under the reference's own truncating metric)
   const bool refm = data->csr && (flags & RPT_KNN_METRIC_REFERENCE);
@@ -4315,6 +4623,24 @@ int32_t brute_knn(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, i
   else
     RPT_TRY(launch_topk_dense<__hip_bfloat16>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0,
                                               ids.p, dist.p, cnt.p));
+  RPT_HIP(stream_sync(ctx->stream));
+  RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+  RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+  return RPT_OK;
+}
+
+int32_t brute_knn_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
+                         int32_t metric, int32_t* ids_host, double* dist_host) {
+  if (metric == 0) return brute_knn(ctx, data, q, k, ids_host, dist_host);
+  RPT_ARG(k <= kBuf / 2, "k too large");
+  const int64_t nq = q->n;
+  if (nq == 0) return RPT_OK;
+  DevBuf<int32_t> ids, cnt;
+  DevBuf<double> dist;
+  RPT_TRY(ids.alloc((size_t)nq * k));
+  RPT_TRY(dist.alloc((size_t)nq * k));
+  RPT_TRY(cnt.alloc((size_t)nq));
+  RPT_TRY(launch_metric(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, metric, ids.p, dist.p, cnt.p));
   RPT_HIP(stream_sync(ctx->stream));
   RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
   RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));

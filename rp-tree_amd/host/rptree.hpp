@@ -223,29 +223,40 @@ inline RPForest forest(Context& ctx, uint64_t seed, int maxd, int minl, int ntre
   return RPForest(ctx, src, std::move(rvss), maxd, minl, chunksize);
 }
 
-// knn metricL2 k forest q  (RPTree.hs:168-176): (distance, point id), duplicates kept
-inline std::vector<std::pair<double, int32_t>> knn(const RPForest& tts, int k, const DVector& q) {
+// The distance `knn` ranks by (the reference's distf argument): metricL2, or the cosine / negated
+// inner-product distances of RPT_KNN_METRIC_COSINE / RPT_KNN_METRIC_INNER (include/rptree_hip.h:
+// every value in double, the dots a left fold; dense data only)
+enum class Metric { L2, Cosine, Inner };
+
+inline int32_t metric_flags(Metric m) {
+  return m == Metric::Cosine ? RPT_KNN_METRIC_COSINE : m == Metric::Inner ? RPT_KNN_METRIC_INNER : 0;
+}
+
+// knn distf k forest q  (RPTree.hs:168-176): (distance, point id), duplicates kept
+inline std::vector<std::pair<double, int32_t>> knn(const RPForest& tts, int k, const DVector& q,
+                                                   Metric metric = Metric::L2) {
   std::vector<DVector> qv{q};
   Dataset qs(*tts.ctx, qv);
   std::vector<int32_t> ids((size_t)k);
   std::vector<double> dist((size_t)k);
   int32_t cnt = 0;
   check(rpt_knn_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), k,
-                     RPT_KNN_KEEP_DUPLICATES, ids.data(), dist.data(), &cnt));
+                     RPT_KNN_KEEP_DUPLICATES | metric_flags(metric), ids.data(), dist.data(), &cnt));
   std::vector<std::pair<double, int32_t>> out;
   for (int i = 0; i < cnt; ++i) out.push_back({dist[(size_t)i], ids[(size_t)i]});
   return out;
 }
 
-// knnPQ metricL2 k forest q  (RPTree.hs:181-194): like knn, one entry per distance (`nub`)
-inline std::vector<std::pair<double, int32_t>> knnPQ(const RPForest& tts, int k, const DVector& q) {
+// knnPQ distf k forest q  (RPTree.hs:181-194): like knn, one entry per distance (`nub`)
+inline std::vector<std::pair<double, int32_t>> knnPQ(const RPForest& tts, int k, const DVector& q,
+                                                     Metric metric = Metric::L2) {
   std::vector<DVector> qv{q};
   Dataset qs(*tts.ctx, qv);
   std::vector<int32_t> ids((size_t)k);
   std::vector<double> dist((size_t)k);
   int32_t cnt = 0;
   check(rpt_knn_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), k,
-                     RPT_KNN_DEDUP_DISTANCE, ids.data(), dist.data(), &cnt));
+                     RPT_KNN_DEDUP_DISTANCE | metric_flags(metric), ids.data(), dist.data(), &cnt));
   std::vector<std::pair<double, int32_t>> out;
   for (int i = 0; i < cnt; ++i) out.push_back({dist[(size_t)i], ids[(size_t)i]});
   return out;

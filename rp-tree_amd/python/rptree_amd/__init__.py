@@ -23,7 +23,8 @@ import numpy as np
 
 from . import gen
 from ._lib import (RPT_BF16, RPT_F32, RPT_F64, RPT_KNN_DEDUP, RPT_KNN_DEDUP_DISTANCE,
-                   RPT_KNN_KEEP_DUPLICATES, RPT_KNN_METRIC_REFERENCE,
+                   RPT_KNN_KEEP_DUPLICATES, RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER,
+                   RPT_KNN_METRIC_REFERENCE,
                    RPT_PROJ_AUTO, RPT_PROJ_EXACT, RPT_PROJ_MFMA, RPTError, check, lib)
 
 __all__ = [
@@ -33,6 +34,7 @@ __all__ = [
     "treeSize", "leafSizes", "metricL2", "inner", "project", "splitSegments", "topology",
     "bruteKnn", "RPTError", "forest", "tree", "saveForest", "loadForest", "importForest",
     "knnH", "knnHBatch", "knnPQ", "candidatesBatch", "to_bf16", "from_bf16", "RPStreamForest",
+    "metricCosine", "metricInner",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -676,6 +678,48 @@ def metricL2(u, v):
     return float(np.sqrt(np.sum((a - b) ** 2)))
 
 
+def _dense_f64(u):
+    # f32 elements (and bf16 ones, given as their float values: from_bf16) widen exactly
+    return np.asarray(u.dvVec if isinstance(u, DVector) else u).astype(np.float64).ravel().tolist()
+
+
+def _dot_fold(a, b):
+    """innerDD (Internal.hs:384-385): ((0 + a0 b0) + a1 b1) + ..., each product and sum rounded."""
+    acc = 0.0
+    for x, y in zip(a, b):
+        acc = acc + x * y
+    return acc
+
+
+def metricInner(u, v):
+    """-(inner u v): the inner-product distance of the device's RPT_KNN_METRIC_INNER (maximum
+    inner-product search; smaller is nearer), the dot a left fold in Double from +0.0."""
+    return -_dot_fold(_dense_f64(u), _dense_f64(v))
+
+
+def metricCosine(u, v):
+    """1 - inner u v / (sqrt (inner u u) * sqrt (inner v v)): the cosine distance of the device's
+    RPT_KNN_METRIC_COSINE, every dot a left fold in Double; NaN when u or v is zero."""
+    a, b = _dense_f64(u), _dense_f64(v)
+    den = np.float64(math.sqrt(_dot_fold(a, a))) * np.float64(math.sqrt(_dot_fold(b, b)))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        return float(1.0 - np.float64(_dot_fold(a, b)) / den)
+
+
+_METRIC_FLAGS = {metricL2: 0, metricCosine: RPT_KNN_METRIC_COSINE, metricInner: RPT_KNN_METRIC_INNER}
+
+
+def _metric_flag(metric):
+    """None / metricL2 / metricCosine / metricInner -> the knn flag bits of the device metric."""
+    if metric is None:
+        return 0
+    try:
+        return _METRIC_FLAGS[metric]
+    except (KeyError, TypeError):
+        raise NotImplementedError(
+            "the device evaluates metricL2, metricCosine and metricInner only") from None
+
+
 # ---------------------------------------------------------------------------------------
 # queries
 # ---------------------------------------------------------------------------------------
@@ -700,7 +744,7 @@ def candidatesBatch(forest, qs):
     return off, ids[:total.value]
 
 
-def knnBatch(k, forest, qs, dedup=False, vote=0, reference_metric=False):
+def knnBatch(k, forest, qs, dedup=False, vote=0, reference_metric=False, metric=None):
     """knn for a batch of queries -> (ids[nq][k], dist[nq][k], count[nq]).
     dedup: False = the reference's knn (duplicates kept), True = each id once,
     RPT_KNN_DEDUP_DISTANCE = knnPQ's `nub` (one entry per distance).
@@ -708,7 +752,9 @@ def knnBatch(k, forest, qs, dedup=False, vote=0, reference_metric=False):
     reference's commented-out counts / keepCounts, RPTree.hs:464-478), ties by ascending id.
     reference_metric: SVector data are ranked by the reference's own metricSSL2 (Internal.hs:
     389-393: the merge of the index lists stops at the shorter vector's end) instead of the true
-    Euclidean distance."""
+    Euclidean distance.
+    metric: None / metricL2, metricCosine or metricInner (dense data; RPT_KNN_METRIC_COSINE /
+    _INNER: every value in f64, bit-exact to those host functions)."""
     ctx = forest.ctx
     qd, nq = _query_dataset(ctx, forest.data, qs)
     ids = np.empty((nq, k), dtype=np.int32)
@@ -719,6 +765,7 @@ def knnBatch(k, forest, qs, dedup=False, vote=0, reference_metric=False):
     flags |= int(vote) << 8                       # RPT_KNN_VOTE(v)
     if reference_metric:                          # SVector data: the truncating metricSSL2
         flags |= RPT_KNN_METRIC_REFERENCE
+    flags |= _metric_flag(metric)
     check(lib().rpt_knn_host(ctx._h, forest._h, forest.data._h, qd._h, int(k), flags, _vp(ids),
                              _vp(dist), _vp(cnt)))
     return ids, dist, cnt
@@ -735,19 +782,18 @@ def knn_last_uncertified(ctx=None):
 def knn(distf, k, tts, q, dedup=False):
     """RPTree.hs:168-176: `knn distf k forest q` -> [(distance, point id)] in increasing
     distance order, duplicates across trees kept (the reference never de-duplicates).
-    Only distf = metricL2 is accelerated (the metric is evaluated on the device)."""
-    if distf is not metricL2:
-        raise NotImplementedError("the device path evaluates metricL2 only")
-    ids, dist, cnt = knnBatch(k, tts, q, dedup=dedup)
+    distf = metricL2, metricCosine or metricInner (the metric is evaluated on the device)."""
+    _metric_flag(distf)                           # anything else: NotImplementedError
+    ids, dist, cnt = knnBatch(k, tts, q, dedup=dedup, metric=distf)
     return [(float(dist[0, i]), int(ids[0, i])) for i in range(int(cnt[0]))]
 
 
 def knnPQ(distf, k, tts, q):
     """RPTree.hs:181-194: like knn, but the heap's `nub` keeps ONE entry per distance value
-    (the first in candidate order here; the reference's pick among ties depends on the heap)."""
-    if distf is not metricL2:
-        raise NotImplementedError("the device path evaluates metricL2 only")
-    ids, dist, cnt = knnBatch(k, tts, q, dedup=RPT_KNN_DEDUP_DISTANCE)
+    (the first in candidate order here; the reference's pick among ties depends on the heap).
+    distf = metricL2, metricCosine or metricInner."""
+    _metric_flag(distf)
+    ids, dist, cnt = knnBatch(k, tts, q, dedup=RPT_KNN_DEDUP_DISTANCE, metric=distf)
     return [(float(dist[0, i]), int(ids[0, i])) for i in range(int(cnt[0]))]
 
 
@@ -778,22 +824,28 @@ def knnH(distf, k, tts, q):
     return [(float(dist[i]), int(ids[i])) for i in range(int(off[0]), int(off[1]))]
 
 
-def bruteKnn(forest_or_data, qs, k, ctx=None):
+def bruteKnn(forest_or_data, qs, k, ctx=None, metric=None):
+    """exhaustive kNN on the device, ties by ascending id; metric: None / metricL2, metricCosine or
+    metricInner"""
     data = forest_or_data.data if isinstance(forest_or_data, RPForest) else forest_or_data
     ctx = ctx or data.ctx
     qd, nq = _query_dataset(ctx, data, qs)
     ids = np.empty((nq, k), dtype=np.int32)
     dist = np.empty((nq, k), dtype=np.float64)
-    check(lib().rpt_brute_knn_host(ctx._h, data._h, qd._h, int(k), _vp(ids), _vp(dist)))
+    flags = _metric_flag(metric)
+    if flags:
+        check(lib().rpt_brute_knn_metric_host(ctx._h, data._h, qd._h, int(k), flags, _vp(ids),
+                                              _vp(dist)))
+    else:
+        check(lib().rpt_brute_knn_host(ctx._h, data._h, qd._h, int(k), _vp(ids), _vp(dist)))
     return ids, dist
 
 
 def recallWith(distf, tt, k, q):
     """RPTree.hs:259-282: mean over trees of |candidates(tree, q) ∩ true kNN| / k, the truth by
-    brute force over all points."""
-    if distf is not metricL2:
-        raise NotImplementedError("the device path evaluates metricL2 only")
-    true_ids, _ = bruteKnn(tt, q, k)
+    brute force over all points under distf (metricL2, metricCosine or metricInner)."""
+    _metric_flag(distf)
+    true_ids, _ = bruteKnn(tt, q, k, metric=distf)
     kk = set(int(i) for i in true_ids[0] if i >= 0)
     off, ids = candidatesBatch(tt, q)
     rs = []

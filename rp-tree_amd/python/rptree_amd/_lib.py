@@ -15,6 +15,7 @@ RPT_F64, RPT_F32, RPT_BF16 = 0, 1, 2
 RPT_PROJ_AUTO, RPT_PROJ_EXACT, RPT_PROJ_MFMA = 0, 1, 2
 RPT_KNN_KEEP_DUPLICATES, RPT_KNN_DEDUP, RPT_KNN_DEDUP_DISTANCE = 0, 1, 2
 RPT_KNN_METRIC_REFERENCE = 1 << 24
+RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER = 1 << 25, 1 << 26
 RPT_COMM_UID_BYTES = 128
 
 i32, i64, f64 = C.c_int32, C.c_int64, C.c_double
@@ -83,6 +84,7 @@ SYMBOLS = {
     "rpt_knn_sharded_dev": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
     "rpt_knn_sharded": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
     "rpt_brute_knn_host": (i32, [vp, vp, vp, i32, vp, vp]),
+    "rpt_brute_knn_metric_host": (i32, [vp, vp, vp, i32, i32, vp, vp]),
 }
 
 

@@ -27,7 +27,7 @@ import numpy as np
 
 from . import _lib
 from . import (RPT_KNN_DEDUP, RPT_KNN_KEEP_DUPLICATES, RPT_PROJ_AUTO, Context, Dataset, RPForest,
-               _live)
+               _live, _metric_flag)
 
 
 def tree_shard(T, world, rank):
@@ -175,13 +175,15 @@ class ShardedForest:
             _ptr_array([x._h for x in queries]), int(k), int(flags), _ptr_array(ids_ptrs),
             _ptr_array(dist_ptrs), _ptr_array(count_ptrs)))
 
-    def knn(self, queries, k, dedup=False):
-        """-> host arrays (ids[nq][k], dist[nq][k], count[nq]) of the merged answer."""
+    def knn(self, queries, k, dedup=False, metric=None):
+        """-> host arrays (ids[nq][k], dist[nq][k], count[nq]) of the merged answer.
+        metric: None / metricL2, metricCosine or metricInner (as knnBatch)."""
         nq = queries[0].n
         ids = np.empty((nq, k), dtype=np.int32)
         dist = np.empty((nq, k), dtype=np.float64)
         cnt = np.empty(nq, dtype=np.int32)
         flags = RPT_KNN_DEDUP if dedup else RPT_KNN_KEEP_DUPLICATES
+        flags |= _metric_flag(metric)
         _lib.check(_lib.lib().rpt_knn_sharded(
             self.comm._h, self._h, _ptr_array([x._h for x in self.datasets]),
             _ptr_array([x._h for x in queries]), int(k), flags, C.c_void_p(ids.ctypes.data),
