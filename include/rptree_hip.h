@@ -92,16 +92,20 @@ extern "C" {
  *   RPT_KNN_METRIC_INNER : dist = -dot(x, q)                          (maximum inner product)
  *   RPT_KNN_METRIC_COSINE: dist = 1 - dot(x, q) / (sqrt(dot(x, x)) * sqrt(dot(q, q)))
  * with correctly rounded sqrt and division; smaller is nearer; a zero row or query gives NaN, and
- * NaN ranks behind every number, NaNs among themselves by candidate position.  Selection, the
- * duplicate rules and the returned bits are as for L2 on f64 rows: candidates are RANKED on a
- * lane-parallel f64 dot, the best k + 8 are evaluated again as the fold and the k best of those
- * by (distance, candidate position) are returned — more than 8 DIFFERENT rows within a few ulp of
- * the k-th distance would be needed to change the membership.  Unlike L2 on f32 / bf16 rows the
- * values are f64 for every dtype.  Or-ed into the knn flags; at most one of the two, not with
+ * NaN ranks behind every number, NaNs among themselves by candidate position.  The answer is
+ * exactly that definition: ALL candidates ranked by (distance, candidate position), the duplicate
+ * rule applied to those distances, the first k.  Candidates are ranked first on a lane-parallel f64
+ * dot; the entries of the best k + 8 different rows are evaluated again as the fold, and the cut is
+ * certified with a rounding bound of the two sums (within (2d + 16) u of each other for cosine,
+ * (2d + 8) u |q| max|x| for the inner product, u = 2^-53).  A query whose cut cannot be certified
+ * (ties or cancellation near the k-th distance, a zero or NaN query, k near 1024) is answered again
+ * by an exact kernel that evaluates every candidate as the fold; rpt_knn_last_uncertified counts
+ * those queries, the context option knn_metric_exact sends every query there.  Unlike L2 on f32 /
+ * bf16 rows the values are f64 for every dtype.  Or-ed into the knn flags; at most one of the two, not with
  * RPT_KNN_METRIC_REFERENCE (RPT_E_ARG); CSR data and RPT_KNN_VOTE: RPT_E_UNSUPPORTED.  Not for
  * knnH (rpt_knnh_host has no flags).
- * Memory note: the first cosine call on a dataset caches its rows' dot(x, x) on the device, 8 bytes
- * per row, freed with the dataset (a dataset borrowed with rpt_dataset_dense_dev must not change
+ * Memory note: the first cosine or inner-product call on a dataset caches its rows' dot(x, x) on the
+ * device, 8 bytes per row, freed with the dataset (a dataset borrowed with rpt_dataset_dense_dev must not change
  * while the library holds it). */
 #define RPT_KNN_METRIC_COSINE (1 << 25)
 #define RPT_KNN_METRIC_INNER (1 << 26)
@@ -313,7 +317,10 @@ int32_t rpt_knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
 /* statistics of the last rpt_knn_* call: total candidates visited (sum over queries) */
 int32_t rpt_knn_last_candidates(rpt_ctx* ctx, int64_t* total);
 /* ... and how many of its queries the f32 prefilter could not certify (equal distances at its
- * cut) and were answered again with all-f64 distances; 0 when the prefilter was not used */
+ * cut) and were answered again with all-f64 distances; 0 when the prefilter was not used.  After
+ * an RPT_KNN_METRIC_COSINE / _INNER call: the queries whose cut could not be certified and that the
+ * exact kernel answered (all of them with the option knn_metric_exact); this reads the count from
+ * the device, so it waits for the call's kernels to finish */
 int32_t rpt_knn_last_uncertified(rpt_ctx* ctx, int64_t* total);
 /* ... and how many took the in-kernel second attempt (a cut the first, narrower selection could not
  * certify, retried with three times the kept entries by the same workgroup).  Telemetry: a forest whose

@@ -237,6 +237,7 @@ const OptDesc kOptions[] = {
     {"knn_kp16", &rpt_options::knn_kp16},
     {"knn_no_pre8", &rpt_options::knn_no_pre8},
     {"knn_kp8", &rpt_options::knn_kp8},
+    {"knn_metric_exact", &rpt_options::knn_metric_exact},
     {"knn_csr_pre32", &rpt_options::knn_csr_pre32},
     {"knn_general", &rpt_options::knn_general},
     {"knn_shard_old", &rpt_options::knn_shard_old},
@@ -357,6 +358,7 @@ int32_t rpt_ctx_destroy(rpt_ctx* ctx) {
       (void)hipStreamDestroy(ctx->stream);
     }
     if (ctx->pin) (void)hipHostFree(ctx->pin);
+    if (ctx->metric_unc_dev) dev_free(ctx->metric_unc_dev);
     dev_trim();
     delete ctx;
     return RPT_OK;
@@ -1077,6 +1079,13 @@ int32_t rpt_knn_last_candidates(rpt_ctx* ctx, int64_t* total) {
 int32_t rpt_knn_last_uncertified(rpt_ctx* ctx, int64_t* total) {
   return guarded([&]() -> int32_t {
     RPT_ARG(ctx && total, "NULL argument");
+    if (ctx->metric_unc_pending) {  // the last call was a cosine / inner-product kNN
+      unsigned long long n = 0;
+      RPT_HIP(stream_sync(ctx->stream));
+      RPT_HIP(hipMemcpy(&n, ctx->metric_unc_dev, 8, hipMemcpyDeviceToHost));
+      ctx->last_uncertified = (int64_t)n;
+      ctx->metric_unc_pending = false;
+    }
     *total = ctx->last_uncertified;
     return RPT_OK;
   });

@@ -163,6 +163,7 @@ struct rpt_options {
   int64_t knn_kp16 = 0;         // kNN: entries the f16 prefilter keeps (0 = k + max(8, k / 2))
   int64_t knn_no_pre8 = 0;      // kNN: never rank on the int8 shadow (the half shadow is the first tier)
   int64_t knn_kp8 = 0;          // kNN: entries the int8 prefilter keeps (0 = k + max(48, k), capped by the kernel variant)
+  int64_t knn_metric_exact = 0;  // kNN, cosine / inner product: every query on the exact kernel (no certified cut)
   int64_t knn_csr_pre32 = 0;    // kNN: rank CSR f64 rows on their (u16 column, f32 value) shadow
   int64_t knn_general = 0;      // kNN: unfused general path
   int64_t knn_shard_old = 0;    // kNN: small shards keep the round-3 one-wave kernel (in-kernel traversal, fixed k')
@@ -184,6 +185,10 @@ struct rpt_ctx {
   char* pin = nullptr;
   size_t pin_cap = 0, pin_off = 0;
   int64_t last_uncertified = 0;  // queries of the last kNN call re-run with all-f64 distances
+  // the metric kNN's count of uncertified queries stays on the device until asked for
+  // (rpt_knn_last_uncertified): metric_unc_pending says last_uncertified is still to be read from it
+  unsigned long long* metric_unc_dev = nullptr;
+  bool metric_unc_pending = false;
   int64_t last_candidates = 0;
   int64_t last_retries = 0;      // queries of the last fused kNN call that took the in-kernel wider second attempt
   int32_t last_tier = 0;  // ranking tier of the last fused kNN call: 0 exact, 1 f32 shadow, 2 half, 3 int8
@@ -272,8 +277,9 @@ struct rpt_dataset {
   mutable int ell_w = 0;
   mutable int ell_state = 0;
   mutable double max_norm = -1.0;
-  // lazily built by the first cosine-metric kNN call on dense data: dot(x, x) of every row as the
-  // reference's left fold (innerDD), [n] doubles
+  // lazily built by the first cosine / inner-product kNN call on dense data: dot(x, x) of every row
+  // as the reference's left fold (innerDD), [n] doubles, then two 8-byte statistics of the rows for
+  // the certified cut (knn.hip row_sqnorm_kernel)
   mutable double* sqnorm = nullptr;
   // lazily built by the first projection of a CSR dataset whose hyperplane tile does not fit LDS
   // whole: index of every row's first nonzero with column >= csr_split_k (project.hip)

@@ -618,7 +618,8 @@ __device__ inline void finalize_leftfold(const TX* __restrict__ X, int d, const 
                                          const int* bpos, int tid, int nthr, Sync sync, int64_t q,
                                          int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
                                          int32_t* __restrict__ out_cnt,
-                                         const double* __restrict__ rn = nullptr, double qq = 0.0) {
+                                         const double* __restrict__ rn = nullptr, double qq = 0.0,
+                                         int* s_w = nullptr, double* s_last = nullptr) {
   for (int i = tid; i < m; i += nthr) {
     if constexpr (METRIC == kMetricL2)
       lf[i] = leftfold_distance(X + (int64_t)bid[i] * d, qs, d);
@@ -651,6 +652,10 @@ __device__ inline void finalize_leftfold(const TX* __restrict__ X, int d, const 
       ++w;
     }
     out_cnt[q] = w;
+    if (s_w) {  // (the metric kernel's certificate: the count and the last value written)
+      *s_w = w;
+      *s_last = w > 0 ? last : 0.0;
+    }
     for (; w < k; ++w) {
       out_ids[q * k + w] = -1;
       out_dist[q * k + w] = __longlong_as_double(0x7ff0000000000000LL);
@@ -873,29 +878,149 @@ __device__ __forceinline__ void batch_distances(const TD* __restrict__ X, int d,
 constexpr int kMB = 512;  // candidates per batch of knn_metric_kernel
 constexpr int kMW = 64;   // leaf ranges it holds in LDS at a time
 
-// dot(x, x) of every row as the left fold (the cosine metric's row norms, cached on the dataset)
+// The certified cut.  Both sums of a row, the left fold and the butterfly, add the SAME rounded
+// products p_j = x_j q_j (-ffp-contract=off: no FMA) in different orders, so by the standard bound
+// of a summation (Higham, Accuracy and Stability, (3.5): each term goes through at most d - 1
+// additions, its product one more rounding) each is within gamma_d S of the exact dot, S = sum |p_j|
+// <= |x| |q| (Cauchy-Schwarz), gamma_d = d u / (1 - d u), u = 2^-53; subnormal results add at most
+// 2^-1075 per rounding, 2d - 1 roundings per sum.  Hence
+//     |fold - butterfly| <= 2 gamma_d |x| |q| + 2d 2^-1074.
+// inner:  the values are -dot.  With xb = sqrt(max rn) + d 2^-537 >= |x| (rn = fold(x.x) >= |x|^2 (1 -
+//   gamma_d) - d 2^-1075: the squares that underflow) and qb the same for the query,
+//   2 gamma_d |x||q| <= 2 d u (1 + 2 d u + 4 u) xb qb <= (2d + 1) u xb qb (d u <= 2^-30), one u xb qb
+//   more for the rounding of b - E (|b| <= (1 + gamma_d) S), two more for the products that form E:
+//     E = (2d + 8) u xb qb + (2d + 8) 2^-1074,
+//   and only when E <= 2^960: then every partial sum stays below 2^1013, no sum overflows.
+// cosine: the values are 1 - dot / D with ONE denominator D = sqrt(rn) sqrt(qq) for both sums.  When
+//   every row's rn and the query's qq lie in [2^-900, 2^900] (zero rows are NaN in both sums: any
+//   rn = 0 row must be all zeros), D >= |x||q| (1 - gamma_d)(1 - u)^3 and the underflow term is
+//   below 2^-159 relative to D: |dot_f - dot_b| / D <= 2 d u + 2 u; the two divisions add u |dot/D|
+//   <= 1.0001 u each, the two 1 - t add u |1 - t| <= 2.0002 u each, b - E is rounded once more
+//   (<= 2.1 u):  2 d u + 10.3 u, rounded up:
+//     E = (2d + 16) u.
+// A query is certified when nothing was excluded from the kept set, or when k entries were written
+// and the k-th (by the fold) is strictly below b - E, b the butterfly value of the LAST kept entry:
+// every excluded candidate has butterfly >= b, so fold >= b - E > the k-th, and cannot belong to the
+// answer (nor, under dedup 2, remove a value from it).  NaN anywhere in that test fails it.
+// E for one query (NaN: the query cannot be certified).  stats: the dataset's row statistics
+// (row_stats_kernel: [0] the largest rn as bits, NaN as the largest; [1] nonzero when some row's rn
+// is outside the cosine range above).
+template <int METRIC>
+__device__ inline double metric_cut_slack(int d, double qq, const unsigned long long* stats) {
+  const double u = 0x1p-53;
+  if constexpr (METRIC == kMetricCosine) {
+    if (stats[1] != 0 || !(qq >= 0x1p-900 && qq <= 0x1p900)) return __longlong_as_double(0x7ff8000000000000LL);
+    return (2.0 * d + 16.0) * u;
+  } else {
+    const double xb = sqrt(__longlong_as_double((long long)stats[0])) + (double)d * 0x1p-537;
+    const double qb = sqrt(qq) + (double)d * 0x1p-537;
+    const double e = (2.0 * d + 8.0) * u * xb * qb + (2.0 * d + 8.0) * 0x1p-1074;
+    return e <= 0x1p960 ? e : __longlong_as_double(0x7ff8000000000000LL);
+  }
+}
+
+// dot(x, x) of every row as the left fold (the metrics' row norms, cached on the dataset) and the
+// dataset's statistics for the certified cut (metric_cut_slack): stats[0] max over the rows of
+// rn's bits (rn >= 0: the bits order as the values; a NaN, sign cleared, above +inf), stats[1] set
+// when a row's rn lies outside [2^-900, 2^900] and the row is not all zeros.  stats zeroed before.
 template <class TD>
 __global__ __launch_bounds__(256) void row_sqnorm_kernel(const TD* __restrict__ X, int64_t n, int d,
-                                                         double* __restrict__ rn) {
+                                                         double* __restrict__ rn,
+                                                         unsigned long long* __restrict__ stats) {
   const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r < n) rn[r] = leftfold_dot<TD, true>(X + r * d, nullptr, d);
+  unsigned long long bits = 0, bad = 0;
+  if (r < n) {
+    const double v = leftfold_dot<TD, true>(X + r * d, nullptr, d);
+    rn[r] = v;
+    bits = (unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffULL;
+    if (!(v >= 0x1p-900 && v <= 0x1p900)) {
+      bad = v != 0.0;
+      for (int j = 0; j < d && !bad; ++j) bad = (double)ld<TD>(X + r * d + j) != 0.0;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long ob = __shfl_xor(bits, o), oo = __shfl_xor(bad, o);
+    bits = ob > bits ? ob : bits;
+    bad |= oo;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (bits) atomicMax(&stats[0], bits);
+    if (bad) atomicOr(&stats[1], bad);
+  }
+}
+
+// knn_metric_kernel's merge: sort buf[0, filled) in the total order and keep a prefix that holds
+// kk DIFFERENT ids (copies of one row, the same point found by several trees, have equal sums of
+// both kinds and must not eat the margin), at most cap entries.  ided: the entries of one id are
+// one entry (the first: the lowest position); the prefix is compacted.  Returns the kept count;
+// *cut (block-uniform) is set when some entry was left out for the prefix (not a same-id copy).
+__device__ int merge_distinct(Entry* buf, int filled, int kk, int cap, bool ided, int* scratch, int* s_out) {
+  int np = 1;
+  while (np < filled) np <<= 1;
+  for (int i = filled + threadIdx.x; i < np; i += blockDim.x)
+    buf[i] = Entry{__longlong_as_double(0x7ff0000000000000LL), 0x7fffffff, -1};
+  __syncthreads();
+  bitonic_entries<true>(buf, np);
+  // same id => same value: a copy sits in the run of equal values before it
+  for (int i = threadIdx.x; i < filled; i += blockDim.x) {
+    const double di = buf[i].dist;
+    int dup = 0;
+    for (int j = i - 1; j >= 0 && (buf[j].dist == di || (di != di && buf[j].dist != buf[j].dist)); --j)
+      if (buf[j].id == buf[i].id) {
+        dup = 1;
+        break;
+      }
+    scratch[i] = dup;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int w = 0, distinct = 0, i = 0, cut = 0;
+    for (; i < filled; ++i) {
+      if (!scratch[i]) {
+        if (distinct == kk || w == cap) {
+          cut = 1;
+          break;
+        }
+        ++distinct;
+      } else if (ided) {
+        continue;
+      } else if (w == cap) {
+        cut = 1;
+        break;
+      }
+      if (w != i) buf[w] = buf[i];
+      ++w;
+    }
+    s_out[0] = w;
+    s_out[1] = cut;
+  }
+  __syncthreads();
+  return s_out[0];
 }
 
 // knn under the cosine or inner-product metric, dense rows of any dtype, values in f64.  One
 // workgroup (four waves) per query over the plan's leaf ranges in candidate order (or, identity:
 // the whole dataset in id order, the brute force).  Batches of kMB candidates: ids and positions
-// gathered across ranges, dots by batch_distances (the butterfly f64 sum, 16-byte row loads, the
-// short-row layout up to 512-byte rows), the metric value, and only the entries that beat the
-// current (k + kLfMargin)-th best in the total order appended to buf; merge_best<true> keeps the
-// best when the next batch might not fit.  The kept entries are evaluated again as the left fold and
-// selected in the finalize_leftfold order (NaN last, by position).  LDS: buf [nbuf] entries (a power
-// of two >= kk + kMB), scratch [nbuf] ints, the batch (kMB x 16 B), the query [d] doubles.
-template <class TD, int METRIC>
+// gathered across ranges, the values, and only the entries that beat the current cut in the total
+// order appended to buf; a merge keeps the best when the next batch might not fit.
+//   EXACT = false (every query): the values from batch_distances (the butterfly f64 sum, 16-byte
+// row loads, the short-row layout up to 512-byte rows); merge_distinct keeps the entries of the
+// best k + kLfMargin different ids (same-id copies collapse under dedup 1 and 2: one id, one value
+// in both sums); those are evaluated again as the left fold and selected in the finalize_leftfold
+// order (NaN last, by position), the duplicate rule on the fold values.  Then the cut is certified
+// (metric_cut_slack); when it is not, q is appended to the list unc (*unc_count entries).
+//   EXACT = true (the queries of that list, grid-stride; unc == nullptr: all nq): every value is the left fold (one
+// thread per row) and merge_best selects on those with no margin; the answer is the definition.
+// LDS: buf [nbuf] entries (a power of two >= kk + kMB), scratch [nbuf] ints, the batch (kMB x 16 B),
+// the query [d] doubles.
+template <class TD, int METRIC, bool EXACT>
 __global__ __launch_bounds__(256) void knn_metric_kernel(
-    const TD* __restrict__ X, int d, const TD* __restrict__ Q, const int32_t* __restrict__ perm,
+    const TD* __restrict__ X, int d, const TD* __restrict__ Q, int64_t nq, const int32_t* __restrict__ perm,
     const Range* __restrict__ ranges, const int64_t* __restrict__ rng_off, int T, int64_t N,
     int identity, int nbuf, int k, int dedup, const double* __restrict__ rn,
-    int32_t* __restrict__ out_ids, double* __restrict__ out_dist, int32_t* __restrict__ out_cnt) {
+    const unsigned long long* __restrict__ stats, int32_t* __restrict__ unc,
+    unsigned long long* __restrict__ unc_count, int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
+    int32_t* __restrict__ out_cnt) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Entry* buf = reinterpret_cast<Entry*>(smem);                      // [nbuf]
   int* scratch = reinterpret_cast<int*>(smem + sizeof(Entry) * nbuf);  // [nbuf]
@@ -904,81 +1029,105 @@ __global__ __launch_bounds__(256) void knn_metric_kernel(
   int* cpos = cid + kMB;                                            // [kMB]
   double* qs = reinterpret_cast<double*>(cpos + kMB);               // [d]
   __shared__ Range s_rng[kMW];
-  __shared__ int s_fill;
-  __shared__ double s_qq;
-  const int64_t q = blockIdx.x;
+  __shared__ int s_fill, s_merge[2], s_w;
+  __shared__ double s_qq, s_blast, s_last;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int j = threadIdx.x; j < d; j += blockDim.x) qs[j] = (double)ld<TD>(Q + q * d + j);
-  if (threadIdx.x == 0) s_fill = 0;
-  __syncthreads();
-  // dot(q, q) (read after the first batch's barriers); the elements in LDS are the widened query
-  if (METRIC == kMetricCosine && threadIdx.x == 0) s_qq = leftfold_dot<double, true>(qs, nullptr, d);
+  const int kk = EXACT ? k : (k + kLfMargin < nbuf / 2 ? k + kLfMargin : nbuf / 2);
+  const int sdedup = EXACT ? dedup : (dedup ? 1 : 0);  // the fast path's rule while streaming
+  const int64_t nw = EXACT && unc ? (int64_t)*unc_count : nq;  // the queries of this launch
+  for (int64_t iw = blockIdx.x; iw < nw; iw += gridDim.x) {
+    const int64_t q = EXACT && unc ? (int64_t)unc[iw] : iw;
+    __syncthreads();  // (the previous query's finalize still reads the arrays)
+    for (int j = threadIdx.x; j < d; j += blockDim.x) qs[j] = (double)ld<TD>(Q + q * d + j);
+    if (threadIdx.x == 0) s_fill = 0;
+    __syncthreads();
+    // dot(q, q) (read after the first batch's barriers); the elements in LDS are the widened query
+    if ((METRIC == kMetricCosine || !EXACT) && threadIdx.x == 0) s_qq = leftfold_dot<double, true>(qs, nullptr, d);
 
-  const int kk = k + kLfMargin < nbuf / 2 ? k + kLfMargin : nbuf / 2;
-  int best = 0;
-  Entry thr{0.0, 0, -1};  // the kk-th best so far; id -1: none yet, every entry enters
-  const int64_t r0 = identity ? 0 : rng_off[q * T];
-  const int64_t r1 = identity ? 1 : rng_off[(q + 1) * T];
-  int64_t r = r0, w0 = r0, w1 = r0;  // next range; ranges [w0, w1) are in s_rng
-  int done = 0;                      // candidates of range r already taken
-  while (r < r1) {
-    int nb = 0;
-    while (nb < kMB && r < r1) {  // block-uniform
-      if (r == w1) {
-        __syncthreads();
-        w0 = r;
-        w1 = r + kMW < r1 ? r + kMW : r1;
-        for (int i = threadIdx.x; i < w1 - w0; i += blockDim.x)
-          s_rng[i] = identity ? Range{0, (int32_t)N, 0} : ranges[w0 + i];
-        __syncthreads();
+    int best = 0;
+    bool cut = false;       // some candidate is not in buf (other than a same-id copy)
+    Entry thr{0.0, 0, -1};  // the last kept entry after a cut; id -1: none yet, every entry enters
+    const int64_t r0 = identity ? 0 : rng_off[q * T];
+    const int64_t r1 = identity ? 1 : rng_off[(q + 1) * T];
+    int64_t r = r0, w0 = r0, w1 = r0;  // next range; ranges [w0, w1) are in s_rng
+    int done = 0;                      // candidates of range r already taken
+    while (r < r1) {
+      int nb = 0;
+      while (nb < kMB && r < r1) {  // block-uniform
+        if (r == w1) {
+          __syncthreads();
+          w0 = r;
+          w1 = r + kMW < r1 ? r + kMW : r1;
+          for (int i = threadIdx.x; i < w1 - w0; i += blockDim.x)
+            s_rng[i] = identity ? Range{0, (int32_t)N, 0} : ranges[w0 + i];
+          __syncthreads();
+        }
+        const Range rg = s_rng[r - w0];
+        int take = rg.n - done;
+        if (take > kMB - nb) take = kMB - nb;
+        for (int i = threadIdx.x; i < take; i += blockDim.x) {
+          const int c = done + i;
+          cid[nb + i] = identity ? c : perm[rg.poff + c];
+          cpos[nb + i] = rg.pos + c;
+        }
+        nb += take;
+        done += take;
+        if (done == rg.n) {
+          ++r;
+          done = 0;
+        }
       }
-      const Range rg = s_rng[r - w0];
-      int take = rg.n - done;
-      if (take > kMB - nb) take = kMB - nb;
-      for (int i = threadIdx.x; i < take; i += blockDim.x) {
-        const int c = done + i;
-        cid[nb + i] = identity ? c : perm[rg.poff + c];
-        cpos[nb + i] = rg.pos + c;
+      __syncthreads();
+      if constexpr (EXACT) {
+        for (int i = threadIdx.x; i < nb; i += blockDim.x) cd[i] = leftfold_dot<TD>(X + (int64_t)cid[i] * d, qs, d);
+      } else {
+        batch_distances<TD, double, 8, false, double, true>(X, d, cid, cd, qs, 0, nb, wave, 4, lane);
       }
-      nb += take;
-      done += take;
-      if (done == rg.n) {
-        ++r;
-        done = 0;
+      __syncthreads();
+      const double qq = METRIC == kMetricCosine ? s_qq : 0.0;
+      // the order inside buf does not matter (the merges sort by value and position)
+      for (int i = threadIdx.x; i < nb; i += blockDim.x) {
+        const Entry e{metric_value<METRIC>(cd[i], METRIC == kMetricCosine ? rn[cid[i]] : 0.0, qq), cpos[i],
+                      cid[i]};
+        if (entry_less_total(e, thr)) buf[atomicAdd(&s_fill, 1)] = e;
+      }
+      __syncthreads();
+      const int filled = s_fill;
+      if (filled + kMB > nbuf || r >= r1) {
+        if constexpr (EXACT) {
+          best = merge_best<true>(buf, filled, kk, sdedup, scratch);
+          if (best == kk) thr = buf[kk - 1];
+        } else {
+          best = merge_distinct(buf, filled, kk, nbuf / 2, sdedup != 0, scratch, s_merge);
+          if (s_merge[1]) {
+            cut = true;
+            thr = buf[best - 1];
+          }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) s_fill = best;
+        __syncthreads();
       }
     }
-    __syncthreads();
-    batch_distances<TD, double, 8, false, double, true>(X, d, cid, cd, qs, 0, nb, wave, 4, lane);
-    __syncthreads();
-    const double qq = METRIC == kMetricCosine ? s_qq : 0.0;
-    // the order inside buf does not matter (merge_best sorts by value and position)
-    for (int i = threadIdx.x; i < nb; i += blockDim.x) {
-      const Entry e{metric_value<METRIC>(cd[i], METRIC == kMetricCosine ? rn[cid[i]] : 0.0, qq), cpos[i],
-                    cid[i]};
-      if (entry_less_total(e, thr)) buf[atomicAdd(&s_fill, 1)] = e;
+    if (threadIdx.x == 0) s_blast = best > 0 ? buf[best - 1].dist : 0.0;  // (buf's lower half stays)
+    double* lf = reinterpret_cast<double*>(scratch);        // nbuf / 2 doubles >= kk
+    int* ids2 = reinterpret_cast<int*>(buf + nbuf / 2);     // the upper half of buf is free now:
+    int* pos2 = ids2 + nbuf / 2;                            // 3 x nbuf / 2 ints fit its 8 x nbuf bytes
+    int* order = pos2 + nbuf / 2;
+    for (int i = threadIdx.x; i < best; i += blockDim.x) {
+      ids2[i] = buf[i].id;
+      pos2[i] = buf[i].pos;
     }
     __syncthreads();
-    const int filled = s_fill;
-    if (filled + kMB > nbuf || r >= r1) {
-      best = merge_best<true>(buf, filled, kk, dedup, scratch);
-      if (best == kk) thr = buf[kk - 1];
-      __syncthreads();
-      if (threadIdx.x == 0) s_fill = best;
-      __syncthreads();
+    finalize_leftfold<METRIC>(X, d, qs, best, k, dedup, lf, order, ids2, pos2, (int)threadIdx.x,
+                              (int)blockDim.x, [] { __syncthreads(); }, q, out_ids, out_dist, out_cnt, rn,
+                              METRIC == kMetricCosine ? s_qq : 0.0, &s_w, &s_last);
+    if (!EXACT && threadIdx.x == 0) {  // (the thread that wrote the answer and s_w / s_last)
+      bool ok = !cut;
+      if (!ok && s_w == k) ok = s_last < s_blast - metric_cut_slack<METRIC>(d, s_qq, stats);
+      if (!ok) unc[atomicAdd(unc_count, 1ULL)] = (int32_t)q;
     }
   }
-  double* lf = reinterpret_cast<double*>(scratch);        // nbuf / 2 doubles >= kk
-  int* ids2 = reinterpret_cast<int*>(buf + nbuf / 2);     // the upper half of buf is free now:
-  int* pos2 = ids2 + nbuf / 2;                            // 3 x nbuf / 2 ints fit its 8 x nbuf bytes
-  int* order = pos2 + nbuf / 2;
-  for (int i = threadIdx.x; i < best; i += blockDim.x) {
-    ids2[i] = buf[i].id;
-    pos2[i] = buf[i].pos;
-  }
-  __syncthreads();
-  finalize_leftfold<METRIC>(X, d, qs, best, k, dedup, lf, order, ids2, pos2, (int)threadIdx.x,
-                            (int)blockDim.x, [] { __syncthreads(); }, q, out_ids, out_dist, out_cnt, rn,
-                            METRIC == kMetricCosine ? s_qq : 0.0);
 }
 
 // ---- int8 ranking tier (round 3) ----------------------------------------------------------
@@ -3747,23 +3896,26 @@ static int32_t ensure_shadow8(rpt_ctx* ctx, const rpt_dataset* data) {
   return RPT_OK;
 }
 
-// The cosine metric's row norms dot(x, x), once per dataset (8 bytes per row, freed with it).  Unlike
-// the shadows this is not optional: without it the metric cannot be evaluated.
+// The metrics' row norms dot(x, x), once per dataset (8 bytes per row, freed with it), followed by
+// the two statistics of row_sqnorm_kernel (the certified cut's bound).  Unlike the shadows this is
+// not optional: without it the metric cannot be evaluated or its cut certified.
 static int32_t ensure_sqnorm(rpt_ctx* ctx, const rpt_dataset* data) {
   if (data->sqnorm) return RPT_OK;
   DevBuf<double> rn;
-  RPT_TRY(rn.alloc((size_t)data->n + 1));
+  RPT_TRY(rn.alloc((size_t)data->n + 2));
+  unsigned long long* stats = reinterpret_cast<unsigned long long*>(rn.p + data->n);
+  RPT_HIP(hipMemsetAsync(stats, 0, 16, ctx->stream));
   const unsigned blocks = (unsigned)((data->n + 255) / 256);
   if (blocks > 0) {
     if (data->dtype == RPT_F64)
       hipLaunchKernelGGL(row_sqnorm_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream,
-                         (const double*)data->X, data->n, data->d, rn.p);
+                         (const double*)data->X, data->n, data->d, rn.p, stats);
     else if (data->dtype == RPT_F32)
       hipLaunchKernelGGL(row_sqnorm_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream,
-                         (const float*)data->X, data->n, data->d, rn.p);
+                         (const float*)data->X, data->n, data->d, rn.p, stats);
     else
       hipLaunchKernelGGL(row_sqnorm_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, ctx->stream,
-                         (const __hip_bfloat16*)data->X, data->n, data->d, rn.p);
+                         (const __hip_bfloat16*)data->X, data->n, data->d, rn.p, stats);
     RPT_HIP(hipGetLastError());
   }
   data->sqnorm = rn.p;
@@ -3775,65 +3927,106 @@ static size_t metric_smem(int nbuf, int d) {
   return (sizeof(Entry) + 4) * (size_t)nbuf + (size_t)kMB * 16 + (size_t)d * 8;
 }
 
-template <class TD, int METRIC>
-static int32_t launch_metric_t(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
+// The metric kernels' list of uncertified queries (unc, [nq] ints, the caller's) and the context's
+// count of them (read lazily by rpt_knn_last_uncertified: no read-back here)
+static int32_t metric_unc_count(rpt_ctx* ctx, unsigned long long** p) {
+  if (!ctx->metric_unc_dev) RPT_HIP(dev_alloc((void**)&ctx->metric_unc_dev, 8));
+  *p = ctx->metric_unc_dev;
+  return RPT_OK;
+}
+
+template <class TD, int METRIC, bool EXACT>
+static int32_t launch_metric_v(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
                                const int32_t* perm, const Range* ranges, const int64_t* rng_off, int T,
-                               int identity, int k, int dedup, int32_t* ids, double* dist, int32_t* cnt) {
+                               int identity, int k, int dedup, int32_t* unc, unsigned long long* unc_count,
+                               int32_t* ids, double* dist, int32_t* cnt) {
   // buf holds the kept kk = k + kLfMargin (at most nbuf / 2) and one batch
   const int nbuf = k + kLfMargin + kMB <= 1024 ? 1024 : kBuf;
   const size_t smem = metric_smem(nbuf, data->d);
   RPT_ARG(smem <= 150 * 1024, "d too large");
   if (smem > 64 * 1024)
-    RPT_HIP(hipFuncSetAttribute((const void*)knn_metric_kernel<TD, METRIC>,
+    RPT_HIP(hipFuncSetAttribute((const void*)knn_metric_kernel<TD, METRIC, EXACT>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  // the exact variant strides over its list of queries (blocks beyond its length return at once)
+  int64_t grid = q->n;
+  if (EXACT && grid > (int64_t)ctx->n_cu * 4) grid = (int64_t)ctx->n_cu * 4;
   ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
-  hipLaunchKernelGGL((knn_metric_kernel<TD, METRIC>), dim3((unsigned)q->n), dim3(256), smem, ctx->stream,
-                     (const TD*)data->X, data->d, (const TD*)q->X, perm, ranges, rng_off, T, data->n,
-                     identity, nbuf, k, dedup, (const double*)data->sqnorm, ids, dist, cnt);
+  hipLaunchKernelGGL((knn_metric_kernel<TD, METRIC, EXACT>), dim3((unsigned)grid), dim3(256), smem,
+                     ctx->stream, (const TD*)data->X, data->d, (const TD*)q->X, q->n, perm, ranges, rng_off, T,
+                     data->n, identity, nbuf, k, dedup, (const double*)data->sqnorm,
+                     reinterpret_cast<const unsigned long long*>(data->sqnorm + data->n), unc, unc_count, ids,
+                     dist, cnt);
   RPT_HIP(hipGetLastError());
   return RPT_OK;
+}
+
+// the fast kernel, then the exact one over the queries it could not certify (all of them with
+// knn_metric_exact); ctx->last_uncertified follows
+template <class TD, int METRIC>
+static int32_t launch_metric_t(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
+                               const int32_t* perm, const Range* ranges, const int64_t* rng_off, int T,
+                               int identity, int k, int dedup, int32_t* unc, int32_t* ids, double* dist,
+                               int32_t* cnt) {
+  unsigned long long* uc = nullptr;
+  RPT_TRY(metric_unc_count(ctx, &uc));
+  if (ctx->opt.knn_metric_exact) {
+    unc = nullptr;  // every query
+    ctx->last_uncertified = q->n;
+    ctx->metric_unc_pending = false;
+  } else {
+    RPT_HIP(hipMemsetAsync(uc, 0, 8, ctx->stream));
+    RPT_TRY((launch_metric_v<TD, METRIC, false>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, unc,
+                                                uc, ids, dist, cnt)));
+    ctx->metric_unc_pending = true;
+  }
+  return launch_metric_v<TD, METRIC, true>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, unc, uc,
+                                           ids, dist, cnt);
 }
 
 template <class TD>
 static int32_t launch_metric_td(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
                                 const int32_t* perm, const Range* ranges, const int64_t* rng_off, int T,
-                                int identity, int k, int dedup, int metric, int32_t* ids, double* dist,
-                                int32_t* cnt) {
+                                int identity, int k, int dedup, int metric, int32_t* unc, int32_t* ids,
+                                double* dist, int32_t* cnt) {
   if (metric == RPT_KNN_METRIC_COSINE)
     return launch_metric_t<TD, kMetricCosine>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup,
-                                              ids, dist, cnt);
-  return launch_metric_t<TD, kMetricInner>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, ids,
-                                           dist, cnt);
+                                              unc, ids, dist, cnt);
+  return launch_metric_t<TD, kMetricInner>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, unc,
+                                           ids, dist, cnt);
 }
 
-// the cosine / inner-product kernel over the query plan (batch and streamed forests alike) or, with
-// identity, over the whole dataset (brute force; ties by id)
+// the cosine / inner-product kernels over the query plan (batch and streamed forests alike) or, with
+// identity, over the whole dataset (brute force; ties by id).  unc: [q->n] ints of device scratch
+// that lives until the kernels are done.
 static int32_t launch_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
                              const int32_t* perm, const Range* ranges, const int64_t* rng_off, int T,
-                             int identity, int k, int dedup, int metric, int32_t* ids, double* dist,
-                             int32_t* cnt) {
-  if (metric == RPT_KNN_METRIC_COSINE) RPT_TRY(ensure_sqnorm(ctx, data));
+                             int identity, int k, int dedup, int metric, int32_t* unc, int32_t* ids,
+                             double* dist, int32_t* cnt) {
+  RPT_TRY(ensure_sqnorm(ctx, data));
   if (data->dtype == RPT_F64)
-    return launch_metric_td<double>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, metric, ids,
-                                    dist, cnt);
+    return launch_metric_td<double>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, metric, unc,
+                                    ids, dist, cnt);
   if (data->dtype == RPT_F32)
-    return launch_metric_td<float>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, metric, ids,
-                                   dist, cnt);
+    return launch_metric_td<float>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, metric, unc,
+                                   ids, dist, cnt);
   return launch_metric_td<__hip_bfloat16>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup,
-                                          metric, ids, dist, cnt);
+                                          metric, unc, ids, dist, cnt);
 }
 
 static int32_t knn_metric(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
                           int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
   ctx->last_uncertified = 0;
+  ctx->metric_unc_pending = false;
   ctx->last_retries = 0;
   ctx->last_tier = 0;
   QueryPlan pl;
   RPT_TRY(make_plan(ctx, f, q, pl));
   ctx->last_candidates = pl.total_cand;
   if (q->n == 0) return RPT_OK;
+  DevBuf<int32_t> unc;
+  RPT_TRY(unc.alloc((size_t)q->n));
   RPT_TRY(launch_metric(ctx, data, q, f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, 0, k, flags & 3,
-                        flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER), ids_dev, dist_dev,
+                        flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER), unc.p, ids_dev, dist_dev,
                         count_dev));
   RPT_HIP(stream_sync(ctx->stream));  // the plan's buffers are released on return
   return RPT_OK;
@@ -4294,6 +4487,7 @@ static int32_t knn_general(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
 
 int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
                 int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  ctx->metric_unc_pending = false;
   RPT_ARG(data->dtype == q->dtype, "data and query dtype must match");
   RPT_ARG(k <= kBuf / 2, "k too large for the LDS merge buffer");
   RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
@@ -4635,12 +4829,17 @@ int32_t brute_knn_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
   RPT_ARG(k <= kBuf / 2, "k too large");
   const int64_t nq = q->n;
   if (nq == 0) return RPT_OK;
+  ctx->last_uncertified = 0;
+  ctx->metric_unc_pending = false;
   DevBuf<int32_t> ids, cnt;
   DevBuf<double> dist;
+  DevBuf<int32_t> unc;
   RPT_TRY(ids.alloc((size_t)nq * k));
   RPT_TRY(dist.alloc((size_t)nq * k));
   RPT_TRY(cnt.alloc((size_t)nq));
-  RPT_TRY(launch_metric(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, metric, ids.p, dist.p, cnt.p));
+  RPT_TRY(unc.alloc((size_t)nq));
+  RPT_TRY(launch_metric(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, metric, unc.p, ids.p, dist.p,
+                        cnt.p));
   RPT_HIP(stream_sync(ctx->stream));
   RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
   RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));

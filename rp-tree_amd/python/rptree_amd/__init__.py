@@ -772,7 +772,9 @@ def knnBatch(k, forest, qs, dedup=False, vote=0, reference_metric=False, metric=
 
 
 def knn_last_uncertified(ctx=None):
-    """queries of the last knn call whose f32 prefilter cut could not be certified (re-run exactly)"""
+    """queries of the last knn call whose cut could not be certified and were answered again
+    exactly: the f32 prefilter's (L2), or, after a metricCosine / metricInner call, the metric
+    kernel's (answered by its exact variant; every query with the option knn_metric_exact)"""
     ctx = ctx or default_context()
     v = C.c_int64()
     check(lib().rpt_knn_last_uncertified(ctx._h, C.byref(v)))
