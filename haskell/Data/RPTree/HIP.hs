@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -47,6 +47,8 @@ foreign import ccall safe "rpt_forest_get_topology" c_forest_topo    :: Ptr Fore
 foreign import ccall safe "rpt_knn_host"            c_knn_host       :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 -- knnH (RPTree.hs:199-217): two calls, the first with null outputs returns the result size
 foreign import ccall safe "rpt_knnh_host"           c_knnh_host      :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int64 -> Ptr Int32 -> Ptr Double -> Int64 -> Ptr Int64 -> IO Int32
+foreign import ccall safe "rpt_dataset_csr_host"    c_dataset_csr    :: Ptr Ctx -> Ptr Int64 -> Ptr Int32 -> Ptr Double -> Int64 -> Int32 -> Int32 -> Ptr (Ptr Dataset) -> IO Int32
+foreign import ccall safe "rpt_recall_hits_host"    c_recall_hits    :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
 -- multi-GPU (csrc/comm.hip on librccl): one process drives n devices; per-device arguments are
 -- arrays with one entry per device (Foreign.Marshal.Array.withArray)
@@ -225,3 +227,37 @@ knnMetricHIP m ctx f ds qs nq k = do
   ids <- VSM.new (nq * k); dist <- VSM.new (nq * k); cnt <- VSM.new nq
   VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_host ctx f ds qs (fromIntegral k) (metricFlag m) a b))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | SVector rows as a CSR dataset on the device (rpt_dataset_csr_host), for the extent of the
+-- callback on an existing context: the point set of an SVector forest, or a batch of SVector queries.
+withDeviceDataSV :: Ptr Ctx -> Int -> V.Vector (SVector Double) -> (Ptr Dataset -> IO a) -> IO a
+withDeviceDataSV ctx dim rows act = do
+  let ixs = [ VU.toList ix | SV _ ix _ <- V.toList rows ]
+      rowptr = VS.fromList (scanl (+) 0 (map (fromIntegral . length) ixs)) :: VS.Vector Int64
+      -- (one slot of padding: the pointers of an all-empty batch stay valid)
+      col = VS.fromList (map fromIntegral (concat ixs) ++ [0]) :: VS.Vector Int32
+      val = VS.fromList (concat [ VU.toList vs | SV _ _ vs <- V.toList rows ] ++ [0]) :: VS.Vector Double
+      acquire mk = alloca $ \pp -> mk pp >>= check >> peek pp
+  bracket (acquire (\pp -> VS.unsafeWith rowptr (\pr -> VS.unsafeWith col (\pc -> VS.unsafeWith val (\pv ->
+             c_dataset_csr ctx pr pc pv (fromIntegral (V.length rows)) (fromIntegral dim) 0 pp)))))
+          c_dataset_free act
+
+-- | 'recallWith metricL2 forest k' (RPTree.hs:259-282) for a batch of SVector queries over an SVector
+-- forest on the device: per query the mean over the trees of
+-- @|candidates tree q `intersection` true kNN| / k@, truth and intersection both on the device
+-- (rpt_recall_hits_host; the division of :276-282 here, in tree order).  @refMetric@ ranks the truth
+-- by the reference's own truncating metricSSL2 (RPT_KNN_METRIC_REFERENCE: the value 'recallWith
+-- metricL2' of the reference itself has on SVector rows) instead of the true Euclidean distance.
+-- @ds@ is the forest's point set ('withDeviceDataSV'), @ntrees@ its number of trees.
+recallWithHIP :: Bool -> Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int -> Int -> Int
+              -> V.Vector (SVector Double) -> IO (V.Vector Double)
+recallWithHIP refMetric ctx f ds ntrees dim k qs =
+  withDeviceDataSV ctx dim qs $ \qd -> do
+    let nq = V.length qs
+        flags = if refMetric then 16777216 else 0     -- RPT_KNN_METRIC_REFERENCE (1 << 24)
+    hits <- VSM.new (max 1 (nq * ntrees)); truth <- VSM.new (max 1 (nq * k))
+    VSM.unsafeWith hits (\a -> VSM.unsafeWith truth (c_recall_hits ctx f ds qd (fromIntegral k) flags a)) >>= check
+    hs <- VS.freeze hits
+    let rec i = sum [ fromIntegral (hs VS.! (i * ntrees + t)) / fromIntegral k | t <- [0 .. ntrees - 1] ]
+                / fromIntegral ntrees
+    pure (V.generate nq rec)

@@ -142,6 +142,9 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *   knn_wave (-1 auto, 0, 1), knn_kp, knn_kp16, knn_kp8, knn_no_pre32, knn_no_pre16, knn_no_pre8,
  *   knn_csr_pre32, knn_general
  *       query kernels; knn_kp8 > 0 also opts bf16 datasets into the int8 ranking tier
+ *   brute_csr_tile (0 auto, n)     brute force over CSR rows: queries per workgroup (1, 2, 4 or 8; other
+ *                                  values round down; halved while the tile does not fit LDS; auto
+ *                                  takes up to 4)
  *   comm_force_exchange            sharded kNN on a ONE-rank communicator still runs record ->
  *                                  ncclAllGather -> merge (set on the communicator's first ctx)
  *   comm_inject_failure            test hook: the device's shard reports a failure (see "Failures"
@@ -424,6 +427,41 @@ int32_t rpt_brute_knn_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_data
 int32_t rpt_brute_knn_metric_host(rpt_ctx* ctx, const rpt_dataset* data,
                                   const rpt_dataset* queries, int32_t k, int32_t flags,
                                   int32_t* ids_host, double* dist_host);
+/* Both entry points take SVector (CSR) data with CSR queries too (same d, same dtype, f64 or f32
+ * values; a dense / CSR pair is RPT_E_ARG).  The candidates are the rows 0 .. n-1; the answer is
+ * the k best by (distance, id), NaN behind every number; with fewer than k rows the unused slots
+ * are id -1, distance +inf.  Two distances, the two rpt_knn_* has on CSR data:
+ *   flags 0                   the true Euclidean distance, evaluated as rpt_knn_* evaluates it:
+ *                             sqrt(max(0, |q|^2 + sum over the row's nonzeros of ((x_j - q_j)^2 -
+ *                             q_j^2))) in double, within about 1e-8 |q| absolute (|q|^2 is summed
+ *                             in a row's order: a query that is a stored row is at distance
+ *                             exactly 0 from it and from its copies)
+ *   RPT_KNN_METRIC_REFERENCE  (rpt_brute_knn_metric_host) the reference's truncating metricSSL2
+ *                             (Internal.hs:389-393 over binSS :435-450), bit-exact: what
+ *                             `recallWith metricL2` of the reference computes on SVector rows.
+ *                             Dense data: RPT_E_ARG, as before.
+ * RPT_KNN_METRIC_COSINE / _INNER on CSR data: RPT_E_UNSUPPORTED.
+ * One workgroup answers a tile of queries (dense-ified in LDS) against a block of rows streamed
+ * once; the option brute_csr_tile sets the tile, the answer does not depend on it. */
+/* ... and into device arrays ids_dev / dist_dev [nq][k], for dense data (flags 0,
+ * RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER) and CSR data (flags 0, RPT_KNN_METRIC_REFERENCE):
+ * enqueued on the ctx stream, not synchronised (rpt_ctx_sync before reading). */
+int32_t rpt_brute_knn_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                          int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev);
+
+/* recallWith (RPTree.hs:259-282) for a query batch, on the device, the division of :276-282 left
+ * to the caller: hits_host[i][t] = | set(candidates(tree t, query i)) n set(truth_i) |, where
+ * truth_i are the valid ids of the brute force of query i under `flags` (as rpt_brute_knn_dev: 0,
+ * RPT_KNN_METRIC_COSINE / _INNER on dense data, RPT_KNN_METRIC_REFERENCE on CSR data); the
+ * reference's value is the mean over t of hits[i][t] / k.  hits_host is [nq][T];
+ * truth_ids_host, if not NULL, receives the truth ids [nq][k] (-1 = unused slot).  Dense and CSR
+ * forests, batch and streamed.  A point counts once per tree.  The rpt_knn_last_* statistics are
+ * untouched (but RPT_KNN_METRIC_COSINE / _INNER reset rpt_knn_last_uncertified, as
+ * rpt_brute_knn_metric_host does). */
+int32_t rpt_recall_hits_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                             const rpt_dataset* queries, int32_t k, int32_t flags,
+                             int32_t* hits_host /*[nq][T]*/,
+                             int32_t* truth_ids_host /*[nq][k], may be NULL*/);
 
 #ifdef __cplusplus
 }

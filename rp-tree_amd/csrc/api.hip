@@ -241,6 +241,7 @@ const OptDesc kOptions[] = {
     {"knn_csr_pre32", &rpt_options::knn_csr_pre32},
     {"knn_general", &rpt_options::knn_general},
     {"knn_shard_old", &rpt_options::knn_shard_old},
+    {"brute_csr_tile", &rpt_options::brute_csr_tile},
     {"comm_force_exchange", &rpt_options::comm_force_exchange},
     {"comm_inject_failure", &rpt_options::comm_inject_failure},
     {"comm_timeout_ms", &rpt_options::comm_timeout_ms},
@@ -1167,18 +1168,37 @@ int32_t rpt_knn_merge_records_dev(rpt_ctx* ctx, const void* records_dev, int64_t
   });
 }
 
+}  // extern "C"
+
+namespace {
+// the brute-force entry points: dense data with dense queries under 0 / RPT_KNN_METRIC_COSINE /
+// _INNER, CSR data with CSR queries under 0 / RPT_KNN_METRIC_REFERENCE
+int32_t check_brute(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t k,
+                    int32_t flags) {
+  RPT_ARG(ctx && data && queries, "NULL argument");
+  RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
+  RPT_ARG(data->csr == queries->csr, "data and queries must both be dense or both CSR");
+  RPT_ARG(data->d == queries->d && data->dtype == queries->dtype, "shape/dtype mismatch");
+  RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
+  if (data->csr) {
+    if (flags == RPT_KNN_METRIC_COSINE || flags == RPT_KNN_METRIC_INNER)
+      return fail(RPT_E_UNSUPPORTED, "RPT_KNN_METRIC_COSINE / _INNER: dense data only");
+    RPT_ARG(flags == 0 || flags == RPT_KNN_METRIC_REFERENCE,
+            "flags must be 0 or RPT_KNN_METRIC_REFERENCE for CSR data");
+  } else {
+    RPT_ARG(flags == 0 || flags == RPT_KNN_METRIC_COSINE || flags == RPT_KNN_METRIC_INNER,
+            "flags must be 0, RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER");
+  }
+  RPT_HIP(hipSetDevice(ctx->device));
+  return RPT_OK;
+}
+}  // namespace
+
+extern "C" {
+
 int32_t rpt_brute_knn_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
                            int32_t k, int32_t* ids_host, double* dist_host) {
-  return guarded([&]() -> int32_t {
-    if (ctx) dev_set_stream(ctx->stream);
-    RPT_ARG(ctx && data && queries && ids_host && dist_host, "NULL argument");
-    RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
-    RPT_ARG(!data->csr && !queries->csr, "brute-force kNN supports dense data only");
-    RPT_ARG(data->d == queries->d && data->dtype == queries->dtype, "shape/dtype mismatch");
-    RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
-    RPT_HIP(hipSetDevice(ctx->device));
-    return brute_knn(ctx, data, queries, k, ids_host, dist_host);
-  });
+  return rpt_brute_knn_metric_host(ctx, data, queries, k, 0, ids_host, dist_host);
 }
 
 int32_t rpt_brute_knn_metric_host(rpt_ctx* ctx, const rpt_dataset* data,
@@ -1186,15 +1206,33 @@ int32_t rpt_brute_knn_metric_host(rpt_ctx* ctx, const rpt_dataset* data,
                                   int32_t* ids_host, double* dist_host) {
   return guarded([&]() -> int32_t {
     if (ctx) dev_set_stream(ctx->stream);
-    RPT_ARG(ctx && data && queries && ids_host && dist_host, "NULL argument");
-    RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
-    RPT_ARG(flags == 0 || flags == RPT_KNN_METRIC_COSINE || flags == RPT_KNN_METRIC_INNER,
-            "flags must be 0, RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER");
-    RPT_ARG(!data->csr && !queries->csr, "brute-force kNN supports dense data only");
-    RPT_ARG(data->d == queries->d && data->dtype == queries->dtype, "shape/dtype mismatch");
-    RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
-    RPT_HIP(hipSetDevice(ctx->device));
+    RPT_ARG(ids_host && dist_host, "NULL argument");
+    RPT_TRY(check_brute(ctx, data, queries, k, flags));
     return brute_knn_metric(ctx, data, queries, k, flags, ids_host, dist_host);
+  });
+}
+
+int32_t rpt_brute_knn_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                          int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ids_dev && dist_dev, "NULL output");
+    RPT_TRY(check_brute(ctx, data, queries, k, flags));
+    return brute_knn_dev(ctx, data, queries, k, flags, ids_dev, dist_dev);
+  });
+}
+
+int32_t rpt_recall_hits_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                             const rpt_dataset* queries, int32_t k, int32_t flags,
+                             int32_t* hits_host, int32_t* truth_ids_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_query(ctx, f, queries));
+    RPT_ARG(hits_host, "NULL output");
+    RPT_TRY(check_brute(ctx, data, queries, k, flags));
+    RPT_ARG(data->n == f->n && data->d == f->d, "data shape differs from the forest's");
+    RPT_ARG(queries->n * (int64_t)f->T <= 0x7fffffff, "too many (query, tree) pairs for one call");
+    return recall_hits(ctx, f, data, queries, k, flags, hits_host, truth_ids_host);
   });
 }
 

@@ -166,6 +166,7 @@ struct rpt_options {
   int64_t knn_metric_exact = 0;  // kNN, cosine / inner product: every query on the exact kernel (no certified cut)
   int64_t knn_csr_pre32 = 0;    // kNN: rank CSR f64 rows on their (u16 column, f32 value) shadow
   int64_t knn_general = 0;      // kNN: unfused general path
+  int64_t brute_csr_tile = 0;   // brute force on CSR rows: queries per workgroup (0 = auto; 1, 2, 4 or 8)
   int64_t knn_shard_old = 0;    // kNN: small shards keep the round-3 one-wave kernel (in-kernel traversal, fixed k')
   int64_t comm_force_exchange = 0;  // sharded kNN: a one-rank communicator runs record -> all-gather -> merge too
   int64_t comm_inject_failure = 0;  // sharded kNN (test hook): this device's shard reports a failure
@@ -369,9 +370,16 @@ int32_t knn_merge_dev(rpt_ctx* ctx, const int32_t* ids_dev, const double* dist_d
                       int32_t* out_count);
 int32_t brute_knn(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
                   int32_t* ids_host, double* dist_host);
-// metric: 0 = L2 (brute_knn), RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER
+// metric: 0 = L2 (brute_knn), RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER; CSR data: 0 or
+// RPT_KNN_METRIC_REFERENCE
 int32_t brute_knn_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
                          int32_t metric, int32_t* ids_host, double* dist_host);
+// device outputs [nq][k], enqueued on the ctx stream; flags: 0, RPT_KNN_METRIC_COSINE / _INNER
+// (dense data) or RPT_KNN_METRIC_REFERENCE (CSR data)
+int32_t brute_knn_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
+                      int32_t flags, int32_t* ids_dev, double* dist_dev);
+int32_t recall_hits(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                    int32_t k, int32_t flags, int32_t* hits_host, int32_t* truth_ids_host);
 int32_t knn_h(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
               int32_t k, int64_t* off_host, int32_t* ids_host, double* dist_host, int64_t cap,
               int64_t* total);

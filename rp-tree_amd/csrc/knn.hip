@@ -4798,51 +4798,450 @@ int32_t knn_merge_dev(rpt_ctx* ctx, const int32_t* ids_dev, const double* dist_d
   return RPT_OK;
 }
 
-int32_t brute_knn(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
-                  int32_t* ids_host, double* dist_host) {
+namespace {
+// ---- brute force over CSR rows, query-tiled ---------------------------------
+// One workgroup answers a TILE of QT queries against a block of consecutive rows: the queries
+// are dense-ified into LDS interleaved (qs[j * QT + i] = coordinate j of query i, so the QT values
+// a nonzero meets are one contiguous LDS read), the rows are streamed ONCE per tile — sixteen
+// lanes per row, kBcU rows per group in flight, the coalesced 16-byte column / value loads of
+// csr_rows_dist2 — and every nonzero is evaluated against all QT queries from registers.  A
+// row's sum is added in csr_rows_dist2's order (four nonzeros per lane in index order, then the
+// fixed butterfly of the group), so a distance does not depend on QT or on the row block.
+// Selection: per query an LDS buffer of `cap` entries, the best k so far at its front.  An entry
+// is appended only if it beats the k-th best so far (rows arrive in ascending id order, so an
+// equal distance loses), and the buffer is sorted (merge_best, total order: NaN behind every
+// number) when the next batch of rows might not fit.
+// RPT_KNN_METRIC_REFERENCE: the truncating merge of metricSSL2 (topk_csr_kernel's refm branch),
+// one thread per (row, query) pair.
+// Grid: x = query tile, y = row block; block y writes its lists at out_*[y][nq][k].
+constexpr int kBcThreads = 512;
+constexpr int kBcU = 4;                              // rows per 16-lane group in flight
+constexpr int kBcGroups = kBcThreads / 16;
+constexpr int kBcRows = kBcGroups * kBcU;            // rows per batch
+static_assert((kBcRows & (kBcRows - 1)) == 0 && kBcThreads % kBcRows == 0, "batch shape");
+
+template <class TD, int QT>
+__global__ __launch_bounds__(kBcThreads) void brute_csr_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+    const TD* __restrict__ val, int64_t nnz, int64_t n, int d,
+    const int64_t* __restrict__ qrowptr, const int32_t* __restrict__ qcol,
+    const TD* __restrict__ qval, int64_t nq, int k, int cap, int64_t rows_per_block, int refm,
+    int32_t* __restrict__ out_ids, double* __restrict__ out_dist, int32_t* __restrict__ out_cnt) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* qs = reinterpret_cast<double*>(smem);                                   // [d][QT]
+  Entry* bufs = reinterpret_cast<Entry*>(smem + (size_t)d * QT * sizeof(double));  // [QT][cap]
+  __shared__ double s_qn2[QT], s_thr[QT];
+  __shared__ int s_fill[QT], s_have[QT];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t q0 = (int64_t)blockIdx.x * QT;
+  const int nqt = nq - q0 < QT ? (int)(nq - q0) : QT;
+  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+  for (int j = tid; j < d * QT; j += kBcThreads) qs[j] = 0.0;
+  if (tid < QT) {
+    s_fill[tid] = 0;
+    s_have[tid] = 0;
+    s_thr[tid] = 0.0;
+    s_qn2[tid] = 0.0;
+  }
+  __syncthreads();
+  if (!refm) {
+    for (int i = 0; i < nqt; ++i)
+      for (int64_t j = qrowptr[q0 + i] + tid; j < qrowptr[q0 + i + 1]; j += kBcThreads)
+        qs[(int64_t)qcol[j] * QT + i] = (double)qval[j];
+    __syncthreads();
+    // |q|^2 over the query's nonzero list in the order a ROW's sum is added (four nonzeros per
+    // lane of a 16-lane group, then the butterfly): against a row that equals the query every term
+    // is -(q_j^2) exactly, the row's sum is -|q|^2 to the bit, and a stored row's distance to
+    // itself (and to its copies) is exactly 0 instead of the rounding noise of two summation orders
+    for (int i = wave; i < nqt; i += kBcThreads / 64) {
+      const int64_t a = qrowptr[q0 + i], b = qrowptr[q0 + i + 1];
+      double s = 0.0;
+      for (int64_t j = a + 4 * (lane & 15); j < b; j += 64)
+        for (int e = 0; e < 4; ++e)
+          if (j + e < b) {
+            const double v = (double)qval[j + e];
+            s += v * v;
+          }
+      for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);
+      if (lane == 0) s_qn2[i] = s;
+    }
+    __syncthreads();
+  }
+  auto push = [&](int i, double dist, int row) {
+    if (!s_have[i] || (dist == dist && !(dist >= s_thr[i])))
+      bufs[i * cap + atomicAdd(&s_fill[i], 1)] = Entry{dist, row, row};
+  };
+  // sorts query i's buffer, keeps the best k in front; every thread calls
+  auto settle = [&](int i) {
+    Entry* buf = bufs + i * cap;
+    const int best = merge_best<true>(buf, s_fill[i], k, 0, nullptr);
+    __syncthreads();
+    if (tid == 0) {
+      s_fill[i] = best;
+      if (best == k) {
+        s_have[i] = 1;
+        s_thr[i] = buf[k - 1].dist;
+      }
+    }
+    __syncthreads();
+    return best;
+  };
+  for (int64_t b0 = r0; b0 < r1; b0 += kBcRows) {
+    if (refm) {
+      const int64_t row = b0 + (tid & (kBcRows - 1));
+      if (row < r1) {
+        const int64_t a1 = rowptr[row], b1 = rowptr[row + 1];
+        for (int i = tid / kBcRows; i < nqt; i += kBcThreads / kBcRows) {
+          int64_t i1 = a1, i2 = qrowptr[q0 + i];
+          const int64_t b2 = qrowptr[q0 + i + 1];
+          double acc = 0.0;
+          while (i1 < b1 && i2 < b2) {
+            const int il = col[i1], ir = qcol[i2];
+            double df;
+            if (il == ir) {
+              df = (double)val[i1] - (double)qval[i2];
+              ++i1;
+              ++i2;
+            } else if (il < ir) {
+              df = (double)val[i1] - 0.0;
+              ++i1;
+            } else {
+              df = 0.0 - (double)qval[i2];
+              ++i2;
+            }
+            acc = acc + df * df;
+          }
+          push(i, sqrt(acc), (int)row);
+        }
+      }
+    } else {
+      struct __attribute__((packed, aligned(4))) C4 { int v[4]; };
+      struct __attribute__((packed, aligned(4))) V4 { TD v[4]; };
+      const int grp = tid >> 4, l16 = tid & 15;
+      int64_t ra[kBcU], rb[kBcU];
+      double s[kBcU][QT];
+#pragma unroll
+      for (int u = 0; u < kBcU; ++u) {
+        const int64_t row = b0 + u * kBcGroups + grp;
+        const bool ok = row < r1;
+        ra[u] = rowptr[ok ? row : r0];
+        rb[u] = ok ? rowptr[row + 1] : ra[u];
+#pragma unroll
+        for (int i = 0; i < QT; ++i) s[u][i] = 0.0;
+      }
+      for (int64_t t = 4 * l16;; t += 64) {
+        C4 c[kBcU];
+        V4 v[kBcU];
+        bool more = false;
+#pragma unroll
+        for (int u = 0; u < kBcU; ++u) {
+          const int64_t j = ra[u] + t;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            c[u].v[e] = 0;
+            v[u].v[e] = (TD)0;
+          }
+          if (j < rb[u]) {
+            if (j + 4 <= nnz) {  // may run past the row's end (masked below), never past the arrays'
+              c[u] = *reinterpret_cast<const C4*>(col + j);
+              v[u] = *reinterpret_cast<const V4*>(val + j);
+            } else {
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+                if (j + e < rb[u]) {
+                  c[u].v[e] = col[j + e];
+                  v[u].v[e] = val[j + e];
+                }
+            }
+          }
+          more = more || j + 64 < rb[u];
+        }
+#pragma unroll
+        for (int u = 0; u < kBcU; ++u) {
+          const int64_t j = ra[u] + t;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const bool ok = j + e < rb[u];
+            const double* qp = qs + (int64_t)(ok ? c[u].v[e] : 0) * QT;
+            const double x = (double)v[u].v[e];
+#pragma unroll
+            for (int i = 0; i < QT; ++i) {
+              const double qj = qp[i];
+              const double df = x - qj;
+              const double term = df * df - qj * qj;
+              s[u][i] += ok ? term : 0.0;
+            }
+          }
+        }
+        if (!__any(more)) break;
+      }
+#pragma unroll
+      for (int u = 0; u < kBcU; ++u) {
+        const int64_t row = b0 + u * kBcGroups + grp;
+#pragma unroll
+        for (int i = 0; i < QT; ++i) {
+          double a = s[u][i];
+          for (int o = 8; o > 0; o >>= 1) a += __shfl_xor(a, o);  // csr_rows_dist2's butterfly
+          if (l16 == 0 && row < r1 && i < nqt) {
+            const double t = a + s_qn2[i];
+            push(i, sqrt(t > 0 ? t : 0.0), (int)row);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // a batch appends at most kBcRows entries to a buffer: sort the ones the next might overflow
+    unsigned need = 0;
+    for (int i = 0; i < nqt; ++i) need |= (s_fill[i] > cap - kBcRows ? 1u : 0u) << i;
+    __syncthreads();
+    for (int i = 0; i < nqt; ++i)
+      if (need >> i & 1) settle(i);
+  }
+  for (int i = 0; i < nqt; ++i) {
+    const int best = settle(i);
+    const Entry* buf = bufs + i * cap;
+    const int64_t o = (int64_t)blockIdx.y * nq + q0 + i;
+    for (int r = tid; r < k; r += kBcThreads) {
+      const bool ok = r < best;
+      out_ids[o * k + r] = ok ? buf[r].id : -1;
+      out_dist[o * k + r] = ok ? buf[r].dist : __longlong_as_double(0x7ff0000000000000LL);
+    }
+    if (tid == 0) out_cnt[o] = best;
+    __syncthreads();
+  }
+}
+
+static inline int brute_csr_cap(int k) {
+  int cap = 256;
+  while (cap < k + kBcRows) cap <<= 1;
+  return cap;
+}
+static inline size_t brute_csr_smem(int d, int qt, int k) {
+  return (size_t)d * qt * sizeof(double) + (size_t)qt * brute_csr_cap(k) * sizeof(Entry);
+}
+constexpr size_t kBcLds = 150 * 1024;  // the budget the other query kernels keep (of 160 KB)
+
+template <class TD, int QT>
+static int32_t launch_brute_csr_t(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k,
+                                  int refm, int64_t rows_per_block, int nblk, int32_t* ids,
+                                  double* dist, int32_t* cnt) {
+  const size_t smem = brute_csr_smem(data->d, QT, k);
+  if (smem > 64 * 1024)
+    RPT_HIP(hipFuncSetAttribute((const void*)brute_csr_kernel<TD, QT>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  const int64_t tiles = (q->n + QT - 1) / QT;
+  hipLaunchKernelGGL((brute_csr_kernel<TD, QT>), dim3((unsigned)tiles, (unsigned)nblk),
+                     dim3(kBcThreads), smem, ctx->stream, data->rowptr, data->col,
+                     (const TD*)data->val, data->nnz, data->n, data->d, q->rowptr, q->col,
+                     (const TD*)q->val, q->n, k, brute_csr_cap(k), rows_per_block, refm, ids, dist,
+                     cnt);
+  RPT_HIP(hipGetLastError());
+  return RPT_OK;
+}
+
+template <class TD>
+static int32_t launch_brute_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k,
+                                int refm, int qt, int64_t rows_per_block, int nblk, int32_t* ids,
+                                double* dist, int32_t* cnt) {
+  switch (qt) {
+    case 8: return launch_brute_csr_t<TD, 8>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt);
+    case 4: return launch_brute_csr_t<TD, 4>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt);
+    case 2: return launch_brute_csr_t<TD, 2>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt);
+    default: return launch_brute_csr_t<TD, 1>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt);
+  }
+}
+
+// queries per workgroup: the option brute_csr_tile (rounded down to 1, 2, 4 or 8), else the
+// largest tile up to 4 the batch can use (measured at C3, 1 000 queries: 240 / 154 / 120 / 127 ms
+// for QT = 1 / 2 / 4 / 8 — from QT = 4 on the kernel is bound by its arithmetic and LDS reads, not
+// by the bytes it streams); halved until the tile's LDS fits (QT = 1 fits whenever the
+// `d too large` rule of the query kernels holds)
+static int brute_csr_tile(const rpt_ctx* ctx, int d, int k, int64_t nq) {
+  int qt = 8;
+  if (ctx->opt.brute_csr_tile > 0) {
+    while (qt > ctx->opt.brute_csr_tile) qt >>= 1;
+  } else {
+    qt = 4;
+    while (qt > 1 && qt / 2 >= nq) qt >>= 1;
+  }
+  while (qt > 1 && brute_csr_smem(d, qt, k) > kBcLds) qt >>= 1;
+  return qt;
+}
+
+// exhaustive kNN of CSR queries over CSR rows 0 .. n-1, k best by (distance, id), into device
+// arrays [nq][k]; cnt: [nq] ints of device scratch.  Enqueues only.
+static int32_t brute_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k, int refm,
+                         int32_t* ids_dev, double* dist_dev, int32_t* cnt_dev) {
+  RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
+  RPT_ARG(data->n <= 0x7fffffff, "too many rows");
+  const int64_t nq = q->n, n = data->n;
+  const int qt = brute_csr_tile(ctx, data->d, k, nq);
+  // few query tiles: split the rows over enough workgroups for two per CU, each with at least
+  // 4096 rows, at most as many as one merge launch takes; the row blocks are "shards" in ascending
+  // id order for merge_kernel, whose (distance, shard, rank) order is then (distance, id)
+  const int64_t tiles = (nq + qt - 1) / qt;
+  int64_t nblk = (2 * (int64_t)ctx->n_cu + tiles - 1) / tiles;
+  nblk = std::min(nblk, std::min<int64_t>(kMergeMax / k, n / 4096));
+  nblk = std::max<int64_t>(nblk, 1);
+  int64_t rows = (n + nblk - 1) / nblk;
+  rows = std::max<int64_t>((rows + kBcRows - 1) / kBcRows * kBcRows, kBcRows);
+  nblk = std::max<int64_t>((n + rows - 1) / rows, 1);
+  ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
+  if (nblk == 1) {
+    if (data->dtype == RPT_F64)
+      return launch_brute_csr<double>(ctx, data, q, k, refm, qt, rows, 1, ids_dev, dist_dev, cnt_dev);
+    return launch_brute_csr<float>(ctx, data, q, k, refm, qt, rows, 1, ids_dev, dist_dev, cnt_dev);
+  }
+  DevBuf<int32_t> pi, pc;
+  DevBuf<double> pd;
+  RPT_TRY(pi.alloc((size_t)nblk * nq * k));
+  RPT_TRY(pd.alloc((size_t)nblk * nq * k));
+  RPT_TRY(pc.alloc((size_t)nblk * nq));
+  if (data->dtype == RPT_F64)
+    RPT_TRY(launch_brute_csr<double>(ctx, data, q, k, refm, qt, rows, (int)nblk, pi.p, pd.p, pc.p));
+  else
+    RPT_TRY(launch_brute_csr<float>(ctx, data, q, k, refm, qt, rows, (int)nblk, pi.p, pd.p, pc.p));
+  // (the partial lists are released on return: the allocator hands a block out again only after
+  // the stream it was freed on has been synchronised)
+  return knn_merge_dev(ctx, pi.p, pd.p, pc.p, 0, (int32_t)nblk, nq, k, 0, ids_dev, dist_dev, cnt_dev);
+}
+
+// ---- recallWith on the device: |candidates(tree t, query i) ∩ truth_i| --------------------------
+// One workgroup per (query, tree): the k truth ids are sorted in LDS, every candidate id of the
+// tree's leaf ranges is looked up by bisection and MARKS the truth slot it equals; the marked slots
+// are counted.  Marking makes the count a set intersection whatever the ranges hold (the reference
+// intersects sets, RPTree.hs:276-282) — and the ranges of one tree are disjoint anyway: a batch
+// tree's perm row is a permutation cut into leaves, and a streamed tree's Tips are disjoint slices
+// [xoff, xoff + xlen) of its perm row, every inserted point stored in exactly one Tip.
+__global__ __launch_bounds__(256) void recall_hits_kernel(const int32_t* __restrict__ truth, int k,
+                                                          const int32_t* __restrict__ perm,
+                                                          const Range* __restrict__ ranges,
+                                                          const int64_t* __restrict__ rng_off, int T,
+                                                          int32_t* __restrict__ hits) {
+  __shared__ int s_id[1024];
+  __shared__ int s_hit[1024];
+  __shared__ int s_cnt;
+  const int64_t qt = blockIdx.x, q = qt / T;
+  int np = 1;
+  while (np < k) np <<= 1;
+  for (int i = threadIdx.x; i < np; i += blockDim.x) {
+    const int id = i < k ? truth[q * k + i] : -1;
+    s_id[i] = id < 0 ? 0x7fffffff : id;  // unused slots sort last and equal no candidate
+    s_hit[i] = 0;
+  }
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  for (int kk = 2; kk <= np; kk <<= 1)
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < (np >> 1); i += blockDim.x) {
+        const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
+        const bool up = (lo & kk) == 0;
+        const int a = s_id[lo], b = s_id[hi];
+        if (up ? b < a : a < b) {
+          s_id[lo] = b;
+          s_id[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  for (int64_t r = rng_off[qt]; r < rng_off[qt + 1]; ++r) {
+    const Range rg = ranges[r];
+    for (int i = threadIdx.x; i < rg.n; i += blockDim.x) {
+      const int id = perm[rg.poff + i];
+      int lo = 0, hi = np;  // first slot with s_id >= id
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s_id[mid] < id) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo < np && s_id[lo] == id) s_hit[lo] = 1;
+    }
+  }
+  __syncthreads();
+  int c = 0;
+  for (int i = threadIdx.x; i < np; i += blockDim.x) c += s_hit[i];
+  if (c) atomicAdd(&s_cnt, c);
+  __syncthreads();
+  if (threadIdx.x == 0) hits[qt] = s_cnt;
+}
+
+}  // namespace
+
+// exhaustive kNN into device arrays [nq][k] (k best by (distance, id); unused slots id -1, +inf):
+// dense data under L2 (flags 0) or RPT_KNN_METRIC_COSINE / _INNER through the identity mode of the
+// query kernels, CSR data under the true L2 or RPT_KNN_METRIC_REFERENCE through brute_csr_kernel.
+// Enqueues on the ctx stream, does not synchronise.
+int32_t brute_knn_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
+                      int32_t flags, int32_t* ids_dev, double* dist_dev) {
   RPT_ARG(k <= kBuf / 2, "k too large");
   const int64_t nq = q->n;
   if (nq == 0) return RPT_OK;
-  DevBuf<int32_t> ids, cnt;
+  DevBuf<int32_t> cnt;
+  RPT_TRY(cnt.alloc((size_t)nq));
+  if (data->csr)
+    return brute_csr(ctx, data, q, k, (flags & RPT_KNN_METRIC_REFERENCE) ? 1 : 0, ids_dev, dist_dev,
+                     cnt.p);
+  const int32_t metric = flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER);
+  if (metric) {
+    ctx->last_uncertified = 0;
+    ctx->metric_unc_pending = false;
+    DevBuf<int32_t> unc;
+    RPT_TRY(unc.alloc((size_t)nq));
+    return launch_metric(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, metric, unc.p, ids_dev,
+                         dist_dev, cnt.p);
+  }
+  if (data->dtype == RPT_F64)
+    return launch_topk_dense<double>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, ids_dev,
+                                     dist_dev, cnt.p);
+  if (data->dtype == RPT_F32)
+    return launch_topk_dense<float>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, ids_dev,
+                                    dist_dev, cnt.p);
+  return launch_topk_dense<__hip_bfloat16>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0,
+                                           ids_dev, dist_dev, cnt.p);
+}
+
+int32_t brute_knn_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
+                         int32_t metric, int32_t* ids_host, double* dist_host) {
+  const int64_t nq = q->n;
+  if (nq == 0) return RPT_OK;
+  DevBuf<int32_t> ids;
   DevBuf<double> dist;
   RPT_TRY(ids.alloc((size_t)nq * k));
   RPT_TRY(dist.alloc((size_t)nq * k));
-  RPT_TRY(cnt.alloc((size_t)nq));
-  if (data->dtype == RPT_F64)
-    RPT_TRY(launch_topk_dense<double>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, ids.p,
-                                      dist.p, cnt.p));
-  else if (data->dtype == RPT_F32)
-    RPT_TRY(launch_topk_dense<float>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, ids.p,
-                                     dist.p, cnt.p));
-  else
-    RPT_TRY(launch_topk_dense<__hip_bfloat16>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0,
-                                              ids.p, dist.p, cnt.p));
+  RPT_TRY(brute_knn_dev(ctx, data, q, k, metric, ids.p, dist.p));
   RPT_HIP(stream_sync(ctx->stream));
   RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
   RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
   return RPT_OK;
 }
 
-int32_t brute_knn_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
-                         int32_t metric, int32_t* ids_host, double* dist_host) {
-  if (metric == 0) return brute_knn(ctx, data, q, k, ids_host, dist_host);
-  RPT_ARG(k <= kBuf / 2, "k too large");
+int32_t brute_knn(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
+                  int32_t* ids_host, double* dist_host) {
+  return brute_knn_metric(ctx, data, q, k, 0, ids_host, dist_host);
+}
+
+// recallWith (RPTree.hs:276-282) for a query batch, the division left to the caller:
+// hits[i][t] = |candidates(tree t, query i) ∩ truth_i|, truth_i = the brute force under `flags`
+int32_t recall_hits(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                    int32_t k, int32_t flags, int32_t* hits_host, int32_t* truth_ids_host) {
   const int64_t nq = q->n;
   if (nq == 0) return RPT_OK;
-  ctx->last_uncertified = 0;
-  ctx->metric_unc_pending = false;
-  DevBuf<int32_t> ids, cnt;
+  DevBuf<int32_t> ids, hits;
   DevBuf<double> dist;
-  DevBuf<int32_t> unc;
   RPT_TRY(ids.alloc((size_t)nq * k));
   RPT_TRY(dist.alloc((size_t)nq * k));
-  RPT_TRY(cnt.alloc((size_t)nq));
-  RPT_TRY(unc.alloc((size_t)nq));
-  RPT_TRY(launch_metric(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, metric, unc.p, ids.p, dist.p,
-                        cnt.p));
+  RPT_TRY(hits.alloc((size_t)nq * f->T));
+  RPT_TRY(brute_knn_dev(ctx, data, q, k, flags, ids.p, dist.p));
+  QueryPlan pl;
+  RPT_TRY(make_plan(ctx, f, q, pl));
+  hipLaunchKernelGGL(recall_hits_kernel, dim3((unsigned)(nq * f->T)), dim3(256), 0, ctx->stream,
+                     ids.p, k, f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, hits.p);
+  RPT_HIP(hipGetLastError());
   RPT_HIP(stream_sync(ctx->stream));
-  RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-  RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+  RPT_HIP(hipMemcpy(hits_host, hits.p, (size_t)nq * f->T * 4, hipMemcpyDeviceToHost));
+  if (truth_ids_host)
+    RPT_HIP(hipMemcpy(truth_ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
   return RPT_OK;
 }
 

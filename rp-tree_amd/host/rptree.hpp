@@ -135,6 +135,24 @@ class Dataset {
       for (int j = 0; j < d; ++j) flat[(size_t)i * d + j] = xs[(size_t)i].dvVec[(size_t)j];
     check(rpt_dataset_dense_host(ctx.get(), flat.data(), n, d, RPT_F64, &h_));
   }
+  // SVector rows as CSR (rowptr / col / val); `dim` is the rows' svDim
+  Dataset(Context& ctx, const std::vector<SVector>& xs, int dim) {
+    n = (int64_t)xs.size();
+    d = dim;
+    std::vector<int64_t> rowptr{0};
+    std::vector<int32_t> col;
+    std::vector<double> val;
+    for (auto& x : xs) {
+      for (auto& iv : x.svVec) {
+        col.push_back(iv.first);
+        val.push_back(iv.second);
+      }
+      rowptr.push_back((int64_t)col.size());
+    }
+    col.push_back(0);  // non-NULL pointers for an all-empty batch
+    val.push_back(0.0);
+    check(rpt_dataset_csr_host(ctx.get(), rowptr.data(), col.data(), val.data(), n, d, RPT_F64, &h_));
+  }
   ~Dataset() { rpt_dataset_free(h_); }
   Dataset(const Dataset&) = delete;
   Dataset& operator=(const Dataset&) = delete;
@@ -289,6 +307,64 @@ inline std::vector<int32_t> candidates(const RPForest& tts, int t, const DVector
   std::vector<int32_t> ids((size_t)(total > 0 ? total : 1));
   check(rpt_candidates(tts.ctx->get(), tts.get(), qs.get(), off.data(), ids.data(), total, &total));
   return std::vector<int32_t>(ids.begin() + off[(size_t)t], ids.begin() + off[(size_t)t + 1]);
+}
+
+inline std::vector<int32_t> candidates(const RPForest& tts, int t, const SVector& q) {
+  std::vector<SVector> qv{q};
+  Dataset qs(*tts.ctx, qv, tts.data->d);
+  std::vector<int64_t> off((size_t)tts.T + 1);
+  int64_t total = 0;
+  check(rpt_candidates(tts.ctx->get(), tts.get(), qs.get(), off.data(), nullptr, 0, &total));
+  std::vector<int32_t> ids((size_t)(total > 0 ? total : 1));
+  check(rpt_candidates(tts.ctx->get(), tts.get(), qs.get(), off.data(), ids.data(), total, &total));
+  return std::vector<int32_t>(ids.begin() + off[(size_t)t], ids.begin() + off[(size_t)t + 1]);
+}
+
+// ---- evaluation: exhaustive kNN and recallWith (RPTree.hs:259-282), dense and SVector data ----
+// flags: 0, metric_flags(Metric::Cosine / Inner) on dense data, RPT_KNN_METRIC_REFERENCE (the
+// reference's truncating metricSSL2) on SVector data
+struct BruteResult {
+  std::vector<int32_t> ids;  // [nq][k], -1 = unused slot
+  std::vector<double> dist;  // [nq][k]
+};
+inline BruteResult bruteKnn(Context& ctx, const Dataset& data, const Dataset& qs, int k, int32_t flags = 0) {
+  BruteResult r{std::vector<int32_t>((size_t)qs.n * k + 1), std::vector<double>((size_t)qs.n * k + 1)};
+  check(rpt_brute_knn_metric_host(ctx.get(), data.get(), qs.get(), k, flags, r.ids.data(), r.dist.data()));
+  r.ids.resize((size_t)qs.n * k);
+  r.dist.resize((size_t)qs.n * k);
+  return r;
+}
+// hits[i][t] = |candidates(tree t, query i) n true kNN of query i|, truth (optional) [nq][k]
+inline std::vector<int32_t> recallHits(const RPForest& tts, int k, const Dataset& qs, int32_t flags = 0,
+                                       std::vector<int32_t>* truth = nullptr) {
+  std::vector<int32_t> hits((size_t)qs.n * tts.T + 1);
+  if (truth) truth->assign((size_t)qs.n * k + 1, -1);
+  check(rpt_recall_hits_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), k, flags, hits.data(),
+                             truth ? truth->data() : nullptr));
+  hits.resize((size_t)qs.n * tts.T);
+  if (truth) truth->resize((size_t)qs.n * k);
+  return hits;
+}
+// per query: mean over the trees of hits / k, summed in tree order (RPTree.hs:276-282)
+inline std::vector<double> recallWithBatch(const RPForest& tts, int k, const Dataset& qs, int32_t flags = 0) {
+  const std::vector<int32_t> hits = recallHits(tts, k, qs, flags);
+  std::vector<double> out((size_t)qs.n);
+  for (int64_t i = 0; i < qs.n; ++i) {
+    double acc = 0.0;
+    for (int t = 0; t < tts.T; ++t) acc += (double)hits[(size_t)i * tts.T + t] / (double)k;
+    out[(size_t)i] = acc / (double)tts.T;
+  }
+  return out;
+}
+inline double recallWith(const RPForest& tts, int k, const DVector& q, Metric metric = Metric::L2) {
+  std::vector<DVector> qv{q};
+  Dataset qs(*tts.ctx, qv);
+  return recallWithBatch(tts, k, qs, metric_flags(metric))[0];
+}
+inline double recallWith(const RPForest& tts, int k, const SVector& q, bool reference_metric = false) {
+  std::vector<SVector> qv{q};
+  Dataset qs(*tts.ctx, qv, tts.data->d);
+  return recallWithBatch(tts, k, qs, reference_metric ? RPT_KNN_METRIC_REFERENCE : 0)[0];
 }
 
 }  // namespace rptree

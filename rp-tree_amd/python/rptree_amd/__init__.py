@@ -34,7 +34,7 @@ __all__ = [
     "treeSize", "leafSizes", "metricL2", "inner", "project", "splitSegments", "topology",
     "bruteKnn", "RPTError", "forest", "tree", "saveForest", "loadForest", "importForest",
     "knnH", "knnHBatch", "knnPQ", "candidatesBatch", "to_bf16", "from_bf16", "RPStreamForest",
-    "metricCosine", "metricInner",
+    "metricCosine", "metricInner", "recallWithBatch", "recallHits",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -826,15 +826,26 @@ def knnH(distf, k, tts, q):
     return [(float(dist[i]), int(ids[i])) for i in range(int(off[0]), int(off[1]))]
 
 
-def bruteKnn(forest_or_data, qs, k, ctx=None, metric=None):
-    """exhaustive kNN on the device, ties by ascending id; metric: None / metricL2, metricCosine or
-    metricInner"""
+def _brute_flags(data, metric, reference_metric):
+    flags = _metric_flag(metric)
+    if reference_metric and data.is_csr:          # dense rows: metricDDL2 is what they get anyway
+        if flags:
+            raise ValueError("reference_metric is an L2 metric: not with metricCosine / metricInner")
+        flags |= RPT_KNN_METRIC_REFERENCE
+    return flags
+
+
+def bruteKnn(forest_or_data, qs, k, ctx=None, metric=None, reference_metric=False):
+    """exhaustive kNN on the device, the k best by (distance, id); metric: None / metricL2,
+    metricCosine or metricInner (the last two: dense data).  SVector (CSR) data: the true Euclidean
+    distance, or with reference_metric the reference's truncating metricSSL2 (Internal.hs:389-393),
+    bit-exact."""
     data = forest_or_data.data if isinstance(forest_or_data, RPForest) else forest_or_data
     ctx = ctx or data.ctx
     qd, nq = _query_dataset(ctx, data, qs)
     ids = np.empty((nq, k), dtype=np.int32)
     dist = np.empty((nq, k), dtype=np.float64)
-    flags = _metric_flag(metric)
+    flags = _brute_flags(data, metric, reference_metric)
     if flags:
         check(lib().rpt_brute_knn_metric_host(ctx._h, data._h, qd._h, int(k), flags, _vp(ids),
                                               _vp(dist)))
@@ -843,18 +854,36 @@ def bruteKnn(forest_or_data, qs, k, ctx=None, metric=None):
     return ids, dist
 
 
-def recallWith(distf, tt, k, q):
+def recallHits(distf, forest, k, qs, reference_metric=False):
+    """-> (hits[nq][T], truth[nq][k]): hits[i][t] = |candidates(tree t, query i) ∩ true kNN of
+    query i|, the truth by brute force under distf, both on the device (rpt_recall_hits_host)."""
+    ctx = forest.ctx
+    qd, nq = _query_dataset(ctx, forest.data, qs)
+    hits = np.empty((nq, forest.T), dtype=np.int32)
+    truth = np.empty((nq, k), dtype=np.int32)
+    flags = _brute_flags(forest.data, distf, reference_metric)
+    check(lib().rpt_recall_hits_host(ctx._h, forest._h, forest.data._h, qd._h, int(k), flags,
+                                     _vp(hits), _vp(truth)))
+    return hits, truth
+
+
+def recallWithBatch(distf, forest, k, qs, reference_metric=False):
+    """recallWith for a batch of queries -> recall[nq]: per query the mean over trees of
+    |candidates(tree, q) ∩ true kNN| / k (RPTree.hs:276-282), summed in tree order.  Dense and
+    SVector forests, batch and streamed; reference_metric: the truth of SVector data under the
+    reference's own metricSSL2."""
+    hits, _ = recallHits(distf, forest, k, qs, reference_metric)
+    out = np.empty(hits.shape[0], dtype=np.float64)
+    for i, row in enumerate(hits.tolist()):
+        out[i] = sum(h / k for h in row) / len(row)
+    return out
+
+
+def recallWith(distf, tt, k, q, reference_metric=False):
     """RPTree.hs:259-282: mean over trees of |candidates(tree, q) ∩ true kNN| / k, the truth by
-    brute force over all points under distf (metricL2, metricCosine or metricInner)."""
-    _metric_flag(distf)
-    true_ids, _ = bruteKnn(tt, q, k, metric=distf)
-    kk = set(int(i) for i in true_ids[0] if i >= 0)
-    off, ids = candidatesBatch(tt, q)
-    rs = []
-    for t in range(tt.T):
-        aa = set(ids[off[t]:off[t + 1]].tolist())
-        rs.append(len(aa & kk) / k)
-    return sum(rs) / len(rs)
+    brute force over all points under distf (metricL2, metricCosine or metricInner): the one-query
+    case of recallWithBatch."""
+    return float(recallWithBatch(distf, tt, k, q, reference_metric)[0])
 
 
 # ---------------------------------------------------------------------------------------

@@ -85,6 +85,8 @@ SYMBOLS = {
     "rpt_knn_sharded": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
     "rpt_brute_knn_host": (i32, [vp, vp, vp, i32, vp, vp]),
     "rpt_brute_knn_metric_host": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+    "rpt_brute_knn_dev": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+    "rpt_recall_hits_host": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
 }
 
 
