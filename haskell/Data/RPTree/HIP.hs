@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -49,6 +49,7 @@ foreign import ccall safe "rpt_knn_host"            c_knn_host       :: Ptr Ctx 
 foreign import ccall safe "rpt_knnh_host"           c_knnh_host      :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int64 -> Ptr Int32 -> Ptr Double -> Int64 -> Ptr Int64 -> IO Int32
 foreign import ccall safe "rpt_dataset_csr_host"    c_dataset_csr    :: Ptr Ctx -> Ptr Int64 -> Ptr Int32 -> Ptr Double -> Int64 -> Int32 -> Int32 -> Ptr (Ptr Dataset) -> IO Int32
 foreign import ccall safe "rpt_recall_hits_host"    c_recall_hits    :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_graph_host"      c_knn_graph_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
 -- multi-GPU (csrc/comm.hip on librccl): one process drives n devices; per-device arguments are
 -- arrays with one entry per device (Foreign.Marshal.Array.withArray)
@@ -226,6 +227,23 @@ knnMetricHIP :: Metric -> Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset ->
 knnMetricHIP m ctx f ds qs nq k = do
   ids <- VSM.new (nq * k); dist <- VSM.new (nq * k); cnt <- VSM.new nq
   VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_host ctx f ds qs (fromIntegral k) (metricFlag m) a b))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | The kNN graph of the forest's own points: 'knn metricL2 k' (RPTree.hs:174-176) with every stored
+-- point as the query, built leaf by leaf (rpt_knn_graph_host).  Row i holds the first k, by
+-- (distance, id), of the points j /= i that share a leaf with i in some tree, with metricDDL2's
+-- left fold (Internal.hs:403-406) as the distance; count[i] entries are valid, the rest are
+-- id -1, distance +Infinity.  @Just earlier@ folds an earlier answer over the same data set and k
+-- in (RPT_GRAPH_ACCUMULATE = 1: another forest, a tree shard); the order of folding does not matter.
+-- Dense batch forests, k <= 64; n = number of stored points.
+knnGraphHIP :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int -> Int
+            -> Maybe (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+            -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnGraphHIP ctx f ds n k earlier = do
+  (ids, dist, cnt, flags) <- case earlier of
+    Nothing -> (,,,) <$> VSM.new (n * k) <*> VSM.new (n * k) <*> VSM.new n <*> pure 0
+    Just (i0, d0, c0) -> (,,,) <$> VS.thaw i0 <*> VS.thaw d0 <*> VS.thaw c0 <*> pure 1
+  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_host ctx f ds (fromIntegral k) flags a b))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | SVector rows as a CSR dataset on the device (rpt_dataset_csr_host), for the extent of the

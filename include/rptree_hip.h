@@ -142,6 +142,7 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *   knn_wave (-1 auto, 0, 1), knn_kp, knn_kp16, knn_kp8, knn_no_pre32, knn_no_pre16, knn_no_pre8,
  *   knn_csr_pre32, knn_general
  *       query kernels; knn_kp8 > 0 also opts bf16 datasets into the int8 ranking tier
+ *   graph_general (0 / 1)          kNN graph: every leaf on the tiled kernel (rpt_knn_graph_*)
  *   brute_csr_tile (0 auto, n)     brute force over CSR rows: queries per workgroup (1, 2, 4 or 8; other
  *                                  values round down; halved while the tile does not fit LDS; auto
  *                                  takes up to 4)
@@ -340,6 +341,56 @@ int32_t rpt_knn_last_tier(rpt_ctx* ctx, int32_t* tier);
  * node share the 16-bit code of its median; the result does not depend on it), and how many of those
  * because a code histogram contradicted the node sizes (a defect if ever non-zero; tested to be 0) */
 int32_t rpt_build_last_handed_back(rpt_ctx* ctx, int64_t* nodes, int64_t* inconsistent);
+
+/* ---- kNN graph of the indexed points: knn (RPTree.hs:174-176) with EVERY STORED POINT as the
+ * query, distf = metricL2 (metricDDL2, Internal.hs:403-406), built leaf by leaf ----
+ * `f` is a batch forest (built or imported) over the dense data set `data`, rows 0 .. n-1.  For a
+ * point i:
+ *   mates(i)   the ids j != i that share a leaf with i in at least one tree.  A point is never its
+ *              own neighbour; a different id holding an equal row is an ordinary neighbour at
+ *              distance 0.
+ *   dist(i, j) sqrt(((0 + (x_i0 - x_j0)^2) + (x_i1 - x_j1)^2) + ...) in double: metricDDL2's left
+ *              fold, every difference, square and sum rounded on its own, no FMA; f32 and bf16
+ *              elements are widened exactly first.  The values are doubles and bit-exact against
+ *              this definition for all three dtypes (as the cosine / inner-product metrics are, and
+ *              unlike rpt_knn_*, whose L2 on f32 / bf16 rows is f32 arithmetic).  The fold is
+ *              symmetric bit for bit, dist(i, j) == dist(j, i): a pair is evaluated once.
+ *   answer     the first k of mates(i) ordered by (distance, id); NaN ranks behind every number,
+ *              NaNs among themselves by id.  count[i] = min(k, |mates(i)|); unused slots hold
+ *              id -1 and distance +inf.
+ * The forest decides only the membership of mates(i): the margin rule of `candidates`
+ * (RPTree.hs:289-314), which sends a query near a cut into both children, plays no part.  The
+ * graph is therefore NOT defined as the de-duplicated self-query rpt_knn_*; the two differ on the
+ * few points that rule sends both ways (3 of 3 000 entries in a trial of 6 000 points).
+ * No ranking shadow, certificate or fallback: every distance is the fold itself, so ties of any
+ * width and duplicate rows are ranked exactly, and rpt_knn_last_tier and the forest's ranking
+ * tiers are untouched.
+ * RPT_GRAPH_ACCUMULATE: the output arrays are also an input.  The valid entries already there
+ * (count[i] of them per row, sorted by (distance, id), free of i) join mates(i) with their stored
+ * distances; duplicate ids collapse to one entry.  The order is total and the union is a set, so
+ * folding forests over one data set (tree shards, several forests) in any order gives the same
+ * arrays.  Without the flag the arrays are output only.
+ * One launch per tree in stream order; within a tree one workgroup owns a point's list: no atomics,
+ * a deterministic result.  Leaves of up to 128 points take a one-workgroup kernel that evaluates
+ * every pair once; larger leaves (a depth cap, maxDepth 0 = all pairs) take a tiled kernel that
+ * evaluates every ordered pair; the context option graph_general sends every leaf there; the
+ * answer does not depend on it.  rpt_knn_graph_last_pairs: distances the last call evaluated,
+ * T * sum over leaves of s (s - 1) / 2 (one-workgroup kernel) or s (s - 1) (tiled kernel), s the
+ * leaf size (the padding lanes of a tile are not counted).
+ * Errors: k outside [1, RPT_GRAPH_MAX_K], data that is not the forest's data set shape (n, d,
+ * dtype), other flag bits: RPT_E_ARG.  CSR data, a streamed forest (explicit topology), the
+ * RPT_KNN_METRIC_* flags: RPT_E_UNSUPPORTED.  n = 0 and forests of depth 0 are valid.  An imported
+ * forest's perm rows must be permutations of 0 .. n-1 (rpt_forest_import checks the range only).
+ * _dev enqueues on the ctx stream and does not synchronise (rpt_ctx_sync before reading); _host
+ * synchronises.  ids / dist are [n][k], count is [n].  Timed under rpt_prof_* class 3. */
+#define RPT_GRAPH_ACCUMULATE 1
+#define RPT_GRAPH_MAX_K 64
+int32_t rpt_knn_graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                          int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+int32_t rpt_knn_graph_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                           int32_t flags, int32_t* ids_host, double* dist_host,
+                           int32_t* count_host);
+int32_t rpt_knn_graph_last_pairs(rpt_ctx* ctx, int64_t* pairs);
 
 /* multi-GPU merge: G per-shard results (shard g holds trees [g*T/G, (g+1)*T/G)), gathered
  * shard-major as ids_dev[G][nq][k] etc. (e.g. by an RCCL all-gather), merged into the

@@ -240,6 +240,7 @@ const OptDesc kOptions[] = {
     {"knn_metric_exact", &rpt_options::knn_metric_exact},
     {"knn_csr_pre32", &rpt_options::knn_csr_pre32},
     {"knn_general", &rpt_options::knn_general},
+    {"graph_general", &rpt_options::graph_general},
     {"knn_shard_old", &rpt_options::knn_shard_old},
     {"brute_csr_tile", &rpt_options::brute_csr_tile},
     {"comm_force_exchange", &rpt_options::comm_force_exchange},
@@ -747,6 +748,7 @@ static int32_t forest_alloc(rpt_ctx* ctx, const rpt_dataset* ds, const double* R
   f->L = L;
   f->min_leaf = min_leaf;
   f->pdtype = proj_dtype(ds->dtype);
+  f->dtype = ds->dtype;
   f->nodes = ((int64_t)1 << L) - 1;
   int32_t s = f->perm.alloc((size_t)T * f->n);
   if (s == RPT_OK) s = f->thr.alloc((size_t)T * f->nodes);
@@ -802,6 +804,7 @@ int32_t rpt_forest_stream_build(rpt_ctx* ctx, const rpt_dataset* ds, const doubl
     f->L = L;
     f->min_leaf = min_leaf;
     f->pdtype = proj_dtype(ds->dtype);
+    f->dtype = ds->dtype;
     f->nodes = ((int64_t)1 << (L + 1)) - 1;
     int32_t s = f->perm.alloc((size_t)T * f->n);
     if (s == RPT_OK) s = f->thr.alloc((size_t)T * f->nodes);
@@ -1113,6 +1116,67 @@ int32_t rpt_knn_last_tier(rpt_ctx* ctx, int32_t* tier) {
   return guarded([&]() -> int32_t {
     RPT_ARG(ctx && tier, "NULL argument");
     *tier = ctx->last_tier;
+    return RPT_OK;
+  });
+}
+
+// ---- kNN graph of the indexed points ------------------------------------------------------
+int32_t rpt_knn_graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                          int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ctx && f && data, "NULL argument");
+    RPT_ARG(f->ctx == ctx && data->ctx == ctx, "handles belong to another context");
+    if (flags > 0 && (flags & (RPT_KNN_METRIC_REFERENCE | RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)))
+      return fail(RPT_E_UNSUPPORTED, "the kNN graph is built under metricL2 only (no metric flags)");
+    RPT_ARG((flags & ~RPT_GRAPH_ACCUMULATE) == 0, "flags must be 0 or RPT_GRAPH_ACCUMULATE");
+    if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph takes dense data only (not CSR rows)");
+    if (f->xtopo)
+      return fail(RPT_E_UNSUPPORTED, "the kNN graph takes batch forests only (not a streamed forest)");
+    RPT_ARG(data->n == f->n && data->d == f->d && data->dtype == f->dtype,
+            "data is not the forest's data set (n, d, dtype)");
+    RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
+    RPT_ARG(f->n <= 0x7fffffff, "graph too large");
+    RPT_ARG(f->n == 0 || (ids_dev && dist_dev && count_dev), "NULL output");
+    RPT_HIP(hipSetDevice(ctx->device));
+    return knn_graph_dev(ctx, f, data, k, flags, ids_dev, dist_dev, count_dev);
+  });
+}
+
+int32_t rpt_knn_graph_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                           int32_t flags, int32_t* ids_host, double* dist_host,
+                           int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ctx && f && data, "NULL argument");
+    RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
+    const int64_t n = f->n;
+    RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL output");
+    DevBuf<int32_t> ids, cnt;
+    DevBuf<double> dist;
+    RPT_TRY(ids.alloc((size_t)n * k));
+    RPT_TRY(dist.alloc((size_t)n * k));
+    RPT_TRY(cnt.alloc((size_t)n));
+    if (n && flags == RPT_GRAPH_ACCUMULATE) {  // the arrays are an input too
+      RPT_HIP(hipMemcpy(ids.p, ids_host, (size_t)n * k * 4, hipMemcpyHostToDevice));
+      RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
+      RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    RPT_TRY(rpt_knn_graph_dev(ctx, f, data, k, flags, ids.p, dist.p, cnt.p));
+    RPT_HIP(stream_sync(ctx->stream));
+    if (n) {
+      RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
+      RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)n * k * 8, hipMemcpyDeviceToHost));
+      RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    return RPT_OK;
+  });
+}
+
+int32_t rpt_knn_graph_last_pairs(rpt_ctx* ctx, int64_t* pairs) {
+  return guarded([&]() -> int32_t {
+    RPT_ARG(ctx && pairs, "NULL argument");
+    *pairs = ctx->last_graph_pairs;
     return RPT_OK;
   });
 }

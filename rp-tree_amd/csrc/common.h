@@ -166,6 +166,7 @@ struct rpt_options {
   int64_t knn_metric_exact = 0;  // kNN, cosine / inner product: every query on the exact kernel (no certified cut)
   int64_t knn_csr_pre32 = 0;    // kNN: rank CSR f64 rows on their (u16 column, f32 value) shadow
   int64_t knn_general = 0;      // kNN: unfused general path
+  int64_t graph_general = 0;    // kNN graph: every leaf on the tiled kernel (64-row blocks), not the one-workgroup leaf kernel
   int64_t brute_csr_tile = 0;   // brute force on CSR rows: queries per workgroup (0 = auto; 1, 2, 4 or 8)
   int64_t knn_shard_old = 0;    // kNN: small shards keep the round-3 one-wave kernel (in-kernel traversal, fixed k')
   int64_t comm_force_exchange = 0;  // sharded kNN: a one-rank communicator runs record -> all-gather -> merge too
@@ -192,6 +193,7 @@ struct rpt_ctx {
   bool metric_unc_pending = false;
   int64_t last_candidates = 0;
   int64_t last_retries = 0;      // queries of the last fused kNN call that took the in-kernel wider second attempt
+  int64_t last_graph_pairs = 0;  // distances the last rpt_knn_graph_* call evaluated
   int32_t last_tier = 0;  // ranking tier of the last fused kNN call: 0 exact, 1 f32 shadow, 2 half, 3 int8
   // last build: nodes csub_kernel handed back to the general kernels (pivot codes shared by more
   // points than its pool), and how many of those for a histogram that contradicted the node
@@ -299,6 +301,7 @@ struct rpt_forest {
   int64_t n = 0;
   int32_t d = 0, T = 0, L = 0, min_leaf = 0;
   int32_t pdtype = RPT_F64;  // type of proj
+  int32_t dtype = RPT_F64;   // element type of the dataset the forest was built on / imported for
   int32_t mode = RPT_PROJ_AUTO;  // projection mode used by the build (queries reuse it)
   // set when a query batch had more than a quarter of its f32-prefilter cuts uncertified (many
   // equal distances: e.g. the queries are data points, found once per tree): later batches on this
@@ -380,6 +383,11 @@ int32_t brute_knn_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* 
                       int32_t flags, int32_t* ids_dev, double* dist_dev);
 int32_t recall_hits(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
                     int32_t k, int32_t flags, int32_t* hits_host, int32_t* truth_ids_host);
+// ---- kNN graph of the indexed points (graph.hip) -----------------------------------------
+// arguments checked by the caller (dense data of the forest's shape, batch topology, k <= 64);
+// flags: 0 or RPT_GRAPH_ACCUMULATE; enqueued on the ctx stream
+int32_t knn_graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                      int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
 int32_t knn_h(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
               int32_t k, int64_t* off_host, int32_t* ids_host, double* dist_host, int64_t cap,
               int64_t* total);

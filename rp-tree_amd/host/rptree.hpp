@@ -323,6 +323,39 @@ inline std::vector<int32_t> candidates(const RPForest& tts, int t, const SVector
 // ---- evaluation: exhaustive kNN and recallWith (RPTree.hs:259-282), dense and SVector data ----
 // flags: 0, metric_flags(Metric::Cosine / Inner) on dense data, RPT_KNN_METRIC_REFERENCE (the
 // reference's truncating metricSSL2) on SVector data
+// kNN graph of the forest's own points (rpt_knn_graph_host): knn (RPTree.hs:174-176) with every
+// stored point as the query, built leaf by leaf.  Row i of ids / dist holds the first k, by
+// (distance, id), of the points j != i that share a leaf with i in some tree; count[i] entries are
+// valid, the rest are id -1, distance +inf.  Distances are metricDDL2's left fold (Internal.hs:403-406).
+// accumulate: an earlier result over the same data set and k (another forest, a tree shard) whose
+// entries join the candidates (RPT_GRAPH_ACCUMULATE); the order of folding does not matter.
+struct GraphResult {
+  int k = 0;
+  std::vector<int32_t> ids;    // [n][k]
+  std::vector<double> dist;    // [n][k]
+  std::vector<int32_t> count;  // [n]
+};
+inline GraphResult knnGraph(const RPForest& tts, int k, const GraphResult* accumulate = nullptr) {
+  const size_t n = (size_t)tts.data->n;
+  GraphResult g;
+  if (accumulate) {
+    if (accumulate->k != k || accumulate->count.size() != n)
+      throw RPTError(RPT_E_ARG, "accumulate: a result of another data set or k");
+    g = *accumulate;
+  }
+  g.k = k;
+  g.ids.resize(n * (size_t)(k > 0 ? k : 0) + 1);  // + 1: non-NULL pointers for an empty data set
+  g.dist.resize(n * (size_t)(k > 0 ? k : 0) + 1);
+  g.count.resize(n + 1);
+  check(rpt_knn_graph_host(tts.ctx->get(), tts.get(), tts.data->get(), k,
+                           accumulate ? RPT_GRAPH_ACCUMULATE : 0, g.ids.data(), g.dist.data(),
+                           g.count.data()));
+  g.ids.resize(n * (size_t)k);
+  g.dist.resize(n * (size_t)k);
+  g.count.resize(n);
+  return g;
+}
+
 struct BruteResult {
   std::vector<int32_t> ids;  // [nq][k], -1 = unused slot
   std::vector<double> dist;  // [nq][k]

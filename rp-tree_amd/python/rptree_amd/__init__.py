@@ -22,7 +22,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import gen
-from ._lib import (RPT_BF16, RPT_F32, RPT_F64, RPT_KNN_DEDUP, RPT_KNN_DEDUP_DISTANCE,
+from ._lib import (RPT_BF16, RPT_F32, RPT_F64, RPT_GRAPH_ACCUMULATE, RPT_GRAPH_MAX_K, RPT_KNN_DEDUP, RPT_KNN_DEDUP_DISTANCE,
                    RPT_KNN_KEEP_DUPLICATES, RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER,
                    RPT_KNN_METRIC_REFERENCE,
                    RPT_PROJ_AUTO, RPT_PROJ_EXACT, RPT_PROJ_MFMA, RPTError, check, lib)
@@ -35,6 +35,7 @@ __all__ = [
     "bruteKnn", "RPTError", "forest", "tree", "saveForest", "loadForest", "importForest",
     "knnH", "knnHBatch", "knnPQ", "candidatesBatch", "to_bf16", "from_bf16", "RPStreamForest",
     "metricCosine", "metricInner", "recallWithBatch", "recallHits",
+    "knnGraph", "knnGraphDev", "knnGraphLastPairs",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -769,6 +770,50 @@ def knnBatch(k, forest, qs, dedup=False, vote=0, reference_metric=False, metric=
     check(lib().rpt_knn_host(ctx._h, forest._h, forest.data._h, qd._h, int(k), flags, _vp(ids),
                              _vp(dist), _vp(cnt)))
     return ids, dist, cnt
+
+
+def knnGraph(k, forest, accumulate=None):
+    """kNN graph of the forest's own points (rpt_knn_graph_host): knn (RPTree.hs:174-176) with every
+    stored point as the query, built leaf by leaf -> (ids[n][k], dist[n][k], count[n]).  Row i holds
+    the first k, by (distance, id), of the points j != i that share a leaf with i in some tree;
+    the distances are metricDDL2's left fold (Internal.hs:403-406) in double for every dtype;
+    unused slots are id -1, distance +inf.  accumulate: an earlier (ids, dist, count) over the
+    same data set and k (another forest, a tree shard) whose entries join the candidates; the
+    result does not depend on the order forests are folded in.  Dense batch forests, k <= 64."""
+    ctx, n = forest.ctx, forest.N
+    if accumulate is None:
+        flags = 0
+        ids = np.empty((n, k), dtype=np.int32)
+        dist = np.empty((n, k), dtype=np.float64)
+        cnt = np.empty(n, dtype=np.int32)
+    else:
+        flags = RPT_GRAPH_ACCUMULATE
+        ids = np.array(accumulate[0], dtype=np.int32, order="C")
+        dist = np.array(accumulate[1], dtype=np.float64, order="C")
+        cnt = np.array(accumulate[2], dtype=np.int32, order="C")
+        if ids.shape != (n, k) or dist.shape != (n, k) or cnt.shape != (n,):
+            raise ValueError("accumulate must be (ids[n][k], dist[n][k], count[n]) of this forest's n and k")
+    check(lib().rpt_knn_graph_host(ctx._h, forest._h, forest.data._h, int(k), flags, _vp(ids),
+                                   _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnGraphDev(k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
+    """knnGraph into device arrays (rpt_knn_graph_dev): int32 [n][k], float64 [n][k], int32 [n]
+    given as device addresses (e.g. torch tensors' data_ptr()).  Enqueued on the ctx stream, not
+    synchronised (forest.ctx.sync() before reading); with accumulate the arrays are an input too
+    and whatever filled them must have finished (see Dataset.dense_device)."""
+    check(lib().rpt_knn_graph_dev(forest.ctx._h, forest._h, forest.data._h, int(k),
+                                  RPT_GRAPH_ACCUMULATE if accumulate else 0, C.c_void_p(ids_ptr),
+                                  C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
+
+
+def knnGraphLastPairs(ctx=None):
+    """distances the last knnGraph call on ctx evaluated (rpt_knn_graph_last_pairs)"""
+    ctx = ctx or default_context()
+    v = C.c_int64()
+    check(lib().rpt_knn_graph_last_pairs(ctx._h, C.byref(v)))
+    return int(v.value)
 
 
 def knn_last_uncertified(ctx=None):

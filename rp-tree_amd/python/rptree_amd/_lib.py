@@ -16,6 +16,8 @@ RPT_PROJ_AUTO, RPT_PROJ_EXACT, RPT_PROJ_MFMA = 0, 1, 2
 RPT_KNN_KEEP_DUPLICATES, RPT_KNN_DEDUP, RPT_KNN_DEDUP_DISTANCE = 0, 1, 2
 RPT_KNN_METRIC_REFERENCE = 1 << 24
 RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER = 1 << 25, 1 << 26
+RPT_GRAPH_ACCUMULATE = 1
+RPT_GRAPH_MAX_K = 64
 RPT_COMM_UID_BYTES = 128
 
 i32, i64, f64 = C.c_int32, C.c_int64, C.c_double
@@ -68,6 +70,9 @@ SYMBOLS = {
     "rpt_build_last_handed_back": (i32, [vp, p_i64, p_i64]),
     "rpt_knn_last_uncertified": (i32, [vp, p_i64]),
     "rpt_knn_last_retries": (i32, [vp, p_i64]),
+    "rpt_knn_graph_dev": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+    "rpt_knn_graph_host": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+    "rpt_knn_graph_last_pairs": (i32, [vp, p_i64]),
     "rpt_knn_merge_dev": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp]),
     "rpt_knn_record_layout": (i32, [i64, i32, vp, vp, vp, vp]),
     "rpt_knn_merge_records_dev": (i32, [vp, vp, i64, i32, i64, i32, i32, vp, vp, vp]),
