@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -50,6 +50,7 @@ foreign import ccall safe "rpt_knnh_host"           c_knnh_host      :: Ptr Ctx 
 foreign import ccall safe "rpt_dataset_csr_host"    c_dataset_csr    :: Ptr Ctx -> Ptr Int64 -> Ptr Int32 -> Ptr Double -> Int64 -> Int32 -> Int32 -> Ptr (Ptr Dataset) -> IO Int32
 foreign import ccall safe "rpt_recall_hits_host"    c_recall_hits    :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_host"      c_knn_graph_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_graph_refine_host" c_knn_graph_refine_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
 -- multi-GPU (csrc/comm.hip on librccl): one process drives n devices; per-device arguments are
 -- arrays with one entry per device (Foreign.Marshal.Array.withArray)
@@ -244,6 +245,21 @@ knnGraphHIP ctx f ds n k earlier = do
     Nothing -> (,,,) <$> VSM.new (n * k) <*> VSM.new (n * k) <*> VSM.new n <*> pure 0
     Just (i0, d0, c0) -> (,,,) <$> VS.thaw i0 <*> VS.thaw d0 <*> VS.thaw c0 <*> pure 1
   VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_host ctx f ds (fromIntegral k) flags a b))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | NN-descent rounds over a kNN graph of the data set (rpt_knn_graph_refine_host): one round gives
+-- row i the first k, by (distance, id), of its neighbours, up to @reverse@ of the points that list i
+-- (0 = none) and all of their neighbours, with metricDDL2's left fold as the distance of every new
+-- entry; @iters@ rounds, ended early by a round that changes nothing.  Deterministic; no forest
+-- takes part.  The input vectors are not modified.  k and reverse <= 64; n = number of stored points.
+knnGraphRefineHIP :: Ptr Ctx -> Ptr Dataset -> Int -> Int -> Int -> Int
+                  -> (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+                  -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnGraphRefineHIP ctx ds _n k reverse iters (i0, d0, c0) = do
+  ids <- VS.thaw i0
+  dist <- VS.thaw d0
+  cnt <- VS.thaw c0
+  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_refine_host ctx ds (fromIntegral k) (fromIntegral reverse) (fromIntegral iters) 0 a b))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | SVector rows as a CSR dataset on the device (rpt_dataset_csr_host), for the extent of the

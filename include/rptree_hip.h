@@ -143,6 +143,8 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *   knn_csr_pre32, knn_general
  *       query kernels; knn_kp8 > 0 also opts bf16 datasets into the int8 ranking tier
  *   graph_general (0 / 1)          kNN graph: every leaf on the tiled kernel (rpt_knn_graph_*)
+ *   graph_refine_general (0 / 1)   kNN graph refinement: one point per workgroup for every k and
+ *                                  reverse (rpt_knn_graph_refine_*)
  *   brute_csr_tile (0 auto, n)     brute force over CSR rows: queries per workgroup (1, 2, 4 or 8; other
  *                                  values round down; halved while the tile does not fit LDS; auto
  *                                  takes up to 4)
@@ -391,6 +393,58 @@ int32_t rpt_knn_graph_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
                            int32_t flags, int32_t* ids_host, double* dist_host,
                            int32_t* count_host);
 int32_t rpt_knn_graph_last_pairs(rpt_ctx* ctx, int64_t* pairs);
+
+/* ---- NN-descent rounds over a kNN graph: "a neighbour of my neighbour is probably my neighbour" ----
+ * Input: the dense data set `data` (f64, f32 or bf16 rows; rows 0 .. n-1) and a graph in
+ * rpt_knn_graph_*'s layout: ids[n][k], dist[n][k], count[n], row i holding count[i] valid entries
+ * sorted by (distance, id), free of i, ids in [0, n), no id twice.  The arrays are input AND
+ * output.  No forest takes part: any graph over the data set will do (rpt_knn_graph_*'s, a
+ * brute-force one, one from elsewhere whose distances are the fold below).
+ * One round maps a graph G to R(G).  For a point i, every set taken from G (never from rows the
+ * round has already rewritten: a round reads the old graph and writes a new one):
+ *   F(i)      the valid ids of row i
+ *   Rev_r(i)  the first r, ordered by (the distance stored with i in row j, j), of {j : i in F(j)};
+ *             r = `reverse`, 0 = none
+ *   B(i)      F(i) u Rev_r(i)
+ *   C(i)      (B(i) u U{F(v) : v in B(i)}) \ {i}, a SET: every id once
+ *   dist      c in F(i): the distance stored in row i.  Any other c: metricDDL2's left fold in
+ *             double exactly as rpt_knn_graph_* defines it (elements widened exactly, every
+ *             difference, square and sum rounded on its own, no FMA, one sqrt), bit-exact for all
+ *             three dtypes
+ *   row i of R(G)   the first k of C(i) by (distance, id), NaN behind every number, NaNs among
+ *             themselves by id; count = min(k, |C(i)|); unused slots hold id -1 and distance +inf
+ * `iters` rounds are applied; a round that changes no row ends the sequence (R is deterministic,
+ * later rounds would be the identity).  F(i) is a subset of C(i), so every slot of a row only ever
+ * moves forward in the (distance, id) order.  The result is a pure function of (data, G, k,
+ * reverse, iters): no sampling, no atomics on the lists, no dependence on the launch shape; two
+ * calls give the same bits.  NN-descent's new / old flags and rho-sampling are deliberately left
+ * out (they trade this determinism for fewer evaluations).
+ * rpt_knn_graph_refine_last (synchronises the stream), statistics of the last call on ctx:
+ *   rounds      rounds applied, up to and including the first one that changed nothing (or iters)
+ *   updates     sum over the applied rounds and i of |F_new(i) \ F_old(i)|
+ *   candidates  sum over the applied rounds and i of |C(i) \ F(i)|: the distances evaluated
+ * A point is owned by one wave (four points per workgroup) while (k + reverse)(k + 1) ids fit its
+ * share of LDS, by a workgroup of its own beyond; the context option graph_refine_general sends
+ * every point there; the answer does not depend on it.
+ * Errors: k outside [1, RPT_GRAPH_MAX_K], reverse outside [0, RPT_GRAPH_MAX_K], iters < 1, flags
+ * other than 0: RPT_E_ARG.  CSR data, any RPT_KNN_METRIC_* bit: RPT_E_UNSUPPORTED.  Scratch (a
+ * second graph, the reverse lists: about 24 k + 20 bytes per point) comes from the context's
+ * pool: RPT_E_NOMEM.  n = 0 and n = 1 are valid.
+ * _host checks the graph BEFORE anything is uploaded (count in [0, k], ids in [0, n), id != i, no
+ * id twice in a row) and returns RPT_E_ARG naming the row; it synchronises.  _dev borrows device
+ * arrays and, like rpt_dataset_csr_dev, does NOT validate them: a count or an id out of range is
+ * skipped, but the result is then unspecified.  _dev enqueues ALL `iters` rounds on the ctx
+ * stream and does not synchronise (rpt_ctx_sync before reading); the kernels of the rounds behind
+ * the first one that changed nothing return at once on a device-side flag.  The caller's arrays
+ * hold the answer for every number of applied rounds.  Timed under rpt_prof_* class 3. */
+int32_t rpt_knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
+                                 int32_t iters, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                                 int32_t* count_dev);
+int32_t rpt_knn_graph_refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
+                                  int32_t iters, int32_t flags, int32_t* ids_host, double* dist_host,
+                                  int32_t* count_host);
+int32_t rpt_knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* updates,
+                                  int64_t* candidates);
 
 /* multi-GPU merge: G per-shard results (shard g holds trees [g*T/G, (g+1)*T/G)), gathered
  * shard-major as ids_dev[G][nq][k] etc. (e.g. by an RCCL all-gather), merged into the

@@ -241,6 +241,7 @@ const OptDesc kOptions[] = {
     {"knn_csr_pre32", &rpt_options::knn_csr_pre32},
     {"knn_general", &rpt_options::knn_general},
     {"graph_general", &rpt_options::graph_general},
+    {"graph_refine_general", &rpt_options::graph_refine_general},
     {"knn_shard_old", &rpt_options::knn_shard_old},
     {"brute_csr_tile", &rpt_options::brute_csr_tile},
     {"comm_force_exchange", &rpt_options::comm_force_exchange},
@@ -361,6 +362,7 @@ int32_t rpt_ctx_destroy(rpt_ctx* ctx) {
     }
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->metric_unc_dev) dev_free(ctx->metric_unc_dev);
+    if (ctx->refine_state_dev) dev_free(ctx->refine_state_dev);
     dev_trim();
     delete ctx;
     return RPT_OK;
@@ -1178,6 +1180,94 @@ int32_t rpt_knn_graph_last_pairs(rpt_ctx* ctx, int64_t* pairs) {
     RPT_ARG(ctx && pairs, "NULL argument");
     *pairs = ctx->last_graph_pairs;
     return RPT_OK;
+  });
+}
+
+// ---- NN-descent rounds over a kNN graph ----------------------------------------------------
+namespace {
+int32_t check_refine(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
+                     int32_t iters, int32_t flags) {
+  RPT_ARG(ctx && data, "NULL argument");
+  RPT_ARG(data->ctx == ctx, "handles belong to another context");
+  if (flags > 0 && (flags & (RPT_KNN_METRIC_REFERENCE | RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)))
+    return fail(RPT_E_UNSUPPORTED, "the kNN graph is refined under metricL2 only (no metric flags)");
+  RPT_ARG(flags == 0, "flags must be 0");
+  if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph refinement takes dense data only (not CSR rows)");
+  RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
+  RPT_ARG(reverse >= 0 && reverse <= RPT_GRAPH_MAX_K, "reverse must be in [0,64] (RPT_GRAPH_MAX_K)");
+  RPT_ARG(iters >= 1, "iters must be at least 1");
+  RPT_ARG(data->n <= 0x7fffffff, "graph too large");
+  return RPT_OK;
+}
+}  // namespace
+
+int32_t rpt_knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
+                                 int32_t iters, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                                 int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_refine(ctx, data, k, reverse, iters, flags));
+    RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
+    RPT_HIP(hipSetDevice(ctx->device));
+    return knn_graph_refine_dev(ctx, data, k, reverse, iters, ids_dev, dist_dev, count_dev);
+  });
+}
+
+int32_t rpt_knn_graph_refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
+                                  int32_t iters, int32_t flags, int32_t* ids_host, double* dist_host,
+                                  int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_refine(ctx, data, k, reverse, iters, flags));
+    const int64_t n = data->n;
+    RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
+    // the graph is checked here, before anything is uploaded: the kernels follow its ids
+    std::vector<int32_t> seen((size_t)n, -1);  // seen[id] = the last row that held id
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t c = count_host[i];
+      if (c < 0 || c > k)
+        return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": count " + std::to_string(c) +
+                                   " outside [0, k]");
+      for (int32_t s = 0; s < c; ++s) {
+        const int32_t id = ids_host[i * k + s];
+        if (id < 0 || id >= n)
+          return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": id " + std::to_string(id) +
+                                     " outside [0, n)");
+        if (id == i) return fail(RPT_E_ARG, "graph row " + std::to_string(i) + " holds its own id");
+        if (seen[id] == (int32_t)i)
+          return fail(RPT_E_ARG, "graph row " + std::to_string(i) + " holds id " + std::to_string(id) + " twice");
+        seen[id] = (int32_t)i;
+      }
+    }
+    RPT_HIP(hipSetDevice(ctx->device));
+    DevBuf<int32_t> ids, cnt;
+    DevBuf<double> dist;
+    RPT_TRY(ids.alloc((size_t)n * k));
+    RPT_TRY(dist.alloc((size_t)n * k));
+    RPT_TRY(cnt.alloc((size_t)n));
+    if (n) {
+      RPT_HIP(hipMemcpy(ids.p, ids_host, (size_t)n * k * 4, hipMemcpyHostToDevice));
+      RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
+      RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    RPT_TRY(knn_graph_refine_dev(ctx, data, k, reverse, iters, ids.p, dist.p, cnt.p));
+    RPT_HIP(stream_sync(ctx->stream));
+    if (n) {
+      RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
+      RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)n * k * 8, hipMemcpyDeviceToHost));
+      RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    return RPT_OK;
+  });
+}
+
+int32_t rpt_knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* updates,
+                                  int64_t* candidates) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ctx && rounds && updates && candidates, "NULL argument");
+    RPT_HIP(hipSetDevice(ctx->device));
+    return knn_graph_refine_last(ctx, rounds, updates, candidates);
   });
 }
 

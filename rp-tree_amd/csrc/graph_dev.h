@@ -1,0 +1,94 @@
+// graph_dev.h — device helpers shared by graph.hip (the graph, leaf by leaf) and graph_refine.hip
+// (its NN-descent rounds): the chunk geometry, the (distance, id) total order, the exact widening
+// of f32 / bf16 elements and the one-wave insertion into a sorted list.  Both translation units
+// are built with -ffp-contract=off.
+#pragma once
+
+#include "common.h"
+
+namespace rpt {
+namespace {
+
+constexpr int kCW = 32;         // columns of a staged chunk
+constexpr int kLS = kCW + 1;    // its row stride in LDS, doubles (odd: no bank conflicts down a column)
+
+// the total order of the answer: numbers by (distance, id), then NaN distances by id
+__device__ inline bool before(double da, int ia, double db, int ib) {
+  const bool an = da != da, bn = db != db;
+  if (an || bn) return an == bn ? ia < ib : bn;
+  return da < db || (da == db && ia < ib);
+}
+
+__device__ inline double pos_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
+
+// elements widen exactly; bf16 rows arrive as their bit patterns
+__device__ inline double widen(double v) { return v; }
+__device__ inline double widen(float v) { return (double)v; }
+__device__ inline double widen(uint16_t v) { return (double)__uint_as_float((uint32_t)v << 16); }
+
+template <class TD>
+__device__ inline void widen16(const uint4& v, double* out);
+template <>
+__device__ inline void widen16<double>(const uint4& v, double* out) {
+  out[0] = __longlong_as_double(((long long)v.y << 32) | v.x);
+  out[1] = __longlong_as_double(((long long)v.w << 32) | v.z);
+}
+template <>
+__device__ inline void widen16<float>(const uint4& v, double* out) {
+  out[0] = (double)__uint_as_float(v.x);
+  out[1] = (double)__uint_as_float(v.y);
+  out[2] = (double)__uint_as_float(v.z);
+  out[3] = (double)__uint_as_float(v.w);
+}
+template <>
+__device__ inline void widen16<uint16_t>(const uint4& v, double* out) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    out[2 * i] = (double)__uint_as_float(w[i] << 16);
+    out[2 * i + 1] = (double)__uint_as_float(w[i] & 0xffff0000u);
+  }
+}
+
+// One wave merges up to two candidates per lane into a sorted list held one entry per lane
+// (lanes [0, c) valid, c <= k <= 64).  Returns whether the list changed.
+__device__ inline bool wave_merge(double& ld, int& lid, int& c, int k, double cd0, int ci0, bool v0,
+                                  double cd1, int ci1, bool v1) {
+  const int lane = threadIdx.x & 63;
+  bool changed = false;
+  for (;;) {
+    if (c == k) {  // a full list: only what comes before its last entry can enter
+      const double td = __shfl(ld, k - 1);
+      const int ti = __shfl(lid, k - 1);
+      v0 = v0 && before(cd0, ci0, td, ti);
+      v1 = v1 && before(cd1, ci1, td, ti);
+    }
+    const unsigned long long m0 = __ballot(v0), m1 = __ballot(v1);
+    if (!(m0 | m1)) break;
+    const bool first = m0 != 0;
+    const int src = __ffsll((long long)(first ? m0 : m1)) - 1;
+    const double nd = __shfl(first ? cd0 : cd1, src);
+    const int ni = __shfl(first ? ci0 : ci1, src);
+    if (lane == src) {
+      if (first) v0 = false;
+      else v1 = false;
+    }
+    if (__ballot(lane < c && lid == ni)) continue;  // the same point, found by an earlier tree
+    const int p = __popcll(__ballot(lane < c && before(ld, lid, nd, ni)));
+    const double ud = __shfl_up(ld, 1);
+    const int ui = __shfl_up(lid, 1);
+    if (lane > p) {
+      ld = ud;
+      lid = ui;
+    } else if (lane == p) {
+      ld = nd;
+      lid = ni;
+    }
+    if (c < k) ++c;
+    changed = true;
+  }
+  return changed;
+}
+
+}  // namespace
+}  // namespace rpt

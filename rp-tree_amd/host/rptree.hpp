@@ -356,6 +356,32 @@ inline GraphResult knnGraph(const RPForest& tts, int k, const GraphResult* accum
   return g;
 }
 
+// NN-descent rounds over a kNN graph (rpt_knn_graph_refine_host) -> the refined graph; `g` is not
+// modified.  One round gives row i the first k, by (distance, id), of its neighbours, up to
+// `reverse` of the points that list i (-1 = k, 0 = none) and all of their neighbours; a round
+// that changes nothing ends the sequence.  Deterministic.  stats (optional): rounds applied, ids
+// that entered a row, distances evaluated (rpt_knn_graph_refine_last).
+struct RefineStats {
+  int64_t rounds = 0, updates = 0, candidates = 0;
+};
+inline GraphResult knnGraphRefine(Context& ctx, const Dataset& data, const GraphResult& g, int iters = 1,
+                                  int reverse = -1, RefineStats* stats = nullptr) {
+  const size_t n = (size_t)data.n;
+  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0) || g.dist.size() != g.ids.size())
+    throw RPTError(RPT_E_ARG, "knnGraphRefine: a graph of another data set or k");
+  GraphResult out = g;
+  out.ids.resize(out.ids.size() + 1);  // + 1: non-NULL pointers for an empty data set
+  out.dist.resize(out.dist.size() + 1);
+  out.count.resize(n + 1);
+  check(rpt_knn_graph_refine_host(ctx.get(), data.get(), g.k, reverse < 0 ? g.k : reverse, iters, 0,
+                                  out.ids.data(), out.dist.data(), out.count.data()));
+  out.ids.resize(n * (size_t)g.k);
+  out.dist.resize(n * (size_t)g.k);
+  out.count.resize(n);
+  if (stats) check(rpt_knn_graph_refine_last(ctx.get(), &stats->rounds, &stats->updates, &stats->candidates));
+  return out;
+}
+
 struct BruteResult {
   std::vector<int32_t> ids;  // [nq][k], -1 = unused slot
   std::vector<double> dist;  // [nq][k]

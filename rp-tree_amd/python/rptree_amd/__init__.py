@@ -36,6 +36,7 @@ __all__ = [
     "knnH", "knnHBatch", "knnPQ", "candidatesBatch", "to_bf16", "from_bf16", "RPStreamForest",
     "metricCosine", "metricInner", "recallWithBatch", "recallHits",
     "knnGraph", "knnGraphDev", "knnGraphLastPairs",
+    "knnGraphRefine", "knnGraphRefineDev", "knnGraphRefineLast",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -814,6 +815,53 @@ def knnGraphLastPairs(ctx=None):
     v = C.c_int64()
     check(lib().rpt_knn_graph_last_pairs(ctx._h, C.byref(v)))
     return int(v.value)
+
+
+def _refine_data(data):
+    return data if isinstance(data, Dataset) else data.data
+
+
+def knnGraphRefine(graph, data, iters=1, reverse=None, ctx=None):
+    """NN-descent rounds over a kNN graph (rpt_knn_graph_refine_host) -> new (ids, dist, count); the
+    input tuple is not modified.  graph: (ids[n][k], dist[n][k], count[n]) over `data`, e.g.
+    knnGraph's; data: a dense Dataset, or a forest (its .data is used; no forest takes part).
+    One round gives row i the first k, by (distance, id), of its neighbours, up to `reverse` of
+    the points that list i (None = k, 0 = none; the nearest by (distance, id)) and all of THEIR
+    neighbours; distances not already in row i are metricDDL2's left fold in double, bit-exact for
+    every dtype.  A round that changes nothing ends the sequence.  Deterministic: the same input
+    gives the same bits.  k and reverse <= 64."""
+    ds = _refine_data(data)
+    ctx = ctx or ds.ctx
+    ids = np.array(graph[0], dtype=np.int32, order="C")
+    dist = np.array(graph[1], dtype=np.float64, order="C")
+    cnt = np.array(graph[2], dtype=np.int32, order="C")
+    if ids.ndim != 2 or ids.shape[0] != ds.n or dist.shape != ids.shape or cnt.shape != (ds.n,):
+        raise ValueError("graph must be (ids[n][k], dist[n][k], count[n]) over the data set's n rows")
+    k = ids.shape[1]
+    check(lib().rpt_knn_graph_refine_host(ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
+                                          int(iters), 0, _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnGraphRefineDev(k, data, ids_ptr, dist_ptr, count_ptr, iters=1, reverse=None):
+    """knnGraphRefine on device arrays in place (rpt_knn_graph_refine_dev): int32 [n][k], float64
+    [n][k], int32 [n] given as device addresses.  The arrays are NOT validated.  All `iters` rounds
+    are enqueued on the ctx stream, not synchronised (ctx.sync() before reading); whatever filled
+    the arrays must have finished (see Dataset.dense_device)."""
+    ds = _refine_data(data)
+    check(lib().rpt_knn_graph_refine_dev(ds.ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
+                                         int(iters), 0, C.c_void_p(ids_ptr), C.c_void_p(dist_ptr),
+                                         C.c_void_p(count_ptr)))
+
+
+def knnGraphRefineLast(ctx=None):
+    """(rounds, updates, candidates) of the last knnGraphRefine call on ctx
+    (rpt_knn_graph_refine_last; synchronises): rounds applied up to and including the first that
+    changed nothing, ids that entered a row, distances evaluated."""
+    ctx = ctx or default_context()
+    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().rpt_knn_graph_refine_last(ctx._h, C.byref(a), C.byref(b), C.byref(c)))
+    return int(a.value), int(b.value), int(c.value)
 
 
 def knn_last_uncertified(ctx=None):
