@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -51,6 +51,8 @@ foreign import ccall safe "rpt_dataset_csr_host"    c_dataset_csr    :: Ptr Ctx 
 foreign import ccall safe "rpt_recall_hits_host"    c_recall_hits    :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_host"      c_knn_graph_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_refine_host" c_knn_graph_refine_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_graph_metric_host" c_knn_graph_metric_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_graph_refine_metric_host" c_knn_graph_refine_metric_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
 -- multi-GPU (csrc/comm.hip on librccl): one process drives n devices; per-device arguments are
 -- arrays with one entry per device (Foreign.Marshal.Array.withArray)
@@ -260,6 +262,33 @@ knnGraphRefineHIP ctx ds _n k reverse iters (i0, d0, c0) = do
   dist <- VS.thaw d0
   cnt <- VS.thaw c0
   VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_refine_host ctx ds (fromIntegral k) (fromIntegral reverse) (fromIntegral iters) 0 a b))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | 'knnGraphHIP' under another distance (rpt_knn_graph_metric_host): 'MetricCosine' / 'MetricInner'
+-- are the distances of 'knnMetricHIP' (the left-fold dot in Double for every dtype, bit-exact; a zero
+-- row is NaN under the cosine distance and ranks last); 'MetricL2' gives 'knnGraphHIP''s bits.
+-- @Just earlier@ must be an answer under the same metric (another is not detected: stored distances
+-- are taken as stored).
+knnGraphMetricHIP :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Metric -> Int -> Int
+                  -> Maybe (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+                  -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnGraphMetricHIP ctx f ds m n k earlier = do
+  (ids, dist, cnt, flags) <- case earlier of
+    Nothing -> (,,,) <$> VSM.new (n * k) <*> VSM.new (n * k) <*> VSM.new n <*> pure 0
+    Just (i0, d0, c0) -> (,,,) <$> VS.thaw i0 <*> VS.thaw d0 <*> VS.thaw c0 <*> pure 1
+  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_metric_host ctx f ds (fromIntegral k) (metricFlag m) flags a b))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | 'knnGraphRefineHIP' under another distance (rpt_knn_graph_refine_metric_host); the graph's stored
+-- distances must be that metric's ('knnGraphMetricHIP' under the same 'Metric').
+knnGraphRefineMetricHIP :: Ptr Ctx -> Ptr Dataset -> Metric -> Int -> Int -> Int -> Int
+                        -> (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+                        -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnGraphRefineMetricHIP ctx ds m _n k reverse iters (i0, d0, c0) = do
+  ids <- VS.thaw i0
+  dist <- VS.thaw d0
+  cnt <- VS.thaw c0
+  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_refine_metric_host ctx ds (fromIntegral k) (fromIntegral reverse) (fromIntegral iters) (metricFlag m) 0 a b))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | SVector rows as a CSR dataset on the device (rpt_dataset_csr_host), for the extent of the

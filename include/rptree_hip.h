@@ -446,6 +446,54 @@ int32_t rpt_knn_graph_refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t
 int32_t rpt_knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* updates,
                                   int64_t* candidates);
 
+/* ---- the kNN graph and its refinement under the cosine and inner-product distances ----
+ * rpt_knn_graph_metric_* and rpt_knn_graph_refine_metric_* are rpt_knn_graph_* and
+ * rpt_knn_graph_refine_* with one more argument, `metric`: 0, RPT_KNN_METRIC_COSINE or
+ * RPT_KNN_METRIC_INNER.  `flags` keeps its meaning (RPT_GRAPH_ACCUMULATE or 0 for the graph, 0 for
+ * the refinement).  Everything stated above carries over word for word: mates(i), the sets F /
+ * Rev_r / B / C, the order (distance, id) with NaN behind every number and NaNs among themselves by
+ * id, counts, unused slots (id -1, distance +inf), one owner per list, no atomics on the lists, a
+ * deterministic result, _dev enqueues and does not synchronise / _host synchronises, the context
+ * options graph_general and graph_refine_general, rpt_prof_* class 3, rpt_knn_graph_last_pairs,
+ * rpt_knn_graph_refine_last, and the validation of the graph by the _host refinement.  The one
+ * thing that changes is dist(i, j).  With dot(a, b) the left fold ((0 + a0 b0) + a1 b1) + ... in
+ * double from +0.0, f32 / bf16 elements widened exactly, every product and sum rounded on its own,
+ * no FMA (the dot of the RPT_KNN_METRIC_* definition above, with q = x_i):
+ *   metric == 0            sqrt of the fold of squared differences, as rpt_knn_graph_* defines it;
+ *                          the same bits as the entry points without `metric`
+ *   RPT_KNN_METRIC_INNER   dist(i, j) = -dot(x_i, x_j)
+ *   RPT_KNN_METRIC_COSINE  dist(i, j) = 1 - dot(x_i, x_j) / (sqrt(dot(x_i, x_i)) * sqrt(dot(x_j, x_j)))
+ *                          with correctly rounded sqrt, product and division; a zero row gives NaN
+ *                          against everything (and so ranks last, by id, in every list)
+ * No ranking shadow, certificate or fallback here either: every distance is that fold.
+ *   Symmetry     both distances are symmetric bit for bit, dist(i, j) == dist(j, i): IEEE
+ *                multiplication commutes and the fold visits the same products in the same order,
+ *                so a pair is still evaluated once.
+ *   Signed zero  -dot can be -0.0.  The order compares numbers, so -0.0 ties with +0.0 and the id
+ *                decides; the stored bits are the computed ones.
+ *   Inner product  it is not a metric and a point may be "nearer" to others than to itself.
+ *                Nothing in the definition cares: i is excluded by id, as above.
+ *   Mixing metrics  accumulating into, or refining, arrays that were built under another metric is
+ *                the caller's error and is NOT detected: stored distances are taken as stored.
+ * Errors: any other `metric` value, both metric bits together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG
+ * (a metric bit in `flags` too: flags must be 0 / RPT_GRAPH_ACCUMULATE).  CSR data and streamed
+ * forests: RPT_E_UNSUPPORTED.  Everything else as the entry points without `metric`.
+ * Memory note: the cosine distance reads the rows' dot(x, x) cached on the dataset by the first
+ * cosine or inner-product call of any kind, 8 bytes per row, freed with the dataset (a dataset
+ * borrowed with rpt_dataset_dense_dev must not change while the library holds it). */
+int32_t rpt_knn_graph_metric_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                                 int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                                 int32_t* count_dev);
+int32_t rpt_knn_graph_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                                  int32_t metric, int32_t flags, int32_t* ids_host,
+                                  double* dist_host, int32_t* count_host);
+int32_t rpt_knn_graph_refine_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                        int32_t reverse, int32_t iters, int32_t metric, int32_t flags,
+                                        int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+int32_t rpt_knn_graph_refine_metric_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                         int32_t reverse, int32_t iters, int32_t metric, int32_t flags,
+                                         int32_t* ids_host, double* dist_host, int32_t* count_host);
+
 /* multi-GPU merge: G per-shard results (shard g holds trees [g*T/G, (g+1)*T/G)), gathered
  * shard-major as ids_dev[G][nq][k] etc. (e.g. by an RCCL all-gather), merged into the
  * global top-k with the reference's stable order (shard ascending = tree ascending).

@@ -1123,25 +1123,74 @@ int32_t rpt_knn_last_tier(rpt_ctx* ctx, int32_t* tier) {
 }
 
 // ---- kNN graph of the indexed points ------------------------------------------------------
+namespace {
+// metric of the rpt_knn_graph_metric_* / rpt_knn_graph_refine_metric_* entry points
+int32_t check_graph_metric(int32_t metric) {
+  RPT_ARG(metric != (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER),
+          "metric: RPT_KNN_METRIC_COSINE and RPT_KNN_METRIC_INNER are exclusive");
+  RPT_ARG(metric == 0 || metric == RPT_KNN_METRIC_COSINE || metric == RPT_KNN_METRIC_INNER,
+          "metric must be 0, RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER");
+  return RPT_OK;
+}
+
+// rpt_knn_graph_dev (has_metric false: the metric bits in flags are refused) and
+// rpt_knn_graph_metric_dev
+int32_t graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k, bool has_metric,
+                  int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                  int32_t* count_dev) {
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_ARG(ctx && f && data, "NULL argument");
+  RPT_ARG(f->ctx == ctx && data->ctx == ctx, "handles belong to another context");
+  if (has_metric)
+    RPT_TRY(check_graph_metric(metric));
+  else if (flags > 0 && (flags & (RPT_KNN_METRIC_REFERENCE | RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)))
+    return fail(RPT_E_UNSUPPORTED, "the kNN graph is built under metricL2 only (no metric flags)");
+  RPT_ARG((flags & ~RPT_GRAPH_ACCUMULATE) == 0, "flags must be 0 or RPT_GRAPH_ACCUMULATE");
+  if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph takes dense data only (not CSR rows)");
+  if (f->xtopo)
+    return fail(RPT_E_UNSUPPORTED, "the kNN graph takes batch forests only (not a streamed forest)");
+  RPT_ARG(data->n == f->n && data->d == f->d && data->dtype == f->dtype,
+          "data is not the forest's data set (n, d, dtype)");
+  RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
+  RPT_ARG(f->n <= 0x7fffffff, "graph too large");
+  RPT_ARG(f->n == 0 || (ids_dev && dist_dev && count_dev), "NULL output");
+  RPT_HIP(hipSetDevice(ctx->device));
+  return knn_graph_dev(ctx, f, data, k, metric, flags, ids_dev, dist_dev, count_dev);
+}
+
+int32_t graph_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k, bool has_metric,
+                   int32_t metric, int32_t flags, int32_t* ids_host, double* dist_host,
+                   int32_t* count_host) {
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_ARG(ctx && f && data, "NULL argument");
+  RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
+  const int64_t n = f->n;
+  RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL output");
+  DevBuf<int32_t> ids, cnt;
+  DevBuf<double> dist;
+  RPT_TRY(ids.alloc((size_t)n * k));
+  RPT_TRY(dist.alloc((size_t)n * k));
+  RPT_TRY(cnt.alloc((size_t)n));
+  if (n && flags == RPT_GRAPH_ACCUMULATE) {  // the arrays are an input too
+    RPT_HIP(hipMemcpy(ids.p, ids_host, (size_t)n * k * 4, hipMemcpyHostToDevice));
+    RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
+    RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  RPT_TRY(graph_dev(ctx, f, data, k, has_metric, metric, flags, ids.p, dist.p, cnt.p));
+  RPT_HIP(stream_sync(ctx->stream));
+  if (n) {
+    RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)n * k * 8, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  }
+  return RPT_OK;
+}
+}  // namespace
+
 int32_t rpt_knn_graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
                           int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
   return guarded([&]() -> int32_t {
-    if (ctx) dev_set_stream(ctx->stream);
-    RPT_ARG(ctx && f && data, "NULL argument");
-    RPT_ARG(f->ctx == ctx && data->ctx == ctx, "handles belong to another context");
-    if (flags > 0 && (flags & (RPT_KNN_METRIC_REFERENCE | RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)))
-      return fail(RPT_E_UNSUPPORTED, "the kNN graph is built under metricL2 only (no metric flags)");
-    RPT_ARG((flags & ~RPT_GRAPH_ACCUMULATE) == 0, "flags must be 0 or RPT_GRAPH_ACCUMULATE");
-    if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph takes dense data only (not CSR rows)");
-    if (f->xtopo)
-      return fail(RPT_E_UNSUPPORTED, "the kNN graph takes batch forests only (not a streamed forest)");
-    RPT_ARG(data->n == f->n && data->d == f->d && data->dtype == f->dtype,
-            "data is not the forest's data set (n, d, dtype)");
-    RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
-    RPT_ARG(f->n <= 0x7fffffff, "graph too large");
-    RPT_ARG(f->n == 0 || (ids_dev && dist_dev && count_dev), "NULL output");
-    RPT_HIP(hipSetDevice(ctx->device));
-    return knn_graph_dev(ctx, f, data, k, flags, ids_dev, dist_dev, count_dev);
+    return graph_dev(ctx, f, data, k, false, 0, flags, ids_dev, dist_dev, count_dev);
   });
 }
 
@@ -1149,29 +1198,23 @@ int32_t rpt_knn_graph_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
                            int32_t flags, int32_t* ids_host, double* dist_host,
                            int32_t* count_host) {
   return guarded([&]() -> int32_t {
-    if (ctx) dev_set_stream(ctx->stream);
-    RPT_ARG(ctx && f && data, "NULL argument");
-    RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
-    const int64_t n = f->n;
-    RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL output");
-    DevBuf<int32_t> ids, cnt;
-    DevBuf<double> dist;
-    RPT_TRY(ids.alloc((size_t)n * k));
-    RPT_TRY(dist.alloc((size_t)n * k));
-    RPT_TRY(cnt.alloc((size_t)n));
-    if (n && flags == RPT_GRAPH_ACCUMULATE) {  // the arrays are an input too
-      RPT_HIP(hipMemcpy(ids.p, ids_host, (size_t)n * k * 4, hipMemcpyHostToDevice));
-      RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
-      RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    RPT_TRY(rpt_knn_graph_dev(ctx, f, data, k, flags, ids.p, dist.p, cnt.p));
-    RPT_HIP(stream_sync(ctx->stream));
-    if (n) {
-      RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
-      RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)n * k * 8, hipMemcpyDeviceToHost));
-      RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    }
-    return RPT_OK;
+    return graph_host(ctx, f, data, k, false, 0, flags, ids_host, dist_host, count_host);
+  });
+}
+
+int32_t rpt_knn_graph_metric_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                                 int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                                 int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    return graph_dev(ctx, f, data, k, true, metric, flags, ids_dev, dist_dev, count_dev);
+  });
+}
+
+int32_t rpt_knn_graph_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                                  int32_t metric, int32_t flags, int32_t* ids_host,
+                                  double* dist_host, int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return graph_host(ctx, f, data, k, true, metric, flags, ids_host, dist_host, count_host);
   });
 }
 
@@ -1185,11 +1228,14 @@ int32_t rpt_knn_graph_last_pairs(rpt_ctx* ctx, int64_t* pairs) {
 
 // ---- NN-descent rounds over a kNN graph ----------------------------------------------------
 namespace {
+// has_metric false (rpt_knn_graph_refine_*): the metric bits in flags are refused
 int32_t check_refine(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
-                     int32_t iters, int32_t flags) {
+                     int32_t iters, bool has_metric, int32_t metric, int32_t flags) {
   RPT_ARG(ctx && data, "NULL argument");
   RPT_ARG(data->ctx == ctx, "handles belong to another context");
-  if (flags > 0 && (flags & (RPT_KNN_METRIC_REFERENCE | RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)))
+  if (has_metric)
+    RPT_TRY(check_graph_metric(metric));
+  else if (flags > 0 && (flags & (RPT_KNN_METRIC_REFERENCE | RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)))
     return fail(RPT_E_UNSUPPORTED, "the kNN graph is refined under metricL2 only (no metric flags)");
   RPT_ARG(flags == 0, "flags must be 0");
   if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph refinement takes dense data only (not CSR rows)");
@@ -1201,24 +1247,25 @@ int32_t check_refine(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t r
 }
 }  // namespace
 
-int32_t rpt_knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
-                                 int32_t iters, int32_t flags, int32_t* ids_dev, double* dist_dev,
-                                 int32_t* count_dev) {
-  return guarded([&]() -> int32_t {
+namespace {
+int32_t refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse, int32_t iters,
+                   bool has_metric, int32_t metric, int32_t flags, int32_t* ids_dev,
+                   double* dist_dev, int32_t* count_dev) {
+  {
     if (ctx) dev_set_stream(ctx->stream);
-    RPT_TRY(check_refine(ctx, data, k, reverse, iters, flags));
+    RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags));
     RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
     RPT_HIP(hipSetDevice(ctx->device));
-    return knn_graph_refine_dev(ctx, data, k, reverse, iters, ids_dev, dist_dev, count_dev);
-  });
+    return knn_graph_refine_dev(ctx, data, k, reverse, iters, metric, ids_dev, dist_dev, count_dev);
+  }
 }
 
-int32_t rpt_knn_graph_refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
-                                  int32_t iters, int32_t flags, int32_t* ids_host, double* dist_host,
-                                  int32_t* count_host) {
-  return guarded([&]() -> int32_t {
+int32_t refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse, int32_t iters,
+                    bool has_metric, int32_t metric, int32_t flags, int32_t* ids_host,
+                    double* dist_host, int32_t* count_host) {
+  {
     if (ctx) dev_set_stream(ctx->stream);
-    RPT_TRY(check_refine(ctx, data, k, reverse, iters, flags));
+    RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags));
     const int64_t n = data->n;
     RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
     // the graph is checked here, before anything is uploaded: the kernels follow its ids
@@ -1250,7 +1297,7 @@ int32_t rpt_knn_graph_refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t
       RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
       RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
     }
-    RPT_TRY(knn_graph_refine_dev(ctx, data, k, reverse, iters, ids.p, dist.p, cnt.p));
+    RPT_TRY(knn_graph_refine_dev(ctx, data, k, reverse, iters, metric, ids.p, dist.p, cnt.p));
     RPT_HIP(stream_sync(ctx->stream));
     if (n) {
       RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
@@ -1258,6 +1305,40 @@ int32_t rpt_knn_graph_refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t
       RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     }
     return RPT_OK;
+  }
+}
+
+}  // namespace
+
+int32_t rpt_knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
+                                 int32_t iters, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                                 int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    return refine_dev(ctx, data, k, reverse, iters, false, 0, flags, ids_dev, dist_dev, count_dev);
+  });
+}
+
+int32_t rpt_knn_graph_refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
+                                  int32_t iters, int32_t flags, int32_t* ids_host, double* dist_host,
+                                  int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return refine_host(ctx, data, k, reverse, iters, false, 0, flags, ids_host, dist_host, count_host);
+  });
+}
+
+int32_t rpt_knn_graph_refine_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                        int32_t reverse, int32_t iters, int32_t metric, int32_t flags,
+                                        int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    return refine_dev(ctx, data, k, reverse, iters, true, metric, flags, ids_dev, dist_dev, count_dev);
+  });
+}
+
+int32_t rpt_knn_graph_refine_metric_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                         int32_t reverse, int32_t iters, int32_t metric, int32_t flags,
+                                         int32_t* ids_host, double* dist_host, int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return refine_host(ctx, data, k, reverse, iters, true, metric, flags, ids_host, dist_host, count_host);
   });
 }
 

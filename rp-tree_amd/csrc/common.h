@@ -385,16 +385,22 @@ int32_t brute_knn_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* 
                       int32_t flags, int32_t* ids_dev, double* dist_dev);
 int32_t recall_hits(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
                     int32_t k, int32_t flags, int32_t* hits_host, int32_t* truth_ids_host);
+// the rows' dot(x, x) as the left fold into data->sqnorm ([n] doubles, then the certified cut's two
+// statistics), once per dataset, enqueued on the ctx stream (knn.hip)
+int32_t ensure_sqnorm(rpt_ctx* ctx, const rpt_dataset* data);
 // ---- kNN graph of the indexed points (graph.hip) -----------------------------------------
 // arguments checked by the caller (dense data of the forest's shape, batch topology, k <= 64);
-// flags: 0 or RPT_GRAPH_ACCUMULATE; enqueued on the ctx stream
+// metric: 0 (L2), RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER; flags: 0 or RPT_GRAPH_ACCUMULATE;
+// enqueued on the ctx stream
 int32_t knn_graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
-                      int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+                      int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                      int32_t* count_dev);
 // ---- NN-descent rounds over a kNN graph (graph_refine.hip) -----------------------------------
-// arguments checked by the caller (dense data, k and reverse <= 64, iters >= 1); the arrays are
-// input and output; enqueued on the ctx stream
+// arguments checked by the caller (dense data, k and reverse <= 64, iters >= 1; metric as
+// knn_graph_dev's); the arrays are input and output; enqueued on the ctx stream
 int32_t knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
-                             int32_t iters, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+                             int32_t iters, int32_t metric, int32_t* ids_dev, double* dist_dev,
+                             int32_t* count_dev);
 // synchronises the stream
 int32_t knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* updates, int64_t* candidates);
 int32_t knn_h(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,

@@ -75,7 +75,9 @@ __device__ inline void stage_chunk(const TD* __restrict__ X, int d, const int* s
 }
 
 // 4 x 4 pairs over cw columns: rows ra + u * sa of bufA against rows rb + v * sb of bufB.  The
-// reference's fold: every difference, square and sum rounded on its own.
+// reference's fold: every difference, square and sum (L2) / every product and sum (the dot of the
+// cosine and inner-product distances) rounded on its own.
+template <int M>
 __device__ inline void tile_fold(const double* bufA, int ra, int sa, const double* bufB, int rb,
                                  int sb, int cw, double (&acc)[16]) {
   const double* pa = bufA + ra * kLS;
@@ -90,11 +92,7 @@ __device__ inline void tile_fold(const double* bufA, int ra, int sa, const doubl
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const double t = a[u] - b[v];
-        const double sq = t * t;
-        acc[u * 4 + v] = acc[u * 4 + v] + sq;
-      }
+      for (int v = 0; v < 4; ++v) acc[u * 4 + v] = fold_step<M>(acc[u * 4 + v], a[u], b[v]);
   }
 }
 
@@ -109,13 +107,15 @@ __global__ void graph_init_kernel(int64_t n, int k, int32_t* __restrict__ ids,
 }
 
 // ---- leaves of up to 128 points: one workgroup per leaf, every pair once ----------------------
-// dynamic LDS: max(4 ng (4 ng + 1), 4 ng * kLS) doubles (the chunk, later the distance matrix),
-// then 4 ng ints (the leaf's ids); ng = ceil(largest leaf / 4)
-template <class TD>
+// dynamic LDS: lds_doubles doubles, then 4 ng ints (the leaf's ids); ng = ceil(largest leaf / 4).
+// lds_doubles = max(4 ng (4 ng + 1), 4 ng * kLS) (the chunk, later the distance matrix), for the
+// cosine distance 4 ng more: the rows' norms rn[id] at the END of the doubles (behind the matrix of
+// the largest leaf, so of every leaf).
+template <class TD, int M>
 __global__ __launch_bounds__(kThreads) void graph_leaf_kernel(
     const TD* __restrict__ X, int d, const int32_t* __restrict__ perm_t,
     const GBlock* __restrict__ blocks, int k, int lds_doubles, int vec, int32_t* __restrict__ ids,
-    double* __restrict__ dist, int32_t* __restrict__ count) {
+    double* __restrict__ dist, int32_t* __restrict__ count, const double* __restrict__ rn) {
   extern __shared__ double smem[];
   double* buf = smem;
   int* sid = reinterpret_cast<int*>(smem + lds_doubles);
@@ -125,7 +125,12 @@ __global__ __launch_bounds__(kThreads) void graph_leaf_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ng = (s + 3) >> 2;  // row groups: group g holds the rows g, g + ng, g + 2 ng, g + 3 ng
   const int P = 4 * ng;
-  for (int r = tid; r < P; r += kThreads) sid[r] = r < s ? perm_t[blk.off + r] : -1;
+  [[maybe_unused]] double* snorm = smem + lds_doubles - P;
+  for (int r = tid; r < P; r += kThreads) {
+    const int id = r < s ? perm_t[blk.off + r] : -1;
+    sid[r] = id;
+    if constexpr (M == kGraphCosine) snorm[r] = id >= 0 ? rn[id] : 0.0;
+  }
 
   // tiles (gi <= gj) of the upper triangle, row-major; up to three per lane
   const int ntiles = ng * (ng + 1) / 2;
@@ -157,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void graph_leaf_kernel(
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < 3; ++u)
-      if (gi[u] >= 0) tile_fold(buf, gi[u], ng, buf, gj[u], ng, cw, acc[u]);
+      if (gi[u] >= 0) tile_fold<M>(buf, gi[u], ng, buf, gj[u], ng, cw, acc[u]);
   }
   __syncthreads();
 
@@ -172,7 +177,9 @@ __global__ __launch_bounds__(kThreads) void graph_leaf_kernel(
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
           const int ri = gi[u] + ng * a, rj = gj[u] + ng * b;
-          const double v = sqrt(acc[u][a * 4 + b]);
+          double v;
+          if constexpr (M == kGraphCosine) v = fold_finish<M>(acc[u][a * 4 + b], snorm[ri], snorm[rj]);
+          else v = fold_finish<M>(acc[u][a * 4 + b], 0.0, 0.0);
           D[ri * SD + rj] = v;
           D[rj * SD + ri] = v;
         }
@@ -224,17 +231,21 @@ __global__ __launch_bounds__(kThreads) void graph_leaf_kernel(
 
 // ---- any leaf: 64 rows of a leaf per workgroup against the leaf in blocks of 64 ---------------
 // dynamic LDS: 2 * 64 * kLS doubles (two chunks, later the 64 x 65 distance block), 64 k doubles
-// (the rows' lists), then ints: 64 k list ids, 64 counts, 64 changed flags, 64 + 64 row ids
-template <class TD>
+// (the rows' lists), for the cosine distance 64 + 64 doubles (the norms of the rows and of the
+// block's points), then ints: 64 k list ids, 64 counts, 64 changed flags, 64 + 64 row ids
+template <class TD, int M>
 __global__ __launch_bounds__(kThreads) void graph_tiled_kernel(
     const TD* __restrict__ X, int d, const int32_t* __restrict__ perm_t,
     const GBlock* __restrict__ blocks, int k, int vec, int32_t* __restrict__ ids,
-    double* __restrict__ dist, int32_t* __restrict__ count) {
+    double* __restrict__ dist, int32_t* __restrict__ count, const double* __restrict__ rn) {
   extern __shared__ double smem[];
+  constexpr int kNorms = M == kGraphCosine ? 2 * kTB : 0;
   double* bufA = smem;
   double* bufB = smem + kTB * kLS;
   double* lst_d = smem + 2 * kTB * kLS;
-  int* lst_i = reinterpret_cast<int*>(lst_d + kTB * k);
+  [[maybe_unused]] double* nrmA = lst_d + kTB * k;
+  [[maybe_unused]] double* nrmB = nrmA + kTB;
+  int* lst_i = reinterpret_cast<int*>(lst_d + kTB * k + kNorms);
   int* lst_c = lst_i + kTB * k;
   int* lst_ch = lst_c + kTB;
   int* sidA = lst_ch + kTB;
@@ -247,6 +258,7 @@ __global__ __launch_bounds__(kThreads) void graph_tiled_kernel(
   if (tid < kTB) {
     const int g = tid < nr ? perm_t[blk.off + blk.row0 + tid] : -1;
     sidA[tid] = g;
+    if constexpr (M == kGraphCosine) nrmA[tid] = g >= 0 ? rn[g] : 0.0;
     int c = g >= 0 ? count[g] : 0;
     lst_c[tid] = c < 0 ? 0 : (c > k ? k : c);
     lst_ch[tid] = 0;
@@ -266,7 +278,11 @@ __global__ __launch_bounds__(kThreads) void graph_tiled_kernel(
   for (int cb = 0; cb < s; cb += kTB) {
     const int nc = s - cb < kTB ? s - cb : kTB;
     __syncthreads();  // the last block's selection is over
-    if (tid < kTB) sidB[tid] = tid < nc ? perm_t[blk.off + cb + tid] : -1;
+    if (tid < kTB) {
+      const int g = tid < nc ? perm_t[blk.off + cb + tid] : -1;
+      sidB[tid] = g;
+      if constexpr (M == kGraphCosine) nrmB[tid] = g >= 0 ? rn[g] : 0.0;
+    }
     double acc[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.0;
@@ -276,14 +292,19 @@ __global__ __launch_bounds__(kThreads) void graph_tiled_kernel(
       stage_chunk<TD>(X, d, sidA, kTB, c0, cw, bufA, vec != 0);
       stage_chunk<TD>(X, d, sidB, kTB, c0, cw, bufB, vec != 0);
       __syncthreads();
-      tile_fold(bufA, gi, 16, bufB, gj, 16, cw, acc);
+      tile_fold<M>(bufA, gi, 16, bufB, gj, 16, cw, acc);
     }
     __syncthreads();
     double* D = smem;
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) D[(gi + 16 * a) * SD + gj + 16 * b] = sqrt(acc[a * 4 + b]);
+      for (int b = 0; b < 4; ++b) {
+        double v;
+        if constexpr (M == kGraphCosine) v = fold_finish<M>(acc[a * 4 + b], nrmA[gi + 16 * a], nrmB[gj + 16 * b]);
+        else v = fold_finish<M>(acc[a * 4 + b], 0.0, 0.0);
+        D[(gi + 16 * a) * SD + gj + 16 * b] = v;
+      }
     __syncthreads();
     for (int r = wave; r < nr; r += 4) {
       const int me = sidA[r];
@@ -316,11 +337,12 @@ __global__ __launch_bounds__(kThreads) void graph_tiled_kernel(
   }
 }
 
-template <class TD>
+template <class TD, int M>
 int32_t launch_graph(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k, bool general,
                      int smax, const GBlock* blocks_dev, int64_t nblocks, int32_t* ids, double* dist,
                      int32_t* count) {
   const TD* X = static_cast<const TD*>(data->X);
+  const double* rn = M == kGraphCosine ? data->sqnorm : nullptr;
   const int d = data->d;
   // 16-byte pieces need a 16-byte base and pitch
   const int vec = ((reinterpret_cast<uintptr_t>(X) & 15) == 0 && ((size_t)d * sizeof(TD)) % 16 == 0) ? 1 : 0;
@@ -328,39 +350,54 @@ int32_t launch_graph(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32
   static DeviceOnce attr_once[2];
   if (!general) {
     const int ng = (smax + 3) / 4, P = 4 * ng;
-    const int lds_doubles = std::max(P * (P + 1), P * kLS);
+    const int lds_doubles = std::max(P * (P + 1), P * kLS) + (M == kGraphCosine ? P : 0);
     const size_t smem = (size_t)lds_doubles * 8 + (size_t)P * 4;
     RPT_TRY(attr_once[0].run(ctx->device, [&]() -> int32_t {
-      RPT_HIP(hipFuncSetAttribute((const void*)graph_leaf_kernel<TD>,
+      RPT_HIP(hipFuncSetAttribute((const void*)graph_leaf_kernel<TD, M>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
       return RPT_OK;
     }));
     for (int32_t t = 0; t < f->T; ++t)
-      hipLaunchKernelGGL(graph_leaf_kernel<TD>, dim3((unsigned)nblocks), dim3(kThreads), smem,
+      hipLaunchKernelGGL((graph_leaf_kernel<TD, M>), dim3((unsigned)nblocks), dim3(kThreads), smem,
                          ctx->stream, X, d, f->perm.p + (int64_t)t * f->n, blocks_dev, k,
-                         lds_doubles, vec, ids, dist, count);
+                         lds_doubles, vec, ids, dist, count, rn);
   } else {
-    const size_t smem = (size_t)(2 * kTB * kLS + kTB * k) * 8 + (size_t)(kTB * k + 4 * kTB) * 4;
+    const size_t smem = (size_t)(2 * kTB * kLS + kTB * k + (M == kGraphCosine ? 2 * kTB : 0)) * 8 +
+                        (size_t)(kTB * k + 4 * kTB) * 4;
     RPT_TRY(attr_once[1].run(ctx->device, [&]() -> int32_t {
-      RPT_HIP(hipFuncSetAttribute((const void*)graph_tiled_kernel<TD>,
+      RPT_HIP(hipFuncSetAttribute((const void*)graph_tiled_kernel<TD, M>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
       return RPT_OK;
     }));
     for (int32_t t = 0; t < f->T; ++t)
-      hipLaunchKernelGGL(graph_tiled_kernel<TD>, dim3((unsigned)nblocks), dim3(kThreads), smem,
+      hipLaunchKernelGGL((graph_tiled_kernel<TD, M>), dim3((unsigned)nblocks), dim3(kThreads), smem,
                          ctx->stream, X, d, f->perm.p + (int64_t)t * f->n, blocks_dev, k, vec, ids,
-                         dist, count);
+                         dist, count, rn);
   }
   RPT_HIP(hipGetLastError());
   return RPT_OK;
 }
 
+template <class TD>
+int32_t launch_graph_metric(int m, rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                            bool general, int smax, const GBlock* blocks_dev, int64_t nblocks,
+                            int32_t* ids, double* dist, int32_t* count) {
+  if (m == kGraphCosine)
+    return launch_graph<TD, kGraphCosine>(ctx, f, data, k, general, smax, blocks_dev, nblocks, ids, dist, count);
+  if (m == kGraphInner)
+    return launch_graph<TD, kGraphInner>(ctx, f, data, k, general, smax, blocks_dev, nblocks, ids, dist, count);
+  return launch_graph<TD, kGraphL2>(ctx, f, data, k, general, smax, blocks_dev, nblocks, ids, dist, count);
+}
+
 }  // namespace
 
 int32_t knn_graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
-                      int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+                      int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                      int32_t* count_dev) {
   ctx->last_graph_pairs = 0;
   if (f->n == 0) return RPT_OK;
+  const int m = graph_metric_of(metric);
+  if (m == kGraphCosine) RPT_TRY(ensure_sqnorm(ctx, data));  // the rows' dot(x, x), cached on the dataset
   // the leaf table: the same for every tree (Internal.hs:289,495,503)
   std::vector<Node> nodes;
   enumerate_topology(f->n, f->L, f->min_leaf, nodes);
@@ -398,11 +435,11 @@ int32_t knn_graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int3
   const int64_t nb = (int64_t)blocks.size();
   switch (data->dtype) {
     case RPT_F64:
-      return launch_graph<double>(ctx, f, data, k, general, (int)smax, bdev.p, nb, ids_dev, dist_dev, count_dev);
+      return launch_graph_metric<double>(m, ctx, f, data, k, general, (int)smax, bdev.p, nb, ids_dev, dist_dev, count_dev);
     case RPT_F32:
-      return launch_graph<float>(ctx, f, data, k, general, (int)smax, bdev.p, nb, ids_dev, dist_dev, count_dev);
+      return launch_graph_metric<float>(m, ctx, f, data, k, general, (int)smax, bdev.p, nb, ids_dev, dist_dev, count_dev);
     default:
-      return launch_graph<uint16_t>(ctx, f, data, k, general, (int)smax, bdev.p, nb, ids_dev, dist_dev, count_dev);
+      return launch_graph_metric<uint16_t>(m, ctx, f, data, k, general, (int)smax, bdev.p, nb, ids_dev, dist_dev, count_dev);
   }
 }
 

@@ -1,7 +1,7 @@
 // graph_dev.h — device helpers shared by graph.hip (the graph, leaf by leaf) and graph_refine.hip
 // (its NN-descent rounds): the chunk geometry, the (distance, id) total order, the exact widening
-// of f32 / bf16 elements and the one-wave insertion into a sorted list.  Both translation units
-// are built with -ffp-contract=off.
+// of f32 / bf16 elements, the metric's fold step and epilogue and the one-wave insertion into a
+// sorted list.  Both translation units are built with -ffp-contract=off.
 #pragma once
 
 #include "common.h"
@@ -11,6 +11,38 @@ namespace {
 
 constexpr int kCW = 32;         // columns of a staged chunk
 constexpr int kLS = kCW + 1;    // its row stride in LDS, doubles (odd: no bank conflicts down a column)
+
+// The distance the kernels are instantiated on.  L2: acc + (a - b)^2, then sqrt.  Cosine / inner
+// product (rpt_knn_graph_metric_*): the left-fold dot acc + a * b (two rounded operations per
+// element instead of three), then 1 - acc / (sqrt(n_i) * sqrt(n_j)) with the rows' cached
+// dot(x, x) (rpt_dataset::sqnorm, the same fold) / -acc.  IEEE multiplication commutes and the
+// columns ascend for both rows of a pair, so all three are symmetric bit for bit.
+constexpr int kGraphL2 = 0, kGraphCosine = 1, kGraphInner = 2;
+
+template <int M>
+__device__ __forceinline__ double fold_step(double acc, double a, double b) {
+  if constexpr (M == kGraphL2) {
+    const double t = a - b;
+    const double sq = t * t;
+    return acc + sq;
+  } else {
+    const double pr = a * b;
+    return acc + pr;
+  }
+}
+
+// ni, nj: dot(x, x) of the two rows (cosine only)
+template <int M>
+__device__ __forceinline__ double fold_finish(double acc, double ni, double nj) {
+  if constexpr (M == kGraphL2) return sqrt(acc);
+  else if constexpr (M == kGraphInner) return -acc;
+  else return 1.0 - acc / (sqrt(ni) * sqrt(nj));
+}
+
+// RPT_KNN_METRIC_COSINE / _INNER / 0 of the C ABI -> kGraph*
+inline int graph_metric_of(int32_t metric) {
+  return metric == RPT_KNN_METRIC_COSINE ? kGraphCosine : metric == RPT_KNN_METRIC_INNER ? kGraphInner : kGraphL2;
+}
 
 // the total order of the answer: numbers by (distance, id), then NaN distances by id
 __device__ inline bool before(double da, int ia, double db, int ib) {

@@ -214,14 +214,16 @@ __device__ inline void wave_stage(const TD* __restrict__ X, int d, const int* si
 }
 
 // dynamic LDS, per wave (wave_bytes): 64 * kLS doubles (a chunk of 64 candidates' rows), kCW
-// doubles (the chunk of x_i), H ints (the hash set, later the new candidates), k + r ints (B(i))
-template <class TD>
+// doubles (the chunk of x_i), H ints (the hash set, later the new candidates), k + r ints (B(i)).
+// M: the distance (graph_dev.h); rn: the rows' dot(x, x) (cosine: x_i's once per point, a
+// candidate's one 8-byte gather per new candidate)
+template <class TD, int M>
 __global__ __launch_bounds__(256) void refine_join_kernel(
     RefineState* st, const TD* __restrict__ X, int64_t n, int d, int k, int r, int vec, int H,
     int wave_bytes, const int32_t* __restrict__ ids, const double* __restrict__ dist,
     const int32_t* __restrict__ count, const int64_t* __restrict__ roff,
     const int32_t* __restrict__ rsrc, const double* __restrict__ rdist, int32_t* __restrict__ oids,
-    double* __restrict__ odist, int32_t* __restrict__ ocount) {
+    double* __restrict__ odist, int32_t* __restrict__ ocount, const double* __restrict__ rn) {
   if (!st->active) return;
   extern __shared__ double smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
@@ -245,6 +247,8 @@ __global__ __launch_bounds__(256) void refine_join_kernel(
       lid = ids[i * k + lane];
     }
     const int oid = lid;
+    double ni = 0.0;
+    if constexpr (M == kGraphCosine) ni = rn[i];
 
     // Rev_r(i): the first r of the segment by (stored distance, source)
     int rc = 0, rid = -1;
@@ -309,14 +313,12 @@ __global__ __launch_bounds__(256) void refine_join_kernel(
         if (lane < nrows) {
           const double* row = buf + lane * kLS;
 #pragma unroll 4
-          for (int cc = 0; cc < cw; ++cc) {
-            const double t = xi[cc] - row[cc];
-            const double sq = t * t;
-            acc = acc + sq;
-          }
+          for (int cc = 0; cc < cw; ++cc) acc = fold_step<M>(acc, xi[cc], row[cc]);
         }
       }
-      changed |= wave_merge(ld, lid, c, k, sqrt(acc), my, lane < nrows, 0.0, -1, false);
+      double nj = 0.0;
+      if constexpr (M == kGraphCosine) nj = lane < nrows ? rn[my] : 0.0;
+      changed |= wave_merge(ld, lid, c, k, fold_finish<M>(acc, ni, nj), my, lane < nrows, 0.0, -1, false);
     }
 
     if (lane < k) {
@@ -339,7 +341,7 @@ __global__ __launch_bounds__(256) void refine_join_kernel(
   }
 }
 
-template <class TD>
+template <class TD, int M>
 int32_t launch_join(rpt_ctx* ctx, RefineState* st, const rpt_dataset* data, int k, int r, int H,
                     int wave_bytes, int W, const int32_t* ids, const double* dist,
                     const int32_t* count, const int64_t* roff, const int32_t* rsrc,
@@ -349,22 +351,32 @@ int32_t launch_join(rpt_ctx* ctx, RefineState* st, const rpt_dataset* data, int 
   const int vec = ((reinterpret_cast<uintptr_t>(X) & 15) == 0 && ((size_t)d * sizeof(TD)) % 16 == 0) ? 1 : 0;
   static DeviceOnce attr_once;
   RPT_TRY(attr_once.run(ctx->device, [&]() -> int32_t {
-    RPT_HIP(hipFuncSetAttribute((const void*)refine_join_kernel<TD>,
+    RPT_HIP(hipFuncSetAttribute((const void*)refine_join_kernel<TD, M>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
     return RPT_OK;
   }));
   const int64_t want = (data->n + W - 1) / W;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)ctx->n_cu * 16));
-  hipLaunchKernelGGL(refine_join_kernel<TD>, dim3(grid), dim3(64 * W), (size_t)wave_bytes * W,
+  hipLaunchKernelGGL((refine_join_kernel<TD, M>), dim3(grid), dim3(64 * W), (size_t)wave_bytes * W,
                      ctx->stream, st, X, data->n, d, k, r, vec, H, wave_bytes, ids, dist, count, roff,
-                     rsrc, rdist, oids, odist, ocount);
+                     rsrc, rdist, oids, odist, ocount, M == kGraphCosine ? data->sqnorm : nullptr);
   return RPT_OK;
+}
+
+template <class TD, class... A>
+int32_t launch_join_metric(int m, A... a) {
+  if (m == kGraphCosine) return launch_join<TD, kGraphCosine>(a...);
+  if (m == kGraphInner) return launch_join<TD, kGraphInner>(a...);
+  return launch_join<TD, kGraphL2>(a...);
 }
 
 }  // namespace
 
 int32_t knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
-                             int32_t iters, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+                             int32_t iters, int32_t metric, int32_t* ids_dev, double* dist_dev,
+                             int32_t* count_dev) {
+  const int m = graph_metric_of(metric);
+  if (m == kGraphCosine) RPT_TRY(ensure_sqnorm(ctx, data));  // the rows' dot(x, x), cached on the dataset
   if (!ctx->refine_state_dev) {
     hipError_t e = dev_alloc(&ctx->refine_state_dev, sizeof(RefineState));
     if (e != hipSuccess)
@@ -412,16 +424,16 @@ int32_t knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, i
       }
       switch (data->dtype) {
         case RPT_F64:
-          RPT_TRY(launch_join<double>(ctx, st, data, k, r, H, wave_bytes, W, ids_dev, dist_dev, count_dev,
-                                      roff.p, rsrc.p, rdist.p, sids.p, sdist.p, scount.p));
+          RPT_TRY(launch_join_metric<double>(m, ctx, st, data, k, r, H, wave_bytes, W, ids_dev, dist_dev,
+                                              count_dev, roff.p, rsrc.p, rdist.p, sids.p, sdist.p, scount.p));
           break;
         case RPT_F32:
-          RPT_TRY(launch_join<float>(ctx, st, data, k, r, H, wave_bytes, W, ids_dev, dist_dev, count_dev,
-                                     roff.p, rsrc.p, rdist.p, sids.p, sdist.p, scount.p));
+          RPT_TRY(launch_join_metric<float>(m, ctx, st, data, k, r, H, wave_bytes, W, ids_dev, dist_dev,
+                                             count_dev, roff.p, rsrc.p, rdist.p, sids.p, sdist.p, scount.p));
           break;
         default:
-          RPT_TRY(launch_join<uint16_t>(ctx, st, data, k, r, H, wave_bytes, W, ids_dev, dist_dev, count_dev,
-                                        roff.p, rsrc.p, rdist.p, sids.p, sdist.p, scount.p));
+          RPT_TRY(launch_join_metric<uint16_t>(m, ctx, st, data, k, r, H, wave_bytes, W, ids_dev, dist_dev,
+                                                count_dev, roff.p, rsrc.p, rdist.p, sids.p, sdist.p, scount.p));
       }
       hipLaunchKernelGGL(refine_copy_kernel, dim3(grid_e), dim3(256), 0, ctx->stream, st, n, k, sids.p,
                          sdist.p, scount.p, ids_dev, dist_dev, count_dev);

@@ -3898,8 +3898,9 @@ static int32_t ensure_shadow8(rpt_ctx* ctx, const rpt_dataset* data) {
 
 // The metrics' row norms dot(x, x), once per dataset (8 bytes per row, freed with it), followed by
 // the two statistics of row_sqnorm_kernel (the certified cut's bound).  Unlike the shadows this is
-// not optional: without it the metric cannot be evaluated or its cut certified.
-static int32_t ensure_sqnorm(rpt_ctx* ctx, const rpt_dataset* data) {
+// not optional: without it the metric cannot be evaluated or its cut certified.  Declared in
+// common.h: the cosine kNN graph and its refinement (graph.hip, graph_refine.hip) read it too.
+int32_t ensure_sqnorm(rpt_ctx* ctx, const rpt_dataset* data) {
   if (data->sqnorm) return RPT_OK;
   DevBuf<double> rn;
   RPT_TRY(rn.alloc((size_t)data->n + 2));

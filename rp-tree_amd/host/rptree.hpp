@@ -356,6 +356,30 @@ inline GraphResult knnGraph(const RPForest& tts, int k, const GraphResult* accum
   return g;
 }
 
+// ... under another distance (rpt_knn_graph_metric_host): Metric::Cosine / Metric::Inner, the
+// distances of RPT_KNN_METRIC_COSINE / _INNER bit for bit (the left-fold dot in double); Metric::L2
+// gives knnGraph's bits.  accumulate must be a result under the same metric (not detected).
+inline GraphResult knnGraph(const RPForest& tts, int k, Metric metric, const GraphResult* accumulate = nullptr) {
+  const size_t n = (size_t)tts.data->n;
+  GraphResult g;
+  if (accumulate) {
+    if (accumulate->k != k || accumulate->count.size() != n)
+      throw RPTError(RPT_E_ARG, "accumulate: a result of another data set or k");
+    g = *accumulate;
+  }
+  g.k = k;
+  g.ids.resize(n * (size_t)(k > 0 ? k : 0) + 1);  // + 1: non-NULL pointers for an empty data set
+  g.dist.resize(n * (size_t)(k > 0 ? k : 0) + 1);
+  g.count.resize(n + 1);
+  check(rpt_knn_graph_metric_host(tts.ctx->get(), tts.get(), tts.data->get(), k, metric_flags(metric),
+                                  accumulate ? RPT_GRAPH_ACCUMULATE : 0, g.ids.data(), g.dist.data(),
+                                  g.count.data()));
+  g.ids.resize(n * (size_t)k);
+  g.dist.resize(n * (size_t)k);
+  g.count.resize(n);
+  return g;
+}
+
 // NN-descent rounds over a kNN graph (rpt_knn_graph_refine_host) -> the refined graph; `g` is not
 // modified.  One round gives row i the first k, by (distance, id), of its neighbours, up to
 // `reverse` of the points that list i (-1 = k, 0 = none) and all of their neighbours; a round
@@ -375,6 +399,27 @@ inline GraphResult knnGraphRefine(Context& ctx, const Dataset& data, const Graph
   out.count.resize(n + 1);
   check(rpt_knn_graph_refine_host(ctx.get(), data.get(), g.k, reverse < 0 ? g.k : reverse, iters, 0,
                                   out.ids.data(), out.dist.data(), out.count.data()));
+  out.ids.resize(n * (size_t)g.k);
+  out.dist.resize(n * (size_t)g.k);
+  out.count.resize(n);
+  if (stats) check(rpt_knn_graph_refine_last(ctx.get(), &stats->rounds, &stats->updates, &stats->candidates));
+  return out;
+}
+
+// ... under another distance (rpt_knn_graph_refine_metric_host); the graph's stored distances must
+// be that metric's (knnGraph's under the same Metric; another is not detected)
+inline GraphResult knnGraphRefine(Context& ctx, const Dataset& data, const GraphResult& g, Metric metric,
+                                  int iters = 1, int reverse = -1, RefineStats* stats = nullptr) {
+  const size_t n = (size_t)data.n;
+  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0) || g.dist.size() != g.ids.size())
+    throw RPTError(RPT_E_ARG, "knnGraphRefine: a graph of another data set or k");
+  GraphResult out = g;
+  out.ids.resize(out.ids.size() + 1);  // + 1: non-NULL pointers for an empty data set
+  out.dist.resize(out.dist.size() + 1);
+  out.count.resize(n + 1);
+  check(rpt_knn_graph_refine_metric_host(ctx.get(), data.get(), g.k, reverse < 0 ? g.k : reverse, iters,
+                                         metric_flags(metric), 0, out.ids.data(), out.dist.data(),
+                                         out.count.data()));
   out.ids.resize(n * (size_t)g.k);
   out.dist.resize(n * (size_t)g.k);
   out.count.resize(n);

@@ -37,6 +37,7 @@ __all__ = [
     "metricCosine", "metricInner", "recallWithBatch", "recallHits",
     "knnGraph", "knnGraphDev", "knnGraphLastPairs",
     "knnGraphRefine", "knnGraphRefineDev", "knnGraphRefineLast",
+    "knnGraphMetric", "knnGraphMetricDev", "knnGraphRefineMetric", "knnGraphRefineMetricDev",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -809,6 +810,40 @@ def knnGraphDev(k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
                                   C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
+def knnGraphMetric(distf, k, forest, accumulate=None):
+    """knnGraph under another distance (rpt_knn_graph_metric_host).  distf: None / metricL2 (the same
+    bits as knnGraph), metricCosine or metricInner; the distances are those host functions bit for
+    bit (the left-fold dot in double for every dtype), a zero row is NaN under metricCosine and
+    ranks last.  accumulate: an earlier answer UNDER THE SAME distf (another is not detected: the
+    stored distances are taken as stored).  Everything else as knnGraph."""
+    metric = _metric_flag(distf)
+    ctx, n = forest.ctx, forest.N
+    if accumulate is None:
+        flags = 0
+        ids = np.empty((n, k), dtype=np.int32)
+        dist = np.empty((n, k), dtype=np.float64)
+        cnt = np.empty(n, dtype=np.int32)
+    else:
+        flags = RPT_GRAPH_ACCUMULATE
+        ids = np.array(accumulate[0], dtype=np.int32, order="C")
+        dist = np.array(accumulate[1], dtype=np.float64, order="C")
+        cnt = np.array(accumulate[2], dtype=np.int32, order="C")
+        if ids.shape != (n, k) or dist.shape != (n, k) or cnt.shape != (n,):
+            raise ValueError("accumulate must be (ids[n][k], dist[n][k], count[n]) of this forest's n and k")
+    check(lib().rpt_knn_graph_metric_host(ctx._h, forest._h, forest.data._h, int(k), metric, flags,
+                                          _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnGraphMetricDev(distf, k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
+    """knnGraphMetric into device arrays (rpt_knn_graph_metric_dev); the arrays and the
+    synchronisation as knnGraphDev's."""
+    metric = _metric_flag(distf)
+    check(lib().rpt_knn_graph_metric_dev(forest.ctx._h, forest._h, forest.data._h, int(k),
+                                         metric, RPT_GRAPH_ACCUMULATE if accumulate else 0,
+                                         C.c_void_p(ids_ptr), C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
+
+
 def knnGraphLastPairs(ctx=None):
     """distances the last knnGraph call on ctx evaluated (rpt_knn_graph_last_pairs)"""
     ctx = ctx or default_context()
@@ -852,6 +887,36 @@ def knnGraphRefineDev(k, data, ids_ptr, dist_ptr, count_ptr, iters=1, reverse=No
     check(lib().rpt_knn_graph_refine_dev(ds.ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
                                          int(iters), 0, C.c_void_p(ids_ptr), C.c_void_p(dist_ptr),
                                          C.c_void_p(count_ptr)))
+
+
+def knnGraphRefineMetric(distf, graph, data, iters=1, reverse=None, ctx=None):
+    """knnGraphRefine under another distance (rpt_knn_graph_refine_metric_host).  distf: None /
+    metricL2 (the same bits as knnGraphRefine), metricCosine or metricInner; distances not already
+    in row i are those host functions bit for bit.  The graph's stored distances must be distf's
+    (knnGraphMetric's under the same distf; another metric is not detected).  Everything else as
+    knnGraphRefine."""
+    metric = _metric_flag(distf)
+    ds = _refine_data(data)
+    ctx = ctx or ds.ctx
+    ids = np.array(graph[0], dtype=np.int32, order="C")
+    dist = np.array(graph[1], dtype=np.float64, order="C")
+    cnt = np.array(graph[2], dtype=np.int32, order="C")
+    if ids.ndim != 2 or ids.shape[0] != ds.n or dist.shape != ids.shape or cnt.shape != (ds.n,):
+        raise ValueError("graph must be (ids[n][k], dist[n][k], count[n]) over the data set's n rows")
+    k = ids.shape[1]
+    check(lib().rpt_knn_graph_refine_metric_host(ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
+                                                 int(iters), metric, 0, _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnGraphRefineMetricDev(distf, k, data, ids_ptr, dist_ptr, count_ptr, iters=1, reverse=None):
+    """knnGraphRefineMetric on device arrays in place (rpt_knn_graph_refine_metric_dev); the arrays
+    and the synchronisation as knnGraphRefineDev's."""
+    metric = _metric_flag(distf)
+    ds = _refine_data(data)
+    check(lib().rpt_knn_graph_refine_metric_dev(ds.ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
+                                                int(iters), metric, 0, C.c_void_p(ids_ptr),
+                                                C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
 def knnGraphRefineLast(ctx=None):

@@ -76,6 +76,10 @@ SYMBOLS = {
     "rpt_knn_graph_refine_dev": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_knn_graph_refine_host": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_knn_graph_refine_last": (i32, [vp, p_i64, p_i64, p_i64]),
+    "rpt_knn_graph_metric_dev": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rpt_knn_graph_metric_host": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rpt_knn_graph_refine_metric_dev": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "rpt_knn_graph_refine_metric_host": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_knn_merge_dev": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp]),
     "rpt_knn_record_layout": (i32, [i64, i32, vp, vp, vp, vp]),
     "rpt_knn_merge_records_dev": (i32, [vp, vp, i64, i32, i64, i32, i32, vp, vp, vp]),
