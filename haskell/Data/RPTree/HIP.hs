@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, graphSearchHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -53,6 +53,7 @@ foreign import ccall safe "rpt_knn_graph_host"      c_knn_graph_host :: Ptr Ctx 
 foreign import ccall safe "rpt_knn_graph_refine_host" c_knn_graph_refine_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_metric_host" c_knn_graph_metric_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_refine_metric_host" c_knn_graph_refine_metric_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_graph_search_host" c_graph_search_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
 -- multi-GPU (csrc/comm.hip on librccl): one process drives n devices; per-device arguments are
 -- arrays with one entry per device (Foreign.Marshal.Array.withArray)
@@ -289,6 +290,23 @@ knnGraphRefineMetricHIP ctx ds m _n k reverse iters (i0, d0, c0) = do
   dist <- VS.thaw d0
   cnt <- VS.thaw c0
   VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_refine_metric_host ctx ds (fromIntegral k) (fromIntegral reverse) (fromIntegral iters) (metricFlag m) 0 a b))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | Query a kNN graph: best-first beam search (rpt_graph_search_host).  @(gids, gcount)@ is a graph
+-- over the data set with @kg@ slots per row ('knnGraphHIP' \/ 'knnGraphRefineHIP', the distances are
+-- not read); @seeds@ holds @s@ start ids per query (-1 = unused slot, s <= 64).  The seeds are
+-- offered to a beam of at most @ef@ entries sorted by (distance, id), then the graph row of the
+-- beam's first unexpanded entry, until none is left; the answer is the first k of the beam, unused
+-- slots id -1, distance +Infinity.  Distances are the metric's left fold in Double ('MetricCosine' \/
+-- 'MetricInner' bit-equal to the exhaustive answer).  k <= 64, k <= ef <= 256; nq = number of queries.
+graphSearchHIP :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Metric -> Int -> Int
+               -> (VS.Vector Int32, VS.Vector Int32) -> Int -> VS.Vector Int32 -> Int -> Int
+               -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+graphSearchHIP ctx ds qs m nq kg (gids, gcount) s seeds k ef = do
+  ids <- VSM.new (nq * k); dist <- VSM.new (nq * k); cnt <- VSM.new nq
+  VS.unsafeWith gids (\pg -> VS.unsafeWith gcount (\pc -> VS.unsafeWith seeds (\ps ->
+    VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
+      c_graph_search_host ctx ds qs (fromIntegral kg) pg pc (fromIntegral s) ps (fromIntegral k) (fromIntegral ef) (metricFlag m) 0 a b)))))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | SVector rows as a CSR dataset on the device (rpt_dataset_csr_host), for the extent of the

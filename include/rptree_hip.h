@@ -145,6 +145,8 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *   graph_general (0 / 1)          kNN graph: every leaf on the tiled kernel (rpt_knn_graph_*)
  *   graph_refine_general (0 / 1)   kNN graph refinement: one point per workgroup for every k and
  *                                  reverse (rpt_knn_graph_refine_*)
+ *   graph_search_nofilter (0 / 1)  graph search: no visited filter, only the beam itself is checked
+ *                                  before a distance is computed (rpt_graph_search_*)
  *   brute_csr_tile (0 auto, n)     brute force over CSR rows: queries per workgroup (1, 2, 4 or 8; other
  *                                  values round down; halved while the tile does not fit LDS; auto
  *                                  takes up to 4)
@@ -493,6 +495,65 @@ int32_t rpt_knn_graph_refine_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, i
 int32_t rpt_knn_graph_refine_metric_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
                                          int32_t reverse, int32_t iters, int32_t metric, int32_t flags,
                                          int32_t* ids_host, double* dist_host, int32_t* count_host);
+
+/* ---- query the kNN graph: best-first beam search from given seeds ----
+ * Input: the dense data set `data` (n rows of f64, f32 or bf16), the dense `queries` (the same d and
+ * element type, as rpt_knn_* requires), a graph over the data set in rpt_knn_graph_*'s layout of
+ * which ONLY gids[n][kg] and gcount[n] are read (the stored distances play no part; kg in
+ * [1, RPT_GRAPH_MAX_K]), seeds[nq][s] (s in [1, 64]; -1 marks an unused slot, the same id twice
+ * counts once), k in [1, 64], ef in [k, RPT_GRAPH_SEARCH_MAX_EF] and `metric`: 0 (L2),
+ * RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER.  The result is a pure function of these.
+ *   dist(q, v)  exactly the distance of rpt_knn_graph_metric_* with q in the place of x_i: a left
+ *               fold in double, columns ascending, elements widened exactly, every operation
+ *               rounded on its own, no FMA; L2 takes one sqrt; cosine uses the cached dot(x, x) of
+ *               the row and the same fold for dot(q, q).  So it is bit-equal to
+ *               rpt_brute_knn_metric_host for cosine and inner product on all three dtypes, and to
+ *               rpt_brute_knn_host (L2) on f64 rows.
+ *   Order       entries are ordered by (distance, id), NaN behind every number, NaNs among
+ *               themselves by id.
+ *   Beam        B holds at most ef entries, sorted, each flagged expanded or not.  Offering a set S
+ *               to B means B <- the first ef of B u {(dist(q, v), v) : v in S}, every id once; new
+ *               entries start unexpanded.
+ *   Search      1. offer the valid seeds (ids in [0, n)).  2. repeat: let u be the first unexpanded
+ *               entry of B in the order; if there is none, stop; otherwise mark u expanded and
+ *               offer the valid ids of graph row u (slots < gcount[u], ids in [0, n); a row whose
+ *               gcount lies outside [0, kg] offers nothing).
+ *   Answer      the first k of B, count = min(k, |B|); unused slots hold id -1 and distance +inf.  A
+ *               query whose seeds are all -1 has count 0.
+ * Termination: an entry that is evicted, or an id that is rejected against a full beam, can never
+ * enter later, because the beam's last entry only moves forward.  So a point is expanded at most
+ * once and the loop ends after at most n expansions (the kernel's loop has exactly that bound).
+ * Visited set: for the same reason, remembering which ids were already evaluated only saves work:
+ * the answer is the same with an exact visited set, a lossy one, or none.  The kernel keeps a
+ * small lossy hash of evaluated ids per query and checks the beam itself exactly; the context
+ * option graph_search_nofilter switches the hash off; the answer and `expansions` do not depend
+ * on it, only `evaluated` does.  One wave answers a query; nothing is shared between queries and
+ * no atomics touch a beam, so the same input gives the same bits whatever the launch shape.
+ * rpt_graph_search_last (synchronises the stream), sums over the last call's queries:
+ *   expansions  entries marked expanded (defined by the text above)
+ *   evaluated   distances the kernel really computed: at least the number of distinct ids offered,
+ *               at most the valid seed slots plus gcount[u] over the expanded u
+ * Errors: k, ef, s or kg out of range, ef < k, flags other than 0, queries whose d or dtype differ
+ * from the data's, a dense / CSR pair, any other `metric` value, both metric bits together,
+ * RPT_KNN_METRIC_REFERENCE: RPT_E_ARG.  CSR data: RPT_E_UNSUPPORTED.  nq = 0 and n = 0 are valid;
+ * with n = 0 every count is 0.  Scratch comes from the context's pool: RPT_E_NOMEM.  Timed under
+ * rpt_prof_* class 3.  A call leaves rpt_knn_last_* and the forests' ranking tiers untouched.
+ * _dev borrows device arrays, enqueues on the ctx stream, does not synchronise and does NOT validate
+ * the arrays: a graph id or seed outside [0, n) and a gcount outside [0, kg] are skipped, never
+ * followed.  _host checks BEFORE anything is uploaded that every gcount is in [0, kg], every valid
+ * graph id in [0, n) and every seed -1 or in [0, n), and returns RPT_E_ARG naming the row; it
+ * synchronises. */
+#define RPT_GRAPH_SEARCH_MAX_EF 256
+int32_t rpt_graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                             int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
+                             const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
+                             int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+int32_t rpt_graph_search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                              int32_t kg, const int32_t* gids_host, const int32_t* gcount_host,
+                              int32_t s, const int32_t* seeds_host, int32_t k, int32_t ef,
+                              int32_t metric, int32_t flags, int32_t* ids_host, double* dist_host,
+                              int32_t* count_host);
+int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
 
 /* multi-GPU merge: G per-shard results (shard g holds trees [g*T/G, (g+1)*T/G)), gathered
  * shard-major as ids_dev[G][nq][k] etc. (e.g. by an RCCL all-gather), merged into the

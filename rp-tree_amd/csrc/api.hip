@@ -242,6 +242,7 @@ const OptDesc kOptions[] = {
     {"knn_general", &rpt_options::knn_general},
     {"graph_general", &rpt_options::graph_general},
     {"graph_refine_general", &rpt_options::graph_refine_general},
+    {"graph_search_nofilter", &rpt_options::graph_search_nofilter},
     {"knn_shard_old", &rpt_options::knn_shard_old},
     {"brute_csr_tile", &rpt_options::brute_csr_tile},
     {"comm_force_exchange", &rpt_options::comm_force_exchange},
@@ -363,6 +364,7 @@ int32_t rpt_ctx_destroy(rpt_ctx* ctx) {
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->metric_unc_dev) dev_free(ctx->metric_unc_dev);
     if (ctx->refine_state_dev) dev_free(ctx->refine_state_dev);
+    if (ctx->search_state_dev) dev_free(ctx->search_state_dev);
     dev_trim();
     delete ctx;
     return RPT_OK;
@@ -1349,6 +1351,109 @@ int32_t rpt_knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* update
     RPT_ARG(ctx && rounds && updates && candidates, "NULL argument");
     RPT_HIP(hipSetDevice(ctx->device));
     return knn_graph_refine_last(ctx, rounds, updates, candidates);
+  });
+}
+
+// ---- beam search over a kNN graph -------------------------------------------------------------
+namespace {
+int32_t check_search(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
+                     int32_t s, int32_t k, int32_t ef, int32_t metric, int32_t flags) {
+  RPT_ARG(ctx && data && queries, "NULL argument");
+  RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
+  RPT_TRY(check_graph_metric(metric));
+  RPT_ARG(flags == 0, "flags must be 0");
+  RPT_ARG(data->csr == queries->csr, "data and queries must both be dense or both CSR");
+  if (data->csr) return fail(RPT_E_UNSUPPORTED, "the graph search takes dense data only (not CSR rows)");
+  RPT_ARG(data->d == queries->d && data->dtype == queries->dtype,
+          "queries differ from the data set in d or dtype");
+  RPT_ARG(kg >= 1 && kg <= RPT_GRAPH_MAX_K, "kg must be in [1,64] (RPT_GRAPH_MAX_K)");
+  RPT_ARG(s >= 1 && s <= 64, "s (seeds per query) must be in [1,64]");
+  RPT_ARG(k >= 1 && k <= 64, "k must be in [1,64]");
+  RPT_ARG(ef >= k, "ef must be at least k");
+  RPT_ARG(ef <= RPT_GRAPH_SEARCH_MAX_EF, "ef must be at most 256 (RPT_GRAPH_SEARCH_MAX_EF)");
+  RPT_ARG(data->n <= 0x7fffffff, "graph too large");
+  return RPT_OK;
+}
+}  // namespace
+
+int32_t rpt_graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                             int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
+                             const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
+                             int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags));
+    RPT_ARG(data->n == 0 || (gids_dev && gcount_dev), "NULL graph arrays");
+    RPT_ARG(queries->n == 0 || (seeds_dev && ids_dev && dist_dev && count_dev), "NULL seeds or output");
+    RPT_HIP(hipSetDevice(ctx->device));
+    return graph_search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric,
+                            ids_dev, dist_dev, count_dev);
+  });
+}
+
+int32_t rpt_graph_search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                              int32_t kg, const int32_t* gids_host, const int32_t* gcount_host,
+                              int32_t s, const int32_t* seeds_host, int32_t k, int32_t ef,
+                              int32_t metric, int32_t flags, int32_t* ids_host, double* dist_host,
+                              int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags));
+    const int64_t n = data->n, nq = queries->n;
+    RPT_ARG(n == 0 || (gids_host && gcount_host), "NULL graph arrays");
+    RPT_ARG(nq == 0 || (seeds_host && ids_host && dist_host && count_host), "NULL seeds or output");
+    // the graph and the seeds are checked here, before anything is uploaded
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t c = gcount_host[i];
+      if (c < 0 || c > kg)
+        return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": count " + std::to_string(c) +
+                                   " outside [0, kg]");
+      for (int32_t e = 0; e < c; ++e) {
+        const int32_t id = gids_host[i * kg + e];
+        if (id < 0 || id >= n)
+          return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": id " + std::to_string(id) +
+                                     " outside [0, n)");
+      }
+    }
+    for (int64_t q = 0; q < nq; ++q)
+      for (int32_t e = 0; e < s; ++e) {
+        const int32_t id = seeds_host[q * s + e];
+        if (id != -1 && (id < 0 || id >= n))
+          return fail(RPT_E_ARG, "seeds row " + std::to_string(q) + ": id " + std::to_string(id) +
+                                     " is neither -1 nor in [0, n)");
+      }
+    RPT_HIP(hipSetDevice(ctx->device));
+    DevBuf<int32_t> gids, gcnt, seeds, ids, cnt;
+    DevBuf<double> dist;
+    RPT_TRY(gids.alloc((size_t)n * kg));
+    RPT_TRY(gcnt.alloc((size_t)n));
+    RPT_TRY(seeds.alloc((size_t)nq * s));
+    RPT_TRY(ids.alloc((size_t)nq * k));
+    RPT_TRY(dist.alloc((size_t)nq * k));
+    RPT_TRY(cnt.alloc((size_t)nq));
+    if (n) {
+      RPT_HIP(hipMemcpy(gids.p, gids_host, (size_t)n * kg * 4, hipMemcpyHostToDevice));
+      RPT_HIP(hipMemcpy(gcnt.p, gcount_host, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    if (nq) RPT_HIP(hipMemcpy(seeds.p, seeds_host, (size_t)nq * s * 4, hipMemcpyHostToDevice));
+    RPT_TRY(graph_search_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, metric, ids.p,
+                             dist.p, cnt.p));
+    RPT_HIP(stream_sync(ctx->stream));
+    if (nq) {
+      RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+      RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+      RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    }
+    return RPT_OK;
+  });
+}
+
+int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ctx && expansions && evaluated, "NULL argument");
+    RPT_HIP(hipSetDevice(ctx->device));
+    return graph_search_last(ctx, expansions, evaluated);
   });
 }
 

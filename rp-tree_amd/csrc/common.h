@@ -168,6 +168,7 @@ struct rpt_options {
   int64_t knn_general = 0;      // kNN: unfused general path
   int64_t graph_general = 0;    // kNN graph: every leaf on the tiled kernel (64-row blocks), not the one-workgroup leaf kernel
   int64_t graph_refine_general = 0;  // kNN graph refinement: one point per workgroup for every k and reverse
+  int64_t graph_search_nofilter = 0;  // graph search: no visited filter (only the beam itself is checked before a distance)
   int64_t brute_csr_tile = 0;   // brute force on CSR rows: queries per workgroup (0 = auto; 1, 2, 4 or 8)
   int64_t knn_shard_old = 0;    // kNN: small shards keep the round-3 one-wave kernel (in-kernel traversal, fixed k')
   int64_t comm_force_exchange = 0;  // sharded kNN: a one-rank communicator runs record -> all-gather -> merge too
@@ -196,6 +197,7 @@ struct rpt_ctx {
   int64_t last_retries = 0;      // queries of the last fused kNN call that took the in-kernel wider second attempt
   int64_t last_graph_pairs = 0;  // distances the last rpt_knn_graph_* call evaluated
   void* refine_state_dev = nullptr;  // graph_refine.hip: the last rpt_knn_graph_refine_* call's flag and counters
+  void* search_state_dev = nullptr;  // graph_search.hip: the last rpt_graph_search_* call's counters
   int32_t last_tier = 0;  // ranking tier of the last fused kNN call: 0 exact, 1 f32 shadow, 2 half, 3 int8
   // last build: nodes csub_kernel handed back to the general kernels (pivot codes shared by more
   // points than its pool), and how many of those for a histogram that contradicted the node
@@ -403,6 +405,16 @@ int32_t knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, i
                              int32_t* count_dev);
 // synchronises the stream
 int32_t knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* updates, int64_t* candidates);
+// ---- beam search over a kNN graph (graph_search.hip) -----------------------------------------
+// arguments checked by the caller (dense data and queries of one shape and dtype, kg, s, k <= 64,
+// k <= ef <= RPT_GRAPH_SEARCH_MAX_EF; metric as knn_graph_dev's); the arrays are not validated:
+// entries out of range are skipped; enqueued on the ctx stream
+int32_t graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
+                         const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
+                         const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
+                         int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+// synchronises the stream
+int32_t graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
 int32_t knn_h(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
               int32_t k, int64_t* off_host, int32_t* ids_host, double* dist_host, int64_t cap,
               int64_t* total);

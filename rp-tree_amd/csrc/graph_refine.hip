@@ -50,12 +50,6 @@ struct RefineState {
   unsigned long long rounds, updates, candidates;
 };
 
-__device__ inline void wave_sync() {  // LDS writes of the wave visible to all its lanes
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ void refine_begin_kernel(RefineState* st) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     st->active = 1;
@@ -171,45 +165,6 @@ __device__ inline void set_insert(int* tab, int mask, int shift, int c, int stor
     const int old = atomicCAS(&tab[h], kEmpty, stored);
     if (old == kEmpty || old == c || old == ~c) return;
     h = (h + 1) & (unsigned)mask;
-  }
-}
-
-// one wave: columns [c0, c0 + cw) of the rows sid[0 .. nrows) as doubles into buf[r * kLS + c],
-// graph.hip's stage_chunk with a wave in place of the workgroup; four loads in flight per lane
-template <class TD>
-__device__ inline void wave_stage(const TD* __restrict__ X, int d, const int* sid, int nrows, int c0,
-                                  int cw, double* buf, bool vec) {
-  const int lane = threadIdx.x & 63;
-  if (vec) {
-    constexpr int E = 16 / (int)sizeof(TD);
-    const int ppr = cw / E, total = nrows * ppr;
-    for (int p0 = 0; p0 < total; p0 += 256) {
-      uint4 v[4];
-      int at[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int p = p0 + u * 64 + lane;
-        at[u] = -1;
-        if (p < total) {
-          const int r = p / ppr, q = p - r * ppr;
-          at[u] = r * kLS + q * E;
-          v[u] = *reinterpret_cast<const uint4*>(X + (size_t)sid[r] * d + c0 + q * E);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (at[u] >= 0) {
-          double w[E];
-          widen16<TD>(v[u], w);
-#pragma unroll
-          for (int e = 0; e < E; ++e) buf[at[u] + e] = w[e];
-        }
-    }
-  } else {
-    for (int p = lane; p < nrows * cw; p += 64) {
-      const int r = p / cw, c = p - r * cw;
-      buf[r * kLS + c] = widen(X[(size_t)sid[r] * d + c0 + c]);
-    }
   }
 }
 

@@ -427,6 +427,64 @@ inline GraphResult knnGraphRefine(Context& ctx, const Dataset& data, const Graph
   return out;
 }
 
+// Query a kNN graph: best-first beam search (rpt_graph_search_host).  g: a graph over `data`
+// (knnGraph's, knnGraphRefine's; only ids and count are read), qs: dense queries of the data's d,
+// seeds: [nq][s] start ids (s <= 64, -1 = unused slot), ef: entries of the beam (k <= ef <= 256).
+// The seeds are offered to the beam, then the graph row of its first unexpanded entry, until none
+// is left; the answer is the first k of the beam by (distance, id), unused slots id -1, distance
+// +inf.  Distances are the metric's left fold in double (Metric::Cosine / Inner bit-equal to
+// bruteKnn's).  stats (optional): entries expanded, distances computed (rpt_graph_search_last).
+struct KnnResult {
+  int k = 0;
+  std::vector<int32_t> ids;    // [nq][k]
+  std::vector<double> dist;    // [nq][k]
+  std::vector<int32_t> count;  // [nq]
+};
+struct SearchStats {
+  int64_t expansions = 0, evaluated = 0;
+};
+inline KnnResult graphSearch(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs, int k,
+                             int ef, const std::vector<int32_t>& seeds, int s, Metric metric,
+                             SearchStats* stats = nullptr) {
+  const size_t n = (size_t)data.n, nq = (size_t)qs.n;
+  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0))
+    throw RPTError(RPT_E_ARG, "graphSearch: a graph of another data set");
+  if (s < 1 || seeds.size() != nq * (size_t)s) throw RPTError(RPT_E_ARG, "graphSearch: seeds must be [nq][s]");
+  const int32_t none = -1;  // non-NULL pointers for empty inputs
+  KnnResult r;
+  r.k = k;
+  r.ids.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
+  r.dist.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
+  r.count.resize(nq + 1);
+  check(rpt_graph_search_host(ctx.get(), data.get(), qs.get(), g.k, n ? g.ids.data() : &none,
+                              n ? g.count.data() : &none, s, nq ? seeds.data() : &none, k, ef,
+                              metric_flags(metric), 0, r.ids.data(), r.dist.data(), r.count.data()));
+  r.ids.resize(nq * (size_t)k);
+  r.dist.resize(nq * (size_t)k);
+  r.count.resize(nq);
+  if (stats) check(rpt_graph_search_last(ctx.get(), &stats->expansions, &stats->evaluated));
+  return r;
+}
+inline KnnResult graphSearch(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs, int k,
+                             int ef, const std::vector<int32_t>& seeds, int s, SearchStats* stats = nullptr) {
+  return graphSearch(ctx, data, g, qs, k, ef, seeds, s, Metric::L2, stats);
+}
+// ... the seeds taken from a forest: the ids of its de-duplicated seed_k nearest candidates
+// (rpt_knn_host with RPT_KNN_DEDUP under the same metric), slots beyond that answer's count -1
+inline KnnResult graphSearch(const RPForest& tts, const GraphResult& g, const Dataset& qs, int k, int ef,
+                             Metric metric = Metric::L2, int seed_k = 8, SearchStats* stats = nullptr) {
+  const size_t nq = (size_t)qs.n;
+  if (seed_k < 1) throw RPTError(RPT_E_ARG, "graphSearch: seed_k must be at least 1");
+  std::vector<int32_t> seeds(nq * (size_t)seed_k + 1), cnt(nq + 1);
+  std::vector<double> dist(nq * (size_t)seed_k + 1);
+  check(rpt_knn_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), seed_k,
+                     RPT_KNN_DEDUP | metric_flags(metric), seeds.data(), dist.data(), cnt.data()));
+  seeds.resize(nq * (size_t)seed_k);
+  for (size_t i = 0; i < nq; ++i)
+    for (int e = cnt[i]; e < seed_k; ++e) seeds[i * (size_t)seed_k + (size_t)e] = -1;
+  return graphSearch(*tts.ctx, *tts.data, g, qs, k, ef, seeds, seed_k, metric, stats);
+}
+
 struct BruteResult {
   std::vector<int32_t> ids;  // [nq][k], -1 = unused slot
   std::vector<double> dist;  // [nq][k]

@@ -22,7 +22,8 @@ from collections import namedtuple
 import numpy as np
 
 from . import gen
-from ._lib import (RPT_BF16, RPT_F32, RPT_F64, RPT_GRAPH_ACCUMULATE, RPT_GRAPH_MAX_K, RPT_KNN_DEDUP, RPT_KNN_DEDUP_DISTANCE,
+from ._lib import (RPT_BF16, RPT_F32, RPT_F64, RPT_GRAPH_ACCUMULATE, RPT_GRAPH_MAX_K, RPT_GRAPH_SEARCH_MAX_EF,
+                   RPT_KNN_DEDUP, RPT_KNN_DEDUP_DISTANCE,
                    RPT_KNN_KEEP_DUPLICATES, RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER,
                    RPT_KNN_METRIC_REFERENCE,
                    RPT_PROJ_AUTO, RPT_PROJ_EXACT, RPT_PROJ_MFMA, RPTError, check, lib)
@@ -38,6 +39,7 @@ __all__ = [
     "knnGraph", "knnGraphDev", "knnGraphLastPairs",
     "knnGraphRefine", "knnGraphRefineDev", "knnGraphRefineLast",
     "knnGraphMetric", "knnGraphMetricDev", "knnGraphRefineMetric", "knnGraphRefineMetricDev",
+    "graphSearch", "graphSearchDev", "graphSearchLast",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -927,6 +929,67 @@ def knnGraphRefineLast(ctx=None):
     a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
     check(lib().rpt_knn_graph_refine_last(ctx._h, C.byref(a), C.byref(b), C.byref(c)))
     return int(a.value), int(b.value), int(c.value)
+
+
+def graphSearch(graph, data, qs, k, ef=None, seeds=None, forest=None, seed_k=8, metric=None, ctx=None):
+    """Best-first beam search over a kNN graph (rpt_graph_search_host) -> (ids[nq][k], dist[nq][k],
+    count[nq]).  graph: (ids[n][kg], dist[n][kg], count[n]) over `data`, e.g. knnGraph's or
+    knnGraphRefine's (the distances are not read; a pair (ids, count) will do); data: a dense Dataset,
+    or a forest (its .data is used).  The beam holds ef entries (None = max(k, 32), at most 256); the
+    search starts from seeds[nq][s] (s <= 64, -1 = unused slot) or, with `forest`, from the ids of
+    knnBatch(seed_k, forest, qs, dedup=True, metric=metric), and repeatedly offers the graph row of
+    the beam's first unexpanded entry until none is left.  The answer is the first k of the beam
+    by (distance, id); metric: None / metricL2, metricCosine or metricInner, the distances those
+    host functions bit for bit (L2: on f64 rows).  Unused slots are id -1, distance +inf."""
+    metric_flag = _metric_flag(metric)
+    ds = _refine_data(data)
+    ctx = ctx or ds.ctx
+    gids = np.ascontiguousarray(graph[0], dtype=np.int32)
+    gcnt = np.ascontiguousarray(graph[-1], dtype=np.int32)
+    if gids.ndim != 2 or gids.shape[0] != ds.n or gcnt.shape != (ds.n,):
+        raise ValueError("graph must be (ids[n][kg], dist[n][kg], count[n]) over the data set's n rows")
+    if ef is None:
+        ef = max(int(k), 32)
+    if seeds is None and forest is None:
+        raise ValueError("graphSearch needs seeds or a forest to take them from")
+    qd, nq = _query_dataset(ctx, ds, qs)
+    if seeds is None:
+        sid, _, scnt = knnBatch(int(seed_k), forest, qd, dedup=True, metric=metric)
+        seeds = np.where(np.arange(sid.shape[1])[None, :] < scnt[:, None], sid, -1)
+    seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+    if seeds.ndim != 2 or seeds.shape[0] != nq:
+        raise ValueError("seeds must be [nq][s]")
+    ids = np.empty((nq, k), dtype=np.int32)
+    dist = np.empty((nq, k), dtype=np.float64)
+    cnt = np.empty(nq, dtype=np.int32)
+    check(lib().rpt_graph_search_host(ctx._h, ds._h, qd._h, int(gids.shape[1]), _vp(gids), _vp(gcnt),
+                                      int(seeds.shape[1]), _vp(seeds), int(k), int(ef), metric_flag, 0,
+                                      _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def graphSearchDev(data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, k, ef, ids_ptr, dist_ptr, count_ptr,
+                   metric=None):
+    """graphSearch on device arrays (rpt_graph_search_dev): data and queries are Datasets, the graph
+    (int32 [n][kg], int32 [n]), the seeds (int32 [nq][s]) and the outputs (int32 [nq][k], float64
+    [nq][k], int32 [nq]) device addresses.  The arrays are NOT validated: entries out of range are
+    skipped.  Enqueued on the ctx stream, not synchronised (ctx.sync() before reading); whatever
+    filled the arrays must have finished (see Dataset.dense_device)."""
+    metric_flag = _metric_flag(metric)
+    ds = _refine_data(data)
+    check(lib().rpt_graph_search_dev(ds.ctx._h, ds._h, queries._h, int(kg), C.c_void_p(gids_ptr),
+                                     C.c_void_p(gcount_ptr), int(s), C.c_void_p(seeds_ptr), int(k), int(ef),
+                                     metric_flag, 0, C.c_void_p(ids_ptr), C.c_void_p(dist_ptr),
+                                     C.c_void_p(count_ptr)))
+
+
+def graphSearchLast(ctx=None):
+    """(expansions, evaluated) of the last graphSearch call on ctx (rpt_graph_search_last;
+    synchronises): beam entries expanded and distances computed, summed over the queries."""
+    ctx = ctx or default_context()
+    a, b = C.c_int64(), C.c_int64()
+    check(lib().rpt_graph_search_last(ctx._h, C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
 
 
 def knn_last_uncertified(ctx=None):
