@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, graphSearchHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, graphSearchHIP, graphPrepareHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -54,6 +54,7 @@ foreign import ccall safe "rpt_knn_graph_refine_host" c_knn_graph_refine_host ::
 foreign import ccall safe "rpt_knn_graph_metric_host" c_knn_graph_metric_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_refine_metric_host" c_knn_graph_refine_metric_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_host" c_graph_search_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_graph_prepare_host" c_graph_prepare_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
 -- multi-GPU (csrc/comm.hip on librccl): one process drives n devices; per-device arguments are
 -- arrays with one entry per device (Foreign.Marshal.Array.withArray)
@@ -307,6 +308,25 @@ graphSearchHIP ctx ds qs m nq kg (gids, gcount) s seeds k ef = do
   VS.unsafeWith gids (\pg -> VS.unsafeWith gcount (\pc -> VS.unsafeWith seeds (\ps ->
     VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
       c_graph_search_host ctx ds qs (fromIntegral kg) pg pc (fromIntegral s) ps (fromIntegral k) (fromIntegral ef) (metricFlag m) 0 a b)))))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | A kNN graph made ready for 'graphSearchHIP' (rpt_graph_prepare_host), PyNNDescent's search graph.
+-- @diversify@: walking a row in stored order, a neighbour is dropped when an already kept neighbour
+-- of the row is nearer to it than the point itself is (a plain <; the pair distance is the metric's
+-- left fold in Double, bit-exact).  @reverse@: every point that lists i after that joins row i at the
+-- distance stored there.  Row i of the answer is the first @kout@ of that set by (distance, id),
+-- unused slots id -1, distance +Infinity.  The metric must be the one the graph was built under;
+-- under 'MetricInner', which is no metric, @diversify@ costs recall.  The input vectors are not
+-- modified.  k and kout <= 64; n = number of stored points.
+graphPrepareHIP :: Ptr Ctx -> Ptr Dataset -> Metric -> Int -> Int -> Int -> Bool -> Bool
+                -> (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+                -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+graphPrepareHIP ctx ds m n k kout diversify reverse (i0, d0, c0) = do
+  ids <- VSM.new (n * kout); dist <- VSM.new (n * kout); cnt <- VSM.new n
+  let flags = (if diversify then 1 else 0) + (if reverse then 2 else 0)
+  VS.unsafeWith i0 (\pi -> VS.unsafeWith d0 (\pd -> VS.unsafeWith c0 (\pc ->
+    VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
+      c_graph_prepare_host ctx ds (fromIntegral k) pi pd pc (fromIntegral kout) (metricFlag m) flags a b)))))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | SVector rows as a CSR dataset on the device (rpt_dataset_csr_host), for the extent of the

@@ -555,6 +555,69 @@ int32_t rpt_graph_search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_d
                               int32_t* count_host);
 int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
 
+/* ---- prepare the kNN graph for the search: diversify, reverse union, degree cap ----
+ * What PyNNDescent does between building a graph and searching it.  Input: the dense data set `data`
+ * (f64, f32 or bf16 rows), a graph ids[n][k], dist[n][k], count[n] in rpt_knn_graph_*'s layout (k in
+ * [1, RPT_GRAPH_MAX_K]), kout in [1, RPT_GRAPH_MAX_K], `metric`: 0 (L2), RPT_KNN_METRIC_COSINE or
+ * RPT_KNN_METRIC_INNER, and `flags`: an or of RPT_GRAPH_PREP_DIVERSIFY and RPT_GRAPH_PREP_REVERSE.
+ * Output: a second graph out_ids[n][kout], out_dist[n][kout], out_count[n]; the input arrays are
+ * const and are never written.  For a point i:
+ *   Kept(i)   without DIVERSIFY: the valid entries of row i.  With DIVERSIFY: walk row i in stored
+ *             order e_0, e_1, ...; e_m is kept unless some ALREADY KEPT e_l (l < m) has
+ *             dist(e_l, e_m) < the distance stored with e_m in row i ("e_l occludes e_m").  A plain
+ *             <: a comparison with NaN is false, so NaN keeps; ids do not break ties, an equal
+ *             distance does not occlude.  e_0 is always kept.
+ *   dist(e_l, e_m)  the fold of rpt_knn_graph_metric_*: a left fold in double over ascending
+ *             columns, elements widened exactly, every operation rounded on its own, no FMA, the
+ *             cached dot(x, x) of the rows for cosine.  It is symmetric bit for bit, so each
+ *             unordered pair of a row is evaluated once.  The metric must be the one the stored
+ *             distances were computed under (not detected).
+ *   Union(i)  without REVERSE: Kept(i).  With REVERSE: Kept(i) u {j : i in Kept(j)}, a SET.  A
+ *             reverse entry j carries the distance stored with i in row j; if j is in Kept(i) too,
+ *             the distance stored in row i wins (this only matters for an inconsistent input).
+ *   row i of the output   the first kout of Union(i) by (distance, id), NaN behind every number,
+ *             NaNs among themselves by id; out_count[i] = min(kout, |Union(i)|); unused slots hold
+ *             id -1 and distance +inf.
+ * Consequences.  A duplicate of a kept neighbour (another id, an equal row) is dropped: it lies at
+ * distance 0 from it.  Duplicates of x_i itself (stored distance 0) are all kept: nothing is below
+ * 0.  A zero row under cosine is NaN against everything, so it is never occluded and never
+ * occludes.  flags = 0 with kout = k reproduces a graph with sorted rows bit for bit.  The output of
+ * DIVERSIFY alone is a valid input again (PyNNDescent's second pass is a second call).  With
+ * REVERSE and kout >= every |Union(i)| the output is symmetric: j in row i <=> i in row j.
+ * The two steps are separate switches on purpose: the occlusion rule assumes a metric.  Under the
+ * inner product, which is none, DIVERSIFY costs recall and is not recommended; REVERSE still helps.
+ * The result is a pure function of the inputs, the same bits on every call, whatever the launch
+ * shape: one wave owns a row, no atomics touch a list.  The reverse lists are built with atomics
+ * (as the refinement's), so the order inside one depends on arrival; the answer is the first kout
+ * of a set under a total order and does not.
+ * rpt_graph_prepare_last (synchronises the stream), three sums over i of the last call on ctx:
+ *   pairs     c_i (c_i - 1) / 2 with DIVERSIFY, c_i the valid entries of row i, else 0: the
+ *             distances evaluated, every pair of a row once
+ *   occluded  c_i - |Kept(i)|
+ *   capped    |Union(i)| - out_count[i]
+ * Errors: k or kout outside [1, RPT_GRAPH_MAX_K], other flag bits, any other `metric` value, both
+ * metric bits together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG.  CSR data: RPT_E_UNSUPPORTED.  Scratch
+ * (the kept graph and the reverse lists: about 24 k + 20 bytes per point) comes from the context's
+ * pool: RPT_E_NOMEM.  n = 0 and n = 1 are valid.  A refused call writes nothing and leaves the
+ * statistics as they were.
+ * _host checks the graph BEFORE anything is uploaded, with the checks and messages of
+ * rpt_knn_graph_refine_host (count in [0, k], ids in [0, n), id != i, no id twice in a row;
+ * RPT_E_ARG naming the row); it synchronises.  _dev borrows device arrays, enqueues on the ctx
+ * stream, does not synchronise (rpt_ctx_sync before reading) and does NOT validate: a count is
+ * clamped to [0, k] and an id outside [0, n) is skipped, as if the entry were not in the row.  Timed
+ * under rpt_prof_* class 3.  A call leaves rpt_knn_last_* and the forests' ranking tiers untouched. */
+#define RPT_GRAPH_PREP_DIVERSIFY 1
+#define RPT_GRAPH_PREP_REVERSE 2
+int32_t rpt_graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
+                              const double* dist_dev, const int32_t* count_dev, int32_t kout,
+                              int32_t metric, int32_t flags, int32_t* out_ids_dev, double* out_dist_dev,
+                              int32_t* out_count_dev);
+int32_t rpt_graph_prepare_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_host,
+                               const double* dist_host, const int32_t* count_host, int32_t kout,
+                               int32_t metric, int32_t flags, int32_t* out_ids_host, double* out_dist_host,
+                               int32_t* out_count_host);
+int32_t rpt_graph_prepare_last(rpt_ctx* ctx, int64_t* pairs, int64_t* occluded, int64_t* capped);
+
 /* multi-GPU merge: G per-shard results (shard g holds trees [g*T/G, (g+1)*T/G)), gathered
  * shard-major as ids_dev[G][nq][k] etc. (e.g. by an RCCL all-gather), merged into the
  * global top-k with the reference's stable order (shard ascending = tree ascending).

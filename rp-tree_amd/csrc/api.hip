@@ -365,6 +365,7 @@ int32_t rpt_ctx_destroy(rpt_ctx* ctx) {
     if (ctx->metric_unc_dev) dev_free(ctx->metric_unc_dev);
     if (ctx->refine_state_dev) dev_free(ctx->refine_state_dev);
     if (ctx->search_state_dev) dev_free(ctx->search_state_dev);
+    if (ctx->prepare_state_dev) dev_free(ctx->prepare_state_dev);
     dev_trim();
     delete ctx;
     return RPT_OK;
@@ -1247,6 +1248,29 @@ int32_t check_refine(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t r
   RPT_ARG(data->n <= 0x7fffffff, "graph too large");
   return RPT_OK;
 }
+
+// the graph a _host entry point is given (rpt_knn_graph_refine_*, rpt_graph_prepare_*), checked
+// before anything is uploaded: the kernels follow its ids
+int32_t check_graph_rows(int64_t n, int32_t k, const int32_t* ids_host, const int32_t* count_host) {
+  std::vector<int32_t> seen((size_t)n, -1);  // seen[id] = the last row that held id
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t c = count_host[i];
+    if (c < 0 || c > k)
+      return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": count " + std::to_string(c) +
+                                 " outside [0, k]");
+    for (int32_t s = 0; s < c; ++s) {
+      const int32_t id = ids_host[i * k + s];
+      if (id < 0 || id >= n)
+        return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": id " + std::to_string(id) +
+                                   " outside [0, n)");
+      if (id == i) return fail(RPT_E_ARG, "graph row " + std::to_string(i) + " holds its own id");
+      if (seen[id] == (int32_t)i)
+        return fail(RPT_E_ARG, "graph row " + std::to_string(i) + " holds id " + std::to_string(id) + " twice");
+      seen[id] = (int32_t)i;
+    }
+  }
+  return RPT_OK;
+}
 }  // namespace
 
 namespace {
@@ -1270,24 +1294,7 @@ int32_t refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t re
     RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags));
     const int64_t n = data->n;
     RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
-    // the graph is checked here, before anything is uploaded: the kernels follow its ids
-    std::vector<int32_t> seen((size_t)n, -1);  // seen[id] = the last row that held id
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t c = count_host[i];
-      if (c < 0 || c > k)
-        return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": count " + std::to_string(c) +
-                                   " outside [0, k]");
-      for (int32_t s = 0; s < c; ++s) {
-        const int32_t id = ids_host[i * k + s];
-        if (id < 0 || id >= n)
-          return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": id " + std::to_string(id) +
-                                     " outside [0, n)");
-        if (id == i) return fail(RPT_E_ARG, "graph row " + std::to_string(i) + " holds its own id");
-        if (seen[id] == (int32_t)i)
-          return fail(RPT_E_ARG, "graph row " + std::to_string(i) + " holds id " + std::to_string(id) + " twice");
-        seen[id] = (int32_t)i;
-      }
-    }
+    RPT_TRY(check_graph_rows(n, k, ids_host, count_host));  // before anything is uploaded
     RPT_HIP(hipSetDevice(ctx->device));
     DevBuf<int32_t> ids, cnt;
     DevBuf<double> dist;
@@ -1454,6 +1461,83 @@ int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evalua
     RPT_ARG(ctx && expansions && evaluated, "NULL argument");
     RPT_HIP(hipSetDevice(ctx->device));
     return graph_search_last(ctx, expansions, evaluated);
+  });
+}
+
+// ---- a kNN graph made ready for the search -------------------------------------------------------
+namespace {
+int32_t check_prepare(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t kout, int32_t metric,
+                      int32_t flags) {
+  RPT_ARG(ctx && data, "NULL argument");
+  RPT_ARG(data->ctx == ctx, "handles belong to another context");
+  RPT_TRY(check_graph_metric(metric));
+  RPT_ARG((flags & ~(RPT_GRAPH_PREP_DIVERSIFY | RPT_GRAPH_PREP_REVERSE)) == 0,
+          "flags must be an or of RPT_GRAPH_PREP_DIVERSIFY and RPT_GRAPH_PREP_REVERSE");
+  if (data->csr) return fail(RPT_E_UNSUPPORTED, "the graph preparation takes dense data only (not CSR rows)");
+  RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
+  RPT_ARG(kout >= 1 && kout <= RPT_GRAPH_MAX_K, "kout must be in [1,64] (RPT_GRAPH_MAX_K)");
+  RPT_ARG(data->n <= 0x7fffffff, "graph too large");
+  return RPT_OK;
+}
+}  // namespace
+
+int32_t rpt_graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
+                              const double* dist_dev, const int32_t* count_dev, int32_t kout,
+                              int32_t metric, int32_t flags, int32_t* out_ids_dev, double* out_dist_dev,
+                              int32_t* out_count_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags));
+    RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
+    RPT_ARG(data->n == 0 || (out_ids_dev && out_dist_dev && out_count_dev), "NULL output");
+    RPT_HIP(hipSetDevice(ctx->device));
+    return graph_prepare_dev(ctx, data, k, ids_dev, dist_dev, count_dev, kout, metric, flags, out_ids_dev,
+                             out_dist_dev, out_count_dev);
+  });
+}
+
+int32_t rpt_graph_prepare_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_host,
+                               const double* dist_host, const int32_t* count_host, int32_t kout,
+                               int32_t metric, int32_t flags, int32_t* out_ids_host, double* out_dist_host,
+                               int32_t* out_count_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags));
+    const int64_t n = data->n;
+    RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
+    RPT_ARG(n == 0 || (out_ids_host && out_dist_host && out_count_host), "NULL output");
+    RPT_TRY(check_graph_rows(n, k, ids_host, count_host));  // before anything is uploaded
+    RPT_HIP(hipSetDevice(ctx->device));
+    DevBuf<int32_t> ids, cnt, oids, ocnt;
+    DevBuf<double> dist, odist;
+    RPT_TRY(ids.alloc((size_t)n * k));
+    RPT_TRY(dist.alloc((size_t)n * k));
+    RPT_TRY(cnt.alloc((size_t)n));
+    RPT_TRY(oids.alloc((size_t)n * kout));
+    RPT_TRY(odist.alloc((size_t)n * kout));
+    RPT_TRY(ocnt.alloc((size_t)n));
+    if (n) {
+      RPT_HIP(hipMemcpy(ids.p, ids_host, (size_t)n * k * 4, hipMemcpyHostToDevice));
+      RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
+      RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    RPT_TRY(graph_prepare_dev(ctx, data, k, ids.p, dist.p, cnt.p, kout, metric, flags, oids.p, odist.p, ocnt.p));
+    RPT_HIP(stream_sync(ctx->stream));
+    if (n) {
+      RPT_HIP(hipMemcpy(out_ids_host, oids.p, (size_t)n * kout * 4, hipMemcpyDeviceToHost));
+      RPT_HIP(hipMemcpy(out_dist_host, odist.p, (size_t)n * kout * 8, hipMemcpyDeviceToHost));
+      RPT_HIP(hipMemcpy(out_count_host, ocnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    return RPT_OK;
+  });
+}
+
+int32_t rpt_graph_prepare_last(rpt_ctx* ctx, int64_t* pairs, int64_t* occluded, int64_t* capped) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ctx && pairs && occluded && capped, "NULL argument");
+    RPT_HIP(hipSetDevice(ctx->device));
+    return graph_prepare_last(ctx, pairs, occluded, capped);
   });
 }
 

@@ -198,6 +198,7 @@ struct rpt_ctx {
   int64_t last_graph_pairs = 0;  // distances the last rpt_knn_graph_* call evaluated
   void* refine_state_dev = nullptr;  // graph_refine.hip: the last rpt_knn_graph_refine_* call's flag and counters
   void* search_state_dev = nullptr;  // graph_search.hip: the last rpt_graph_search_* call's counters
+  void* prepare_state_dev = nullptr;  // graph_prepare.hip: the last rpt_graph_prepare_* call's counters
   int32_t last_tier = 0;  // ranking tier of the last fused kNN call: 0 exact, 1 f32 shadow, 2 half, 3 int8
   // last build: nodes csub_kernel handed back to the general kernels (pivot codes shared by more
   // points than its pool), and how many of those for a histogram that contradicted the node
@@ -415,6 +416,16 @@ int32_t graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
                          int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
 // synchronises the stream
 int32_t graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
+// ---- a kNN graph made ready for the search (graph_prepare.hip) ---------------------------------
+// arguments checked by the caller (dense data, k and kout <= 64, flags an or of
+// RPT_GRAPH_PREP_DIVERSIFY / _REVERSE; metric as knn_graph_dev's); the input arrays are read only
+// and not validated: entries out of range are skipped; enqueued on the ctx stream
+int32_t graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
+                          const double* dist_dev, const int32_t* count_dev, int32_t kout, int32_t metric,
+                          int32_t flags, int32_t* out_ids_dev, double* out_dist_dev,
+                          int32_t* out_count_dev);
+// synchronises the stream
+int32_t graph_prepare_last(rpt_ctx* ctx, int64_t* pairs, int64_t* occluded, int64_t* capped);
 int32_t knn_h(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
               int32_t k, int64_t* off_host, int32_t* ids_host, double* dist_host, int64_t cap,
               int64_t* total);

@@ -1,9 +1,12 @@
 // graph_dev.h — device helpers shared by graph.hip (the graph, leaf by leaf), graph_refine.hip
 // (its NN-descent rounds) and graph_search.hip (the beam search over it): the chunk geometry, the
 // (distance, id) total order, the exact widening of f32 / bf16 elements, the metric's fold step
-// and epilogue, the one-wave insertion into a sorted list and the one-wave staging of a chunk of
-// rows.  The translation units are built with -ffp-contract=off.
+// and epilogue, the one-wave insertion into a sorted list, the one-wave staging of a chunk of
+// rows and the CSR of a graph's reverse edges (graph_prepare.hip takes these too).  The
+// translation units are built with -ffp-contract=off.
 #pragma once
+
+#include <algorithm>
 
 #include "common.h"
 
@@ -165,6 +168,89 @@ __device__ inline void wave_stage(const TD* __restrict__ X, int d, const int* si
       const int r = p / cw, c = p - r * cw;
       buf[r * kLS + c] = widen(X[(size_t)sid[r] * d + c0 + c]);
     }
+  }
+}
+
+// ---- the reverse edges of a graph as a CSR, shared by the refinement (graph_refine.hip, per round)
+// and the preparation (graph_prepare.hip): zero, in-degrees (vector atomics), an exclusive scan by one
+// workgroup, fill.  The position inside a target's segment comes from an atomic cursor, so the ORDER
+// of a segment depends on arrival; both readers take a set or the first entries under a total order
+// from it, so their answers do not.  `active`: a device-side flag, 0 = return at once.
+constexpr int kScanThreads = 1024;
+
+__global__ void rev_zero_kernel(const int32_t* active, int64_t n, int32_t* __restrict__ deg,
+                                   int32_t* __restrict__ cur) {
+  if (!*active) return;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    deg[i] = 0;
+    cur[i] = 0;
+  }
+}
+
+// edge e = (row j, slot s) of the graph: valid when s < count[j] and its target is a row
+__device__ inline bool edge_of(int64_t e, int64_t n, int k, const int32_t* ids, const int32_t* count,
+                               int64_t& j, int& t) {
+  j = e / k;
+  const int s = (int)(e - j * k);
+  if (s >= count[j]) return false;
+  t = ids[e];
+  return (unsigned)t < (unsigned long long)n;
+}
+
+__global__ void rev_degree_kernel(const int32_t* active, int64_t n, int k,
+                                     const int32_t* __restrict__ ids,
+                                     const int32_t* __restrict__ count, int32_t* deg) {
+  if (!*active) return;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n * k; e += stride) {
+    int64_t j;
+    int t;
+    if (edge_of(e, n, k, ids, count, j, t)) atomicAdd(&deg[t], 1);
+  }
+}
+
+// off[0 .. n] = exclusive scan of deg[0 .. n): one workgroup, a contiguous run of rows per thread
+__global__ __launch_bounds__(kScanThreads) void rev_scan_kernel(const int32_t* active, int64_t n,
+                                                                   const int32_t* __restrict__ deg,
+                                                                   int64_t* __restrict__ off) {
+  if (!*active) return;
+  __shared__ int64_t part[kScanThreads];
+  const int tid = threadIdx.x;
+  const int64_t per = (n + kScanThreads - 1) / kScanThreads;
+  const int64_t lo = std::min<int64_t>(n, per * tid), hi = std::min<int64_t>(n, lo + per);
+  int64_t s = 0;
+  for (int64_t i = lo; i < hi; ++i) s += deg[i];
+  part[tid] = s;
+  __syncthreads();
+  for (int step = 1; step < kScanThreads; step <<= 1) {  // inclusive scan of the partial sums
+    const int64_t add = tid >= step ? part[tid - step] : 0;
+    __syncthreads();
+    part[tid] += add;
+    __syncthreads();
+  }
+  int64_t run = part[tid] - s;
+  for (int64_t i = lo; i < hi; ++i) {
+    off[i] = run;
+    run += deg[i];
+  }
+  if (tid == kScanThreads - 1) off[n] = part[tid];
+}
+
+__global__ void rev_fill_kernel(const int32_t* active, int64_t n, int k,
+                                   const int32_t* __restrict__ ids, const double* __restrict__ dist,
+                                   const int32_t* __restrict__ count, const int64_t* __restrict__ off,
+                                   int32_t* cur, int32_t* __restrict__ rsrc,
+                                   double* __restrict__ rdist) {
+  if (!*active) return;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n * k; e += stride) {
+    int64_t j;
+    int t;
+    if (!edge_of(e, n, k, ids, count, j, t)) continue;
+    const int64_t p = off[t] + atomicAdd(&cur[t], 1);
+    rsrc[p] = (int32_t)j;
+    rdist[p] = dist[e];
   }
 }
 

@@ -9,10 +9,10 @@
 // no row and every kernel of the later rounds exits at once on it.
 //
 // Kernels of a round, in stream order:
-//   refine_zero_kernel     in-degrees and fill cursors to 0                          (reverse > 0)
-//   refine_degree_kernel   in-degree of every target, vector atomics                 (reverse > 0)
-//   refine_scan_kernel     exclusive scan of the in-degrees, one workgroup           (reverse > 0)
-//   refine_fill_kernel     (source, stored distance) of every edge into its target's segment; the
+//   rev_zero_kernel        in-degrees and fill cursors to 0                          (reverse > 0)
+//   rev_degree_kernel      in-degree of every target, vector atomics                 (reverse > 0)
+//   rev_scan_kernel        exclusive scan of the in-degrees, one workgroup           (reverse > 0)
+//   rev_fill_kernel        (source, stored distance) of every edge into its target's segment; the
 //                          position inside a segment comes from an atomic cursor, so the ORDER of a
 //                          segment depends on arrival — the join takes the first r of a segment by
 //                          (stored distance, source), a total order, so Rev_r(i) does not
@@ -41,7 +41,6 @@ namespace {
 constexpr int kEmpty = (int)0x80000000;  // free slot of the hash set; a member c is stored as c
                                          // (new) or ~c (i itself and F(i): never a candidate)
 constexpr int kLdsMax = 160 * 1024;
-constexpr int kScanThreads = 1024;
 
 struct RefineState {
   int32_t active;  // 0: an earlier round changed no row, the kernels of this round return at once
@@ -66,82 +65,6 @@ __global__ void refine_end_kernel(RefineState* st) {
     st->rounds += 1;
     if (st->changed == 0) st->active = 0;
     st->changed = 0;
-  }
-}
-
-__global__ void refine_zero_kernel(const RefineState* st, int64_t n, int32_t* __restrict__ deg,
-                                   int32_t* __restrict__ cur) {
-  if (!st->active) return;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    deg[i] = 0;
-    cur[i] = 0;
-  }
-}
-
-// edge e = (row j, slot s) of the graph: valid when s < count[j] and its target is a row
-__device__ inline bool edge_of(int64_t e, int64_t n, int k, const int32_t* ids, const int32_t* count,
-                               int64_t& j, int& t) {
-  j = e / k;
-  const int s = (int)(e - j * k);
-  if (s >= count[j]) return false;
-  t = ids[e];
-  return (unsigned)t < (unsigned long long)n;
-}
-
-__global__ void refine_degree_kernel(const RefineState* st, int64_t n, int k,
-                                     const int32_t* __restrict__ ids,
-                                     const int32_t* __restrict__ count, int32_t* deg) {
-  if (!st->active) return;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n * k; e += stride) {
-    int64_t j;
-    int t;
-    if (edge_of(e, n, k, ids, count, j, t)) atomicAdd(&deg[t], 1);
-  }
-}
-
-// off[0 .. n] = exclusive scan of deg[0 .. n): one workgroup, a contiguous run of rows per thread
-__global__ __launch_bounds__(kScanThreads) void refine_scan_kernel(const RefineState* st, int64_t n,
-                                                                   const int32_t* __restrict__ deg,
-                                                                   int64_t* __restrict__ off) {
-  if (!st->active) return;
-  __shared__ int64_t part[kScanThreads];
-  const int tid = threadIdx.x;
-  const int64_t per = (n + kScanThreads - 1) / kScanThreads;
-  const int64_t lo = std::min<int64_t>(n, per * tid), hi = std::min<int64_t>(n, lo + per);
-  int64_t s = 0;
-  for (int64_t i = lo; i < hi; ++i) s += deg[i];
-  part[tid] = s;
-  __syncthreads();
-  for (int step = 1; step < kScanThreads; step <<= 1) {  // inclusive scan of the partial sums
-    const int64_t add = tid >= step ? part[tid - step] : 0;
-    __syncthreads();
-    part[tid] += add;
-    __syncthreads();
-  }
-  int64_t run = part[tid] - s;
-  for (int64_t i = lo; i < hi; ++i) {
-    off[i] = run;
-    run += deg[i];
-  }
-  if (tid == kScanThreads - 1) off[n] = part[tid];
-}
-
-__global__ void refine_fill_kernel(const RefineState* st, int64_t n, int k,
-                                   const int32_t* __restrict__ ids, const double* __restrict__ dist,
-                                   const int32_t* __restrict__ count, const int64_t* __restrict__ off,
-                                   int32_t* cur, int32_t* __restrict__ rsrc,
-                                   double* __restrict__ rdist) {
-  if (!st->active) return;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n * k; e += stride) {
-    int64_t j;
-    int t;
-    if (!edge_of(e, n, k, ids, count, j, t)) continue;
-    const int64_t p = off[t] + atomicAdd(&cur[t], 1);
-    rsrc[p] = (int32_t)j;
-    rdist[p] = dist[e];
   }
 }
 
@@ -369,12 +292,12 @@ int32_t knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, i
   for (int32_t it = 0; it < iters; ++it) {
     if (n > 0) {
       if (r > 0) {
-        hipLaunchKernelGGL(refine_zero_kernel, dim3(grid_n), dim3(256), 0, ctx->stream, st, n, deg.p, cur.p);
-        hipLaunchKernelGGL(refine_degree_kernel, dim3(grid_e), dim3(256), 0, ctx->stream, st, n, k, ids_dev,
+        hipLaunchKernelGGL(rev_zero_kernel, dim3(grid_n), dim3(256), 0, ctx->stream, &st->active, n, deg.p, cur.p);
+        hipLaunchKernelGGL(rev_degree_kernel, dim3(grid_e), dim3(256), 0, ctx->stream, &st->active, n, k, ids_dev,
                            count_dev, deg.p);
-        hipLaunchKernelGGL(refine_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, st, n, deg.p,
+        hipLaunchKernelGGL(rev_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, &st->active, n, deg.p,
                            roff.p);
-        hipLaunchKernelGGL(refine_fill_kernel, dim3(grid_e), dim3(256), 0, ctx->stream, st, n, k, ids_dev,
+        hipLaunchKernelGGL(rev_fill_kernel, dim3(grid_e), dim3(256), 0, ctx->stream, &st->active, n, k, ids_dev,
                            dist_dev, count_dev, roff.p, cur.p, rsrc.p, rdist.p);
       }
       switch (data->dtype) {

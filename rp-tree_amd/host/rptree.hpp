@@ -427,6 +427,47 @@ inline GraphResult knnGraphRefine(Context& ctx, const Dataset& data, const Graph
   return out;
 }
 
+// A kNN graph made ready for graphSearch (rpt_graph_prepare_host) -> a graph of kout columns; `g`
+// is not modified.  diversify: walking a row in stored order, a neighbour is dropped when an
+// already kept neighbour of the row is nearer to it than the point itself is (a plain <, the
+// metric's fold bit for bit); reverse: every point that lists i after that joins row i at the
+// distance stored there; the row is the first kout (-1 = min(64, 2 k)) of that set by (distance,
+// id).  The metric must be the one the graph was built under; under Metric::Inner, which is no
+// metric, diversify costs recall.  stats (optional): pair distances evaluated, entries dropped by
+// diversify, entries cut off by kout (rpt_graph_prepare_last).
+struct PrepareStats {
+  int64_t pairs = 0, occluded = 0, capped = 0;
+};
+inline GraphResult graphPrepare(Context& ctx, const Dataset& data, const GraphResult& g, Metric metric,
+                                int kout = -1, bool diversify = true, bool reverse = true,
+                                PrepareStats* stats = nullptr) {
+  const size_t n = (size_t)data.n;
+  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0) || g.dist.size() != g.ids.size())
+    throw RPTError(RPT_E_ARG, "graphPrepare: a graph of another data set or k");
+  if (kout < 0) kout = 2 * g.k < RPT_GRAPH_MAX_K ? 2 * g.k : RPT_GRAPH_MAX_K;
+  if (kout < 1 || kout > RPT_GRAPH_MAX_K) throw RPTError(RPT_E_ARG, "graphPrepare: kout must be in [1,64]");
+  const int32_t none = -1;  // non-NULL pointers for an empty data set
+  const double nod = 0.0;
+  GraphResult out;
+  out.k = kout;
+  out.ids.resize(n * (size_t)kout + 1);
+  out.dist.resize(n * (size_t)kout + 1);
+  out.count.resize(n + 1);
+  check(rpt_graph_prepare_host(ctx.get(), data.get(), g.k, n ? g.ids.data() : &none, n ? g.dist.data() : &nod,
+                               n ? g.count.data() : &none, kout, metric_flags(metric),
+                               (diversify ? RPT_GRAPH_PREP_DIVERSIFY : 0) | (reverse ? RPT_GRAPH_PREP_REVERSE : 0),
+                               out.ids.data(), out.dist.data(), out.count.data()));
+  out.ids.resize(n * (size_t)kout);
+  out.dist.resize(n * (size_t)kout);
+  out.count.resize(n);
+  if (stats) check(rpt_graph_prepare_last(ctx.get(), &stats->pairs, &stats->occluded, &stats->capped));
+  return out;
+}
+inline GraphResult graphPrepare(Context& ctx, const Dataset& data, const GraphResult& g, int kout = -1,
+                                bool diversify = true, bool reverse = true, PrepareStats* stats = nullptr) {
+  return graphPrepare(ctx, data, g, Metric::L2, kout, diversify, reverse, stats);
+}
+
 // Query a kNN graph: best-first beam search (rpt_graph_search_host).  g: a graph over `data`
 // (knnGraph's, knnGraphRefine's; only ids and count are read), qs: dense queries of the data's d,
 // seeds: [nq][s] start ids (s <= 64, -1 = unused slot), ef: entries of the beam (k <= ef <= 256).

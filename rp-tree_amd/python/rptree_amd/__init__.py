@@ -23,6 +23,7 @@ import numpy as np
 
 from . import gen
 from ._lib import (RPT_BF16, RPT_F32, RPT_F64, RPT_GRAPH_ACCUMULATE, RPT_GRAPH_MAX_K, RPT_GRAPH_SEARCH_MAX_EF,
+                   RPT_GRAPH_PREP_DIVERSIFY, RPT_GRAPH_PREP_REVERSE,
                    RPT_KNN_DEDUP, RPT_KNN_DEDUP_DISTANCE,
                    RPT_KNN_KEEP_DUPLICATES, RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER,
                    RPT_KNN_METRIC_REFERENCE,
@@ -40,6 +41,7 @@ __all__ = [
     "knnGraphRefine", "knnGraphRefineDev", "knnGraphRefineLast",
     "knnGraphMetric", "knnGraphMetricDev", "knnGraphRefineMetric", "knnGraphRefineMetricDev",
     "graphSearch", "graphSearchDev", "graphSearchLast",
+    "graphPrepare", "graphPrepareDev", "graphPrepareLast",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -990,6 +992,68 @@ def graphSearchLast(ctx=None):
     a, b = C.c_int64(), C.c_int64()
     check(lib().rpt_graph_search_last(ctx._h, C.byref(a), C.byref(b)))
     return int(a.value), int(b.value)
+
+
+def _prepare_flags(diversify, reverse):
+    return (RPT_GRAPH_PREP_DIVERSIFY if diversify else 0) | (RPT_GRAPH_PREP_REVERSE if reverse else 0)
+
+
+def graphPrepare(graph, data, kout=None, diversify=True, reverse=True, metric=None, ctx=None):
+    """A kNN graph made ready for graphSearch (rpt_graph_prepare_host) -> new (ids[n][kout],
+    dist[n][kout], count[n]); the input tuple is not modified.  graph: (ids[n][k], dist[n][k],
+    count[n]) over `data`, e.g. knnGraph's or knnGraphRefine's; data: a dense Dataset, or a forest
+    (its .data is used).  diversify: walking a row in stored order, a neighbour is dropped when an
+    already kept neighbour of the row is nearer to it than the point itself is (a plain <; the pair
+    distance is metric's fold, bit for bit).  reverse: every point that lists i after that joins row
+    i, at the distance stored there.  The row is the first kout (None = min(64, 2 k)) of that set by
+    (distance, id); unused slots are id -1, distance +inf.  metric: None / metricL2, metricCosine or
+    metricInner, the one the graph was built under.  Under metricInner, which is no metric,
+    diversify costs recall: pass diversify=False there.  Deterministic; k and kout <= 64."""
+    metric_flag = _metric_flag(metric)
+    ds = _refine_data(data)
+    ctx = ctx or ds.ctx
+    ids = np.ascontiguousarray(graph[0], dtype=np.int32)
+    dist = np.ascontiguousarray(graph[1], dtype=np.float64)
+    cnt = np.ascontiguousarray(graph[2], dtype=np.int32)
+    if ids.ndim != 2 or ids.shape[0] != ds.n or dist.shape != ids.shape or cnt.shape != (ds.n,):
+        raise ValueError("graph must be (ids[n][k], dist[n][k], count[n]) over the data set's n rows")
+    k = ids.shape[1]
+    if kout is None:
+        kout = min(RPT_GRAPH_MAX_K, 2 * k)
+    kout = int(kout)
+    if kout < 1 or kout > RPT_GRAPH_MAX_K:   # before the outputs are sized by it
+        raise ValueError("kout must be in [1,64]")
+    oids = np.empty((ds.n, kout), dtype=np.int32)
+    odist = np.empty((ds.n, kout), dtype=np.float64)
+    ocnt = np.empty(ds.n, dtype=np.int32)
+    check(lib().rpt_graph_prepare_host(ctx._h, ds._h, int(k), _vp(ids), _vp(dist), _vp(cnt), kout, metric_flag,
+                                       _prepare_flags(diversify, reverse), _vp(oids), _vp(odist), _vp(ocnt)))
+    return oids, odist, ocnt
+
+
+def graphPrepareDev(k, data, ids_ptr, dist_ptr, count_ptr, kout, out_ids_ptr, out_dist_ptr, out_count_ptr,
+                    diversify=True, reverse=True, metric=None):
+    """graphPrepare on device arrays (rpt_graph_prepare_dev): the graph (int32 [n][k], float64 [n][k],
+    int32 [n]; read only) and the outputs (int32 [n][kout], float64 [n][kout], int32 [n]) given as
+    device addresses.  The arrays are NOT validated: a count is clamped to [0, k], an id outside
+    [0, n) is skipped.  Enqueued on the ctx stream, not synchronised (ctx.sync() before reading);
+    whatever filled the arrays must have finished (see Dataset.dense_device)."""
+    metric_flag = _metric_flag(metric)
+    ds = _refine_data(data)
+    check(lib().rpt_graph_prepare_dev(ds.ctx._h, ds._h, int(k), C.c_void_p(ids_ptr), C.c_void_p(dist_ptr),
+                                      C.c_void_p(count_ptr), int(kout), metric_flag,
+                                      _prepare_flags(diversify, reverse), C.c_void_p(out_ids_ptr),
+                                      C.c_void_p(out_dist_ptr), C.c_void_p(out_count_ptr)))
+
+
+def graphPrepareLast(ctx=None):
+    """(pairs, occluded, capped) of the last graphPrepare call on ctx (rpt_graph_prepare_last;
+    synchronises): pair distances evaluated by diversify, entries it dropped, entries of the unions
+    that the cap kout cut off, summed over the rows."""
+    ctx = ctx or default_context()
+    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().rpt_graph_prepare_last(ctx._h, C.byref(a), C.byref(b), C.byref(c)))
+    return int(a.value), int(b.value), int(c.value)
 
 
 def knn_last_uncertified(ctx=None):

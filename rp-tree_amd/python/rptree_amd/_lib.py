@@ -19,6 +19,8 @@ RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER = 1 << 25, 1 << 26
 RPT_GRAPH_ACCUMULATE = 1
 RPT_GRAPH_MAX_K = 64
 RPT_GRAPH_SEARCH_MAX_EF = 256
+RPT_GRAPH_PREP_DIVERSIFY = 1
+RPT_GRAPH_PREP_REVERSE = 2
 RPT_COMM_UID_BYTES = 128
 
 i32, i64, f64 = C.c_int32, C.c_int64, C.c_double
@@ -84,6 +86,9 @@ SYMBOLS = {
     "rpt_graph_search_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_last": (i32, [vp, p_i64, p_i64]),
+    "rpt_graph_prepare_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rpt_graph_prepare_host": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rpt_graph_prepare_last": (i32, [vp, p_i64, p_i64, p_i64]),
     "rpt_knn_merge_dev": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp]),
     "rpt_knn_record_layout": (i32, [i64, i32, vp, vp, vp, vp]),
     "rpt_knn_merge_records_dev": (i32, [vp, vp, i64, i32, i64, i32, i32, vp, vp, vp]),
