@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, graphSearchHIP, graphPrepareHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, graphSearchHIP, graphPrepareHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -53,6 +53,8 @@ foreign import ccall safe "rpt_knn_graph_host"      c_knn_graph_host :: Ptr Ctx 
 foreign import ccall safe "rpt_knn_graph_refine_host" c_knn_graph_refine_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_metric_host" c_knn_graph_metric_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_refine_metric_host" c_knn_graph_refine_metric_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_graph_csr_host" c_knn_graph_csr_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_graph_refine_csr_host" c_knn_graph_refine_csr_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_host" c_graph_search_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_host" c_graph_prepare_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
@@ -264,6 +266,32 @@ knnGraphRefineHIP ctx ds _n k reverse iters (i0, d0, c0) = do
   dist <- VS.thaw d0
   cnt <- VS.thaw c0
   VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_refine_host ctx ds (fromIntegral k) (fromIntegral reverse) (fromIntegral iters) 0 a b))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | 'knnGraphHIP' for a forest over SVector rows ('withDeviceDataSV'; rpt_knn_graph_csr_host).  The
+-- distance is metricDDL2's left fold over the dense-ified rows (absent entries +0.0), so the answer
+-- is bit-equal to 'knnGraphHIP' on the dense-ified data set with the same forest; the kernels visit
+-- only the 32-column windows in which a leaf holds a nonzero.  Indices must ascend strictly.
+knnGraphSVHIP :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int -> Int
+              -> Maybe (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+              -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnGraphSVHIP ctx f ds n k earlier = do
+  (ids, dist, cnt, flags) <- case earlier of
+    Nothing -> (,,,) <$> VSM.new (n * k) <*> VSM.new (n * k) <*> VSM.new n <*> pure 0
+    Just (i0, d0, c0) -> (,,,) <$> VS.thaw i0 <*> VS.thaw d0 <*> VS.thaw c0 <*> pure 1
+  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_csr_host ctx f ds (fromIntegral k) flags a b))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | 'knnGraphRefineHIP' over SVector rows (rpt_knn_graph_refine_csr_host): the same rounds, bit-equal
+-- to 'knnGraphRefineHIP' on the dense-ified data set.
+knnGraphRefineSVHIP :: Ptr Ctx -> Ptr Dataset -> Int -> Int -> Int -> Int
+                    -> (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+                    -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnGraphRefineSVHIP ctx ds _n k reverse iters (i0, d0, c0) = do
+  ids <- VS.thaw i0
+  dist <- VS.thaw d0
+  cnt <- VS.thaw c0
+  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_refine_csr_host ctx ds (fromIntegral k) (fromIntegral reverse) (fromIntegral iters) 0 a b))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | 'knnGraphHIP' under another distance (rpt_knn_graph_metric_host): 'MetricCosine' / 'MetricInner'

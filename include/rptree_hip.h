@@ -496,6 +496,49 @@ int32_t rpt_knn_graph_refine_metric_host(rpt_ctx* ctx, const rpt_dataset* data, 
                                          int32_t reverse, int32_t iters, int32_t metric, int32_t flags,
                                          int32_t* ids_host, double* dist_host, int32_t* count_host);
 
+/* ---- the kNN graph and its NN-descent rounds on SVector (CSR) rows, under L2 ----
+ * rpt_knn_graph_csr_* and rpt_knn_graph_refine_csr_* are rpt_knn_graph_* and rpt_knn_graph_refine_*
+ * for a CSR data set (rpt_dataset_csr_*, f64 or f32 values); `f` is a batch forest over it.  Let
+ * dense(x) be the row of d doubles that a CSR row stands for: absent columns are +0.0, f32 values
+ * are widened exactly, and a stored zero is a zero.  Everything stated for the dense entry points
+ * carries over word for word with dist(i, j) = metricDDL2's left fold over dense(x_i), dense(x_j):
+ * mates(i), the sets F / Rev_r / B / C, the order (distance, id) with NaN behind every number and
+ * NaNs among themselves by id, counts and unused slots (id -1, distance +inf),
+ * RPT_GRAPH_ACCUMULATE, one owner per list and no atomics on a list, a round that changes nothing
+ * ends the sequence, _dev enqueues and does not synchronise / _host validates the graph (the
+ * refinement) and synchronises, the context options graph_general and graph_refine_general,
+ * rpt_knn_graph_last_pairs, rpt_knn_graph_refine_last, rpt_prof_* class 3.
+ *   Bit-equal to the dense entry points  The kernels do not visit all d columns and need not.  A
+ *                column where both rows hold +0.0 contributes acc + (+0.0), which is acc for every
+ *                acc the fold can hold: it starts at +0.0 and, a sum of squares, never becomes
+ *                -0.0.  A pair's fold over any ascending superset of the union of the two supports
+ *                therefore gives the same bits, and the answer is bit-equal to what
+ *                rpt_knn_graph_* / rpt_knn_graph_refine_* give on the dense-ified rows with the same
+ *                perm.  The fold stays symmetric bit for bit: a pair of a leaf is still evaluated
+ *                once.  Two rows without nonzeros are at distance 0.
+ *   Ascending columns  A row's columns must ascend strictly (the SVector invariant;
+ *                rpt_dataset_csr_host checks only col < d).  For rows that break the invariant the
+ *                answer is unspecified, but the kernels stay in bounds and terminate.
+ * There is no limit on a row's length or on d: the leaf kernels stage windows of 32 columns (only
+ * the windows in which the leaf holds a nonzero), the refinement merges a candidate's row against
+ * x_i's, which passes through LDS in pieces of bounded size.
+ * Errors: a dense data set: RPT_E_ARG (the message names rpt_knn_graph_* / rpt_knn_graph_refine_*);
+ * a data set of another shape than the forest's (n, d, dtype), k outside [1, RPT_GRAPH_MAX_K],
+ * reverse outside [0, RPT_GRAPH_MAX_K], iters < 1, other flag bits: RPT_E_ARG.  A streamed forest,
+ * any RPT_KNN_METRIC_* bit: RPT_E_UNSUPPORTED.  n = 0, n = 1, depth 0 and rows with no nonzeros are
+ * valid. */
+int32_t rpt_knn_graph_csr_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                              int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+int32_t rpt_knn_graph_csr_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                               int32_t flags, int32_t* ids_host, double* dist_host,
+                               int32_t* count_host);
+int32_t rpt_knn_graph_refine_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                     int32_t reverse, int32_t iters, int32_t flags, int32_t* ids_dev,
+                                     double* dist_dev, int32_t* count_dev);
+int32_t rpt_knn_graph_refine_csr_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                      int32_t reverse, int32_t iters, int32_t flags,
+                                      int32_t* ids_host, double* dist_host, int32_t* count_host);
+
 /* ---- query the kNN graph: best-first beam search from given seeds ----
  * Input: the dense data set `data` (n rows of f64, f32 or bf16), the dense `queries` (the same d and
  * element type, as rpt_knn_* requires), a graph over the data set in rpt_knn_graph_*'s layout of

@@ -1140,7 +1140,7 @@ int32_t check_graph_metric(int32_t metric) {
 // rpt_knn_graph_metric_dev
 int32_t graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k, bool has_metric,
                   int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
-                  int32_t* count_dev) {
+                  int32_t* count_dev, bool csr = false) {
   if (ctx) dev_set_stream(ctx->stream);
   RPT_ARG(ctx && f && data, "NULL argument");
   RPT_ARG(f->ctx == ctx && data->ctx == ctx, "handles belong to another context");
@@ -1149,7 +1149,8 @@ int32_t graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t 
   else if (flags > 0 && (flags & (RPT_KNN_METRIC_REFERENCE | RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)))
     return fail(RPT_E_UNSUPPORTED, "the kNN graph is built under metricL2 only (no metric flags)");
   RPT_ARG((flags & ~RPT_GRAPH_ACCUMULATE) == 0, "flags must be 0 or RPT_GRAPH_ACCUMULATE");
-  if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph takes dense data only (not CSR rows)");
+  if (csr) RPT_ARG(data->csr, "rpt_knn_graph_csr_* takes CSR data only (dense rows: rpt_knn_graph_*)");
+  else if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph takes dense data only (not CSR rows)");
   if (f->xtopo)
     return fail(RPT_E_UNSUPPORTED, "the kNN graph takes batch forests only (not a streamed forest)");
   RPT_ARG(data->n == f->n && data->d == f->d && data->dtype == f->dtype,
@@ -1158,12 +1159,13 @@ int32_t graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t 
   RPT_ARG(f->n <= 0x7fffffff, "graph too large");
   RPT_ARG(f->n == 0 || (ids_dev && dist_dev && count_dev), "NULL output");
   RPT_HIP(hipSetDevice(ctx->device));
+  if (csr) return knn_graph_csr_dev(ctx, f, data, k, flags, ids_dev, dist_dev, count_dev);
   return knn_graph_dev(ctx, f, data, k, metric, flags, ids_dev, dist_dev, count_dev);
 }
 
 int32_t graph_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k, bool has_metric,
                    int32_t metric, int32_t flags, int32_t* ids_host, double* dist_host,
-                   int32_t* count_host) {
+                   int32_t* count_host, bool csr = false) {
   if (ctx) dev_set_stream(ctx->stream);
   RPT_ARG(ctx && f && data, "NULL argument");
   RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
@@ -1179,7 +1181,7 @@ int32_t graph_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t
     RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
     RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
   }
-  RPT_TRY(graph_dev(ctx, f, data, k, has_metric, metric, flags, ids.p, dist.p, cnt.p));
+  RPT_TRY(graph_dev(ctx, f, data, k, has_metric, metric, flags, ids.p, dist.p, cnt.p, csr));
   RPT_HIP(stream_sync(ctx->stream));
   if (n) {
     RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
@@ -1221,6 +1223,21 @@ int32_t rpt_knn_graph_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset
   });
 }
 
+int32_t rpt_knn_graph_csr_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                              int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    return graph_dev(ctx, f, data, k, false, 0, flags, ids_dev, dist_dev, count_dev, true);
+  });
+}
+
+int32_t rpt_knn_graph_csr_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                               int32_t flags, int32_t* ids_host, double* dist_host,
+                               int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return graph_host(ctx, f, data, k, false, 0, flags, ids_host, dist_host, count_host, true);
+  });
+}
+
 int32_t rpt_knn_graph_last_pairs(rpt_ctx* ctx, int64_t* pairs) {
   return guarded([&]() -> int32_t {
     RPT_ARG(ctx && pairs, "NULL argument");
@@ -1233,7 +1250,7 @@ int32_t rpt_knn_graph_last_pairs(rpt_ctx* ctx, int64_t* pairs) {
 namespace {
 // has_metric false (rpt_knn_graph_refine_*): the metric bits in flags are refused
 int32_t check_refine(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
-                     int32_t iters, bool has_metric, int32_t metric, int32_t flags) {
+                     int32_t iters, bool has_metric, int32_t metric, int32_t flags, bool csr) {
   RPT_ARG(ctx && data, "NULL argument");
   RPT_ARG(data->ctx == ctx, "handles belong to another context");
   if (has_metric)
@@ -1241,7 +1258,8 @@ int32_t check_refine(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t r
   else if (flags > 0 && (flags & (RPT_KNN_METRIC_REFERENCE | RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)))
     return fail(RPT_E_UNSUPPORTED, "the kNN graph is refined under metricL2 only (no metric flags)");
   RPT_ARG(flags == 0, "flags must be 0");
-  if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph refinement takes dense data only (not CSR rows)");
+  if (csr) RPT_ARG(data->csr, "rpt_knn_graph_refine_csr_* takes CSR data only (dense rows: rpt_knn_graph_refine_*)");
+  else if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph refinement takes dense data only (not CSR rows)");
   RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
   RPT_ARG(reverse >= 0 && reverse <= RPT_GRAPH_MAX_K, "reverse must be in [0,64] (RPT_GRAPH_MAX_K)");
   RPT_ARG(iters >= 1, "iters must be at least 1");
@@ -1276,22 +1294,23 @@ int32_t check_graph_rows(int64_t n, int32_t k, const int32_t* ids_host, const in
 namespace {
 int32_t refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse, int32_t iters,
                    bool has_metric, int32_t metric, int32_t flags, int32_t* ids_dev,
-                   double* dist_dev, int32_t* count_dev) {
+                   double* dist_dev, int32_t* count_dev, bool csr = false) {
   {
     if (ctx) dev_set_stream(ctx->stream);
-    RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags));
+    RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags, csr));
     RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
     RPT_HIP(hipSetDevice(ctx->device));
+    if (csr) return knn_graph_refine_csr_dev(ctx, data, k, reverse, iters, ids_dev, dist_dev, count_dev);
     return knn_graph_refine_dev(ctx, data, k, reverse, iters, metric, ids_dev, dist_dev, count_dev);
   }
 }
 
 int32_t refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse, int32_t iters,
                     bool has_metric, int32_t metric, int32_t flags, int32_t* ids_host,
-                    double* dist_host, int32_t* count_host) {
+                    double* dist_host, int32_t* count_host, bool csr = false) {
   {
     if (ctx) dev_set_stream(ctx->stream);
-    RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags));
+    RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags, csr));
     const int64_t n = data->n;
     RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
     RPT_TRY(check_graph_rows(n, k, ids_host, count_host));  // before anything is uploaded
@@ -1306,7 +1325,8 @@ int32_t refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t re
       RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
       RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
     }
-    RPT_TRY(knn_graph_refine_dev(ctx, data, k, reverse, iters, metric, ids.p, dist.p, cnt.p));
+    if (csr) RPT_TRY(knn_graph_refine_csr_dev(ctx, data, k, reverse, iters, ids.p, dist.p, cnt.p));
+    else RPT_TRY(knn_graph_refine_dev(ctx, data, k, reverse, iters, metric, ids.p, dist.p, cnt.p));
     RPT_HIP(stream_sync(ctx->stream));
     if (n) {
       RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
@@ -1348,6 +1368,22 @@ int32_t rpt_knn_graph_refine_metric_host(rpt_ctx* ctx, const rpt_dataset* data, 
                                          int32_t* ids_host, double* dist_host, int32_t* count_host) {
   return guarded([&]() -> int32_t {
     return refine_host(ctx, data, k, reverse, iters, true, metric, flags, ids_host, dist_host, count_host);
+  });
+}
+
+int32_t rpt_knn_graph_refine_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                     int32_t reverse, int32_t iters, int32_t flags, int32_t* ids_dev,
+                                     double* dist_dev, int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    return refine_dev(ctx, data, k, reverse, iters, false, 0, flags, ids_dev, dist_dev, count_dev, true);
+  });
+}
+
+int32_t rpt_knn_graph_refine_csr_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                      int32_t reverse, int32_t iters, int32_t flags,
+                                      int32_t* ids_host, double* dist_host, int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return refine_host(ctx, data, k, reverse, iters, false, 0, flags, ids_host, dist_host, count_host, true);
   });
 }
 

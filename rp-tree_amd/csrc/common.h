@@ -404,6 +404,14 @@ int32_t knn_graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int3
 int32_t knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
                              int32_t iters, int32_t metric, int32_t* ids_dev, double* dist_dev,
                              int32_t* count_dev);
+// ---- the same two on CSR rows under L2 (graph_csr.hip) -------------------------------------------
+// arguments checked by the caller (CSR data, f64 or f32 values, of the forest's shape); the
+// statistics go where knn_graph_dev's and knn_graph_refine_dev's go
+int32_t knn_graph_csr_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                          int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+int32_t knn_graph_refine_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
+                                 int32_t iters, int32_t* ids_dev, double* dist_dev,
+                                 int32_t* count_dev);
 // synchronises the stream
 int32_t knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* updates, int64_t* candidates);
 // ---- beam search over a kNN graph (graph_search.hip) -----------------------------------------

@@ -29,67 +29,18 @@
 //   refine_end_kernel      the round's bookkeeping: rounds + 1, active = (some row changed)
 // No atomics touch the lists; the counters (updates, candidates, changed rows) are sums, which do
 // not depend on the order of their terms.
+// RefineState, refine_begin / refine_end / refine_copy_kernel and the hash set's set_insert live in
+// graph_refine_dev.h: the rounds over CSR rows (graph_csr.hip) run on the same ones.
 #include <string.h>
 
 #include <algorithm>
 
-#include "graph_dev.h"
+#include "graph_refine_dev.h"
 
 namespace rpt {
 namespace {
 
-constexpr int kEmpty = (int)0x80000000;  // free slot of the hash set; a member c is stored as c
-                                         // (new) or ~c (i itself and F(i): never a candidate)
 constexpr int kLdsMax = 160 * 1024;
-
-struct RefineState {
-  int32_t active;  // 0: an earlier round changed no row, the kernels of this round return at once
-  int32_t pad;
-  unsigned long long changed;  // rows the running round changed
-  unsigned long long rounds, updates, candidates;
-};
-
-__global__ void refine_begin_kernel(RefineState* st) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    st->active = 1;
-    st->pad = 0;
-    st->changed = 0;
-    st->rounds = 0;
-    st->updates = 0;
-    st->candidates = 0;
-  }
-}
-
-__global__ void refine_end_kernel(RefineState* st) {
-  if (threadIdx.x == 0 && blockIdx.x == 0 && st->active) {
-    st->rounds += 1;
-    if (st->changed == 0) st->active = 0;
-    st->changed = 0;
-  }
-}
-
-__global__ void refine_copy_kernel(const RefineState* st, int64_t n, int k,
-                                   const int32_t* __restrict__ sids, const double* __restrict__ sdist,
-                                   const int32_t* __restrict__ scount, int32_t* __restrict__ ids,
-                                   double* __restrict__ dist, int32_t* __restrict__ count) {
-  if (!st->active) return;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n * k; e += stride) {
-    ids[e] = sids[e];
-    dist[e] = sdist[e];
-    if (e < n) count[e] = scount[e];
-  }
-}
-
-// c joins the set unless it is there (as old or new); `stored` is c or ~c
-__device__ inline void set_insert(int* tab, int mask, int shift, int c, int stored) {
-  unsigned h = ((unsigned)c * 2654435761u) >> shift;
-  for (;;) {
-    const int old = atomicCAS(&tab[h], kEmpty, stored);
-    if (old == kEmpty || old == c || old == ~c) return;
-    h = (h + 1) & (unsigned)mask;
-  }
-}
 
 // dynamic LDS, per wave (wave_bytes): 64 * kLS doubles (a chunk of 64 candidates' rows), kCW
 // doubles (the chunk of x_i), H ints (the hash set, later the new candidates), k + r ints (B(i)).

@@ -40,6 +40,7 @@ __all__ = [
     "knnGraph", "knnGraphDev", "knnGraphLastPairs",
     "knnGraphRefine", "knnGraphRefineDev", "knnGraphRefineLast",
     "knnGraphMetric", "knnGraphMetricDev", "knnGraphRefineMetric", "knnGraphRefineMetricDev",
+    "knnGraphSV", "knnGraphSVDev", "knnGraphRefineSV", "knnGraphRefineSVDev",
     "graphSearch", "graphSearchDev", "graphSearchLast",
     "graphPrepare", "graphPrepareDev", "graphPrepareLast",
 ]
@@ -848,6 +849,39 @@ def knnGraphMetricDev(distf, k, forest, ids_ptr, dist_ptr, count_ptr, accumulate
                                          C.c_void_p(ids_ptr), C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
+def knnGraphSV(k, forest, accumulate=None):
+    """knnGraph of a forest over SVector (CSR) rows (rpt_knn_graph_csr_host) -> (ids[n][k],
+    dist[n][k], count[n]).  The distances are metricDDL2's left fold over the dense-ified rows
+    (absent columns +0.0, f32 values widened exactly), so the answer is bit-equal to knnGraph on
+    the dense-ified data set with the same forest; the kernels visit only the 32-column windows in
+    which a leaf holds a nonzero.  Rows must have strictly ascending columns.  accumulate as
+    knnGraph's.  Batch forests over CSR data (f64 or f32 values), L2 only, k <= 64."""
+    ctx, n = forest.ctx, forest.N
+    if accumulate is None:
+        flags = 0
+        ids = np.empty((n, k), dtype=np.int32)
+        dist = np.empty((n, k), dtype=np.float64)
+        cnt = np.empty(n, dtype=np.int32)
+    else:
+        flags = RPT_GRAPH_ACCUMULATE
+        ids = np.array(accumulate[0], dtype=np.int32, order="C")
+        dist = np.array(accumulate[1], dtype=np.float64, order="C")
+        cnt = np.array(accumulate[2], dtype=np.int32, order="C")
+        if ids.shape != (n, k) or dist.shape != (n, k) or cnt.shape != (n,):
+            raise ValueError("accumulate must be (ids[n][k], dist[n][k], count[n]) of this forest's n and k")
+    check(lib().rpt_knn_graph_csr_host(ctx._h, forest._h, forest.data._h, int(k), flags, _vp(ids),
+                                       _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnGraphSVDev(k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
+    """knnGraphSV into device arrays (rpt_knn_graph_csr_dev); the arrays and the synchronisation
+    as knnGraphDev's."""
+    check(lib().rpt_knn_graph_csr_dev(forest.ctx._h, forest._h, forest.data._h, int(k),
+                                      RPT_GRAPH_ACCUMULATE if accumulate else 0, C.c_void_p(ids_ptr),
+                                      C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
+
+
 def knnGraphLastPairs(ctx=None):
     """distances the last knnGraph call on ctx evaluated (rpt_knn_graph_last_pairs)"""
     ctx = ctx or default_context()
@@ -891,6 +925,33 @@ def knnGraphRefineDev(k, data, ids_ptr, dist_ptr, count_ptr, iters=1, reverse=No
     check(lib().rpt_knn_graph_refine_dev(ds.ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
                                          int(iters), 0, C.c_void_p(ids_ptr), C.c_void_p(dist_ptr),
                                          C.c_void_p(count_ptr)))
+
+
+def knnGraphRefineSV(graph, data, iters=1, reverse=None, ctx=None):
+    """knnGraphRefine over SVector (CSR) rows (rpt_knn_graph_refine_csr_host) -> new (ids, dist,
+    count).  data: a CSR Dataset, or a forest over one.  The distances are metricDDL2's left fold
+    over the dense-ified rows, so the answer (and knnGraphRefineLast's numbers) is bit-equal to
+    knnGraphRefine on the dense-ified data set.  Everything else as knnGraphRefine."""
+    ds = _refine_data(data)
+    ctx = ctx or ds.ctx
+    ids = np.array(graph[0], dtype=np.int32, order="C")
+    dist = np.array(graph[1], dtype=np.float64, order="C")
+    cnt = np.array(graph[2], dtype=np.int32, order="C")
+    if ids.ndim != 2 or ids.shape[0] != ds.n or dist.shape != ids.shape or cnt.shape != (ds.n,):
+        raise ValueError("graph must be (ids[n][k], dist[n][k], count[n]) over the data set's n rows")
+    k = ids.shape[1]
+    check(lib().rpt_knn_graph_refine_csr_host(ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
+                                              int(iters), 0, _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnGraphRefineSVDev(k, data, ids_ptr, dist_ptr, count_ptr, iters=1, reverse=None):
+    """knnGraphRefineSV on device arrays in place (rpt_knn_graph_refine_csr_dev); the arrays and
+    the synchronisation as knnGraphRefineDev's."""
+    ds = _refine_data(data)
+    check(lib().rpt_knn_graph_refine_csr_dev(ds.ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
+                                             int(iters), 0, C.c_void_p(ids_ptr), C.c_void_p(dist_ptr),
+                                             C.c_void_p(count_ptr)))
 
 
 def knnGraphRefineMetric(distf, graph, data, iters=1, reverse=None, ctx=None):
