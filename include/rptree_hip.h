@@ -147,6 +147,8 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *                                  reverse (rpt_knn_graph_refine_*)
  *   graph_search_nofilter (0 / 1)  graph search: no visited filter, only the beam itself is checked
  *                                  before a distance is computed (rpt_graph_search_*)
+ *   graph_search_csr_stream (0 / 1)  graph search on CSR rows: every query passes through LDS in
+ *                                  pieces, none stays resident (rpt_graph_search_csr_*)
  *   brute_csr_tile (0 auto, n)     brute force over CSR rows: queries per workgroup (1, 2, 4 or 8; other
  *                                  values round down; halved while the tile does not fit LDS; auto
  *                                  takes up to 4)
@@ -597,6 +599,51 @@ int32_t rpt_graph_search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_d
                               int32_t metric, int32_t flags, int32_t* ids_host, double* dist_host,
                               int32_t* count_host);
 int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
+
+/* ---- query the kNN graph on SVector (CSR) rows, under L2 ----
+ * rpt_graph_search_csr_* is rpt_graph_search_* for a CSR data set and CSR queries (rpt_dataset_csr_*,
+ * f64 or f32 values, the same d and the same dtype); the parameter lists are the dense ones.  With
+ * dense(x) as rpt_knn_graph_csr_* defines it (absent columns are +0.0, f32 values are widened
+ * exactly, a stored zero is a zero), everything stated for rpt_graph_search_* carries over word for
+ * word with dist(q, v) = metricDDL2's left fold over dense(q), dense(x_v), no FMA, one sqrt: the
+ * beam, the offers, the order (distance, id) with NaN behind every number and NaNs among themselves
+ * by id, the answer, counts and unused slots (id -1, distance +inf), termination after at most n
+ * expansions, the visited filter that only saves work (graph_search_nofilter), _dev skipping ids
+ * and counts out of range without validating, _host validating the graph and the seeds before
+ * anything is uploaded (the same messages) and synchronising, rpt_prof_* class 3, rpt_knn_last_*
+ * untouched.  rpt_graph_search_last serves both pairs of entry points: it reports the last call of
+ * either.
+ *   Bit-equal to the dense entry points  The kernel visits the union of the two supports only: a
+ *                column where both hold +0.0 contributes acc + (+0.0), which is acc for every acc
+ *                the fold can hold (it starts at +0.0 and, a sum of squares, never becomes -0.0).
+ *                The fold over any ascending superset of the union of the two supports gives the
+ *                same bits, so the answer and both statistics' definitions are bit-equal to
+ *                rpt_graph_search_* on the dense-ified data and queries with the same graph and
+ *                seeds.  A query and a row without nonzeros are at distance 0.
+ *   metric       must be 0.  RPT_KNN_METRIC_COSINE and RPT_KNN_METRIC_INNER: RPT_E_UNSUPPORTED (the
+ *                parameter is there so that they need no new symbol); any other value, both bits
+ *                together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG.
+ *   The query in LDS  A candidate's row is merged against the query's (column, value) pairs.  A
+ *                query of at most min(d, 2048) entries stays in LDS for its whole search; a longer
+ *                one passes through LDS in pieces of 64 per offer.  The context option
+ *                graph_search_csr_stream = 1 sends every query down the second path; the answer and
+ *                both statistics do not depend on it.  There is no limit on a row's length or on d.
+ *   Ascending columns  A row's columns must ascend strictly; for rows or queries that break the
+ *                invariant the answer is unspecified, but the kernel stays in bounds and terminates.
+ * Errors, all RPT_E_ARG: a dense data set (the message names rpt_graph_search_*), a dense / CSR
+ * pair, d or dtype differing between data and queries, kg, s or k outside [1, 64], ef outside
+ * [k, RPT_GRAPH_SEARCH_MAX_EF], flags other than 0.  n = 0, nq = 0, n = 1, rows and queries without
+ * nonzeros are valid.  A refused call writes nothing and leaves the statistics and the context
+ * usable.  rpt_graph_search_* keeps refusing CSR data (RPT_E_UNSUPPORTED). */
+int32_t rpt_graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                 int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
+                                 const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
+                                 int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+int32_t rpt_graph_search_csr_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                  int32_t kg, const int32_t* gids_host, const int32_t* gcount_host,
+                                  int32_t s, const int32_t* seeds_host, int32_t k, int32_t ef,
+                                  int32_t metric, int32_t flags, int32_t* ids_host, double* dist_host,
+                                  int32_t* count_host);
 
 /* ---- prepare the kNN graph for the search: diversify, reverse union, degree cap ----
  * What PyNNDescent does between building a graph and searching it.  Input: the dense data set `data`

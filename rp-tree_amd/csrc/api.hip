@@ -243,6 +243,7 @@ const OptDesc kOptions[] = {
     {"graph_general", &rpt_options::graph_general},
     {"graph_refine_general", &rpt_options::graph_refine_general},
     {"graph_search_nofilter", &rpt_options::graph_search_nofilter},
+    {"graph_search_csr_stream", &rpt_options::graph_search_csr_stream},
     {"knn_shard_old", &rpt_options::knn_shard_old},
     {"brute_csr_tile", &rpt_options::brute_csr_tile},
     {"comm_force_exchange", &rpt_options::comm_force_exchange},
@@ -1399,14 +1400,18 @@ int32_t rpt_knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* update
 
 // ---- beam search over a kNN graph -------------------------------------------------------------
 namespace {
+// csr: the rpt_graph_search_csr_* entry points (CSR data and queries, L2 only)
 int32_t check_search(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
-                     int32_t s, int32_t k, int32_t ef, int32_t metric, int32_t flags) {
+                     int32_t s, int32_t k, int32_t ef, int32_t metric, int32_t flags, bool csr = false) {
   RPT_ARG(ctx && data && queries, "NULL argument");
   RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
   RPT_TRY(check_graph_metric(metric));
+  if (csr && metric != 0)
+    return fail(RPT_E_UNSUPPORTED, "the graph search on CSR rows is built under metricL2 only (metric must be 0)");
   RPT_ARG(flags == 0, "flags must be 0");
   RPT_ARG(data->csr == queries->csr, "data and queries must both be dense or both CSR");
-  if (data->csr) return fail(RPT_E_UNSUPPORTED, "the graph search takes dense data only (not CSR rows)");
+  if (csr) RPT_ARG(data->csr, "rpt_graph_search_csr_* takes CSR data only (dense rows: rpt_graph_search_*)");
+  else if (data->csr) return fail(RPT_E_UNSUPPORTED, "the graph search takes dense data only (not CSR rows)");
   RPT_ARG(data->d == queries->d && data->dtype == queries->dtype,
           "queries differ from the data set in d or dtype");
   RPT_ARG(kg >= 1 && kg <= RPT_GRAPH_MAX_K, "kg must be in [1,64] (RPT_GRAPH_MAX_K)");
@@ -1417,6 +1422,86 @@ int32_t check_search(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q
   RPT_ARG(data->n <= 0x7fffffff, "graph too large");
   return RPT_OK;
 }
+
+// the graph and the seeds a _host entry point is given, checked before anything is uploaded
+int32_t check_search_arrays(int64_t n, int64_t nq, int32_t kg, const int32_t* gids_host,
+                            const int32_t* gcount_host, int32_t s, const int32_t* seeds_host) {
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t c = gcount_host[i];
+    if (c < 0 || c > kg)
+      return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": count " + std::to_string(c) +
+                                 " outside [0, kg]");
+    for (int32_t e = 0; e < c; ++e) {
+      const int32_t id = gids_host[i * kg + e];
+      if (id < 0 || id >= n)
+        return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": id " + std::to_string(id) +
+                                   " outside [0, n)");
+    }
+  }
+  for (int64_t q = 0; q < nq; ++q)
+    for (int32_t e = 0; e < s; ++e) {
+      const int32_t id = seeds_host[q * s + e];
+      if (id != -1 && (id < 0 || id >= n))
+        return fail(RPT_E_ARG, "seeds row " + std::to_string(q) + ": id " + std::to_string(id) +
+                                   " is neither -1 nor in [0, n)");
+    }
+  return RPT_OK;
+}
+
+int32_t search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
+                   const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s, const int32_t* seeds_dev,
+                   int32_t k, int32_t ef, int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                   int32_t* count_dev, bool csr) {
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, csr));
+  RPT_ARG(data->n == 0 || (gids_dev && gcount_dev), "NULL graph arrays");
+  RPT_ARG(queries->n == 0 || (seeds_dev && ids_dev && dist_dev && count_dev), "NULL seeds or output");
+  RPT_HIP(hipSetDevice(ctx->device));
+  if (csr)
+    return graph_search_csr_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, ids_dev,
+                                dist_dev, count_dev);
+  return graph_search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric,
+                          ids_dev, dist_dev, count_dev);
+}
+
+int32_t search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
+                    const int32_t* gids_host, const int32_t* gcount_host, int32_t s,
+                    const int32_t* seeds_host, int32_t k, int32_t ef, int32_t metric, int32_t flags,
+                    int32_t* ids_host, double* dist_host, int32_t* count_host, bool csr) {
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, csr));
+  const int64_t n = data->n, nq = queries->n;
+  RPT_ARG(n == 0 || (gids_host && gcount_host), "NULL graph arrays");
+  RPT_ARG(nq == 0 || (seeds_host && ids_host && dist_host && count_host), "NULL seeds or output");
+  RPT_TRY(check_search_arrays(n, nq, kg, gids_host, gcount_host, s, seeds_host));
+  RPT_HIP(hipSetDevice(ctx->device));
+  DevBuf<int32_t> gids, gcnt, seeds, ids, cnt;
+  DevBuf<double> dist;
+  RPT_TRY(gids.alloc((size_t)n * kg));
+  RPT_TRY(gcnt.alloc((size_t)n));
+  RPT_TRY(seeds.alloc((size_t)nq * s));
+  RPT_TRY(ids.alloc((size_t)nq * k));
+  RPT_TRY(dist.alloc((size_t)nq * k));
+  RPT_TRY(cnt.alloc((size_t)nq));
+  if (n) {
+    RPT_HIP(hipMemcpy(gids.p, gids_host, (size_t)n * kg * 4, hipMemcpyHostToDevice));
+    RPT_HIP(hipMemcpy(gcnt.p, gcount_host, (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  if (nq) RPT_HIP(hipMemcpy(seeds.p, seeds_host, (size_t)nq * s * 4, hipMemcpyHostToDevice));
+  if (csr)
+    RPT_TRY(graph_search_csr_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, ids.p, dist.p,
+                                 cnt.p));
+  else
+    RPT_TRY(graph_search_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, metric, ids.p,
+                             dist.p, cnt.p));
+  RPT_HIP(stream_sync(ctx->stream));
+  if (nq) {
+    RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+  }
+  return RPT_OK;
+}
 }  // namespace
 
 int32_t rpt_graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
@@ -1424,13 +1509,8 @@ int32_t rpt_graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_da
                              const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
                              int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
   return guarded([&]() -> int32_t {
-    if (ctx) dev_set_stream(ctx->stream);
-    RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags));
-    RPT_ARG(data->n == 0 || (gids_dev && gcount_dev), "NULL graph arrays");
-    RPT_ARG(queries->n == 0 || (seeds_dev && ids_dev && dist_dev && count_dev), "NULL seeds or output");
-    RPT_HIP(hipSetDevice(ctx->device));
-    return graph_search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric,
-                            ids_dev, dist_dev, count_dev);
+    return search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric, flags,
+                      ids_dev, dist_dev, count_dev, false);
   });
 }
 
@@ -1440,54 +1520,29 @@ int32_t rpt_graph_search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_d
                               int32_t metric, int32_t flags, int32_t* ids_host, double* dist_host,
                               int32_t* count_host) {
   return guarded([&]() -> int32_t {
-    if (ctx) dev_set_stream(ctx->stream);
-    RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags));
-    const int64_t n = data->n, nq = queries->n;
-    RPT_ARG(n == 0 || (gids_host && gcount_host), "NULL graph arrays");
-    RPT_ARG(nq == 0 || (seeds_host && ids_host && dist_host && count_host), "NULL seeds or output");
-    // the graph and the seeds are checked here, before anything is uploaded
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t c = gcount_host[i];
-      if (c < 0 || c > kg)
-        return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": count " + std::to_string(c) +
-                                   " outside [0, kg]");
-      for (int32_t e = 0; e < c; ++e) {
-        const int32_t id = gids_host[i * kg + e];
-        if (id < 0 || id >= n)
-          return fail(RPT_E_ARG, "graph row " + std::to_string(i) + ": id " + std::to_string(id) +
-                                     " outside [0, n)");
-      }
-    }
-    for (int64_t q = 0; q < nq; ++q)
-      for (int32_t e = 0; e < s; ++e) {
-        const int32_t id = seeds_host[q * s + e];
-        if (id != -1 && (id < 0 || id >= n))
-          return fail(RPT_E_ARG, "seeds row " + std::to_string(q) + ": id " + std::to_string(id) +
-                                     " is neither -1 nor in [0, n)");
-      }
-    RPT_HIP(hipSetDevice(ctx->device));
-    DevBuf<int32_t> gids, gcnt, seeds, ids, cnt;
-    DevBuf<double> dist;
-    RPT_TRY(gids.alloc((size_t)n * kg));
-    RPT_TRY(gcnt.alloc((size_t)n));
-    RPT_TRY(seeds.alloc((size_t)nq * s));
-    RPT_TRY(ids.alloc((size_t)nq * k));
-    RPT_TRY(dist.alloc((size_t)nq * k));
-    RPT_TRY(cnt.alloc((size_t)nq));
-    if (n) {
-      RPT_HIP(hipMemcpy(gids.p, gids_host, (size_t)n * kg * 4, hipMemcpyHostToDevice));
-      RPT_HIP(hipMemcpy(gcnt.p, gcount_host, (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    if (nq) RPT_HIP(hipMemcpy(seeds.p, seeds_host, (size_t)nq * s * 4, hipMemcpyHostToDevice));
-    RPT_TRY(graph_search_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, metric, ids.p,
-                             dist.p, cnt.p));
-    RPT_HIP(stream_sync(ctx->stream));
-    if (nq) {
-      RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-      RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-      RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    }
-    return RPT_OK;
+    return search_host(ctx, data, queries, kg, gids_host, gcount_host, s, seeds_host, k, ef, metric, flags,
+                       ids_host, dist_host, count_host, false);
+  });
+}
+
+int32_t rpt_graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                 int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
+                                 const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
+                                 int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    return search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric, flags,
+                      ids_dev, dist_dev, count_dev, true);
+  });
+}
+
+int32_t rpt_graph_search_csr_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                  int32_t kg, const int32_t* gids_host, const int32_t* gcount_host,
+                                  int32_t s, const int32_t* seeds_host, int32_t k, int32_t ef,
+                                  int32_t metric, int32_t flags, int32_t* ids_host, double* dist_host,
+                                  int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return search_host(ctx, data, queries, kg, gids_host, gcount_host, s, seeds_host, k, ef, metric, flags,
+                       ids_host, dist_host, count_host, true);
   });
 }
 

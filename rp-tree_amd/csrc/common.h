@@ -169,6 +169,7 @@ struct rpt_options {
   int64_t graph_general = 0;    // kNN graph: every leaf on the tiled kernel (64-row blocks), not the one-workgroup leaf kernel
   int64_t graph_refine_general = 0;  // kNN graph refinement: one point per workgroup for every k and reverse
   int64_t graph_search_nofilter = 0;  // graph search: no visited filter (only the beam itself is checked before a distance)
+  int64_t graph_search_csr_stream = 0;  // graph search on CSR rows: every query passes through LDS in pieces (none stays resident)
   int64_t brute_csr_tile = 0;   // brute force on CSR rows: queries per workgroup (0 = auto; 1, 2, 4 or 8)
   int64_t knn_shard_old = 0;    // kNN: small shards keep the round-3 one-wave kernel (in-kernel traversal, fixed k')
   int64_t comm_force_exchange = 0;  // sharded kNN: a one-rank communicator runs record -> all-gather -> merge too
@@ -422,6 +423,12 @@ int32_t graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
                          const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
                          const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
                          int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+// the same on CSR rows under L2 (graph_search_csr.hip): CSR data and queries of one d and dtype (f64
+// or f32 values); the statistics go where graph_search_dev's go
+int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                             int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
+                             const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t* ids_dev,
+                             double* dist_dev, int32_t* count_dev);
 // synchronises the stream
 int32_t graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
 // ---- a kNN graph made ready for the search (graph_prepare.hip) ---------------------------------

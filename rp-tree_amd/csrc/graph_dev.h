@@ -2,8 +2,10 @@
 // (its NN-descent rounds) and graph_search.hip (the beam search over it): the chunk geometry, the
 // (distance, id) total order, the exact widening of f32 / bf16 elements, the metric's fold step
 // and epilogue, the one-wave insertion into a sorted list, the one-wave staging of a chunk of
-// rows and the CSR of a graph's reverse edges (graph_prepare.hip takes these too).  The
-// translation units are built with -ffp-contract=off.
+// rows, the CSR of a graph's reverse edges (graph_prepare.hip takes these too) and the beam of the
+// search: its offers, its visited filter and its insertion, which graph_search.hip (dense rows) and
+// graph_search_csr.hip (CSR rows) run around their own distance step.  The translation units are
+// built with -ffp-contract=off.
 #pragma once
 
 #include <algorithm>
@@ -169,6 +171,174 @@ __device__ inline void wave_stage(const TD* __restrict__ X, int d, const int* si
       buf[r * kLS + c] = widen(X[(size_t)sid[r] * d + c0 + c]);
     }
   }
+}
+
+// ---- the beam of the graph search, shared by graph_search_kernel (graph_search.hip) and
+// graph_search_csr_kernel (graph_search_csr.hip).  One wave owns a query; per wave in LDS:
+//   bd/bi ef doubles / ints  the beam, sorted; bi holds id (unexpanded) or ~id (expanded)
+//   tab   H ints             the visited filter: a hash of evaluated ids, kProbe slots per id, a
+//                            full neighbourhood is overwritten (lossy)
+//   sid   R ints             the ids of the running offer that are evaluated
+// All 64 lanes of the wave call every function below together.
+constexpr int kEmpty = (int)0x80000000;  // free slot of a hash of ids in LDS (never an id): the
+                                         // search's filter, the refinement's candidate set
+constexpr int kProbe = 8;                // slots of the filter an id may take
+constexpr int kBeamJ = RPT_GRAPH_SEARCH_MAX_EF / 64;  // beam entries a lane looks after
+
+struct SearchState {
+  unsigned long long expansions, evaluated;
+};
+
+struct SearchArgs {
+  int64_t n, nq;
+  int d, kg, s, k, ef;
+  int R, H, qres, vec, nofilter, wave_bytes;
+  int qcap, stream;  // CSR rows: entries of a query that stay in LDS, 1 = every query is streamed
+  const int32_t* gids;
+  const int32_t* gcount;
+  const int32_t* seeds;
+  const double* rn;  // dot(x, x) of the data rows (cosine)
+  const double* qn;  // ... of the queries
+  int32_t* ids;
+  double* dist;
+  int32_t* count;
+  SearchState* st;
+};
+
+__global__ void search_begin_kernel(SearchState* st) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    st->expansions = 0;
+    st->evaluated = 0;
+  }
+}
+
+__device__ inline int beam_id(int v) { return v < 0 ? ~v : v; }
+
+// The next offer, a candidate per lane (-1: none): a batch of R seeds, then the graph row of the
+// first unexpanded entry, which is marked expanded.  false: no unexpanded entry is left, the search
+// is over.  The caller bounds the loop: once the seeds are through, at most n expansions.
+__device__ __forceinline__ bool beam_next_offer(const SearchArgs& a, int64_t qi, int* bi, int c, int nj,
+                                                int lane, int& s0, int64_t& expanded, int& cand) {
+  cand = -1;
+  if (s0 < a.s) {
+    if (lane < a.R && s0 + lane < a.s) cand = a.seeds[qi * a.s + s0 + lane];
+    s0 += a.R;
+    return true;
+  }
+  int pos = -1;
+  for (int j = 0; j < nj && pos < 0; ++j) {
+    const int p = j * 64 + lane;
+    const unsigned long long bal = __ballot(p < c && bi[p] >= 0);
+    if (bal) pos = j * 64 + __ffsll((long long)bal) - 1;
+  }
+  if (pos < 0) return false;
+  const int u = __builtin_amdgcn_readfirstlane(bi[pos]);
+  wave_sync();
+  if (lane == 0) bi[pos] = ~u;
+  wave_sync();
+  ++expanded;
+  const int g = a.gcount[u];
+  if (g >= 0 && g <= a.kg && lane < g) cand = a.gids[(int64_t)u * a.kg + lane];
+  return true;
+}
+
+// Drops what is outside [0, n), what the filter remembers and what the beam holds; the rest is
+// remembered by the filter and compacted into sid[0 .. nrows).  Returns nrows.
+__device__ __forceinline__ int beam_admit(const SearchArgs& a, const int* bi, int c, int* tab, int* sid,
+                                          bool filter, int lane, int cand) {
+  const int mask = a.H - 1, shift = 32 - (31 - __clz(a.H));
+  bool v = cand >= 0 && (int64_t)cand < a.n;
+  const unsigned h = ((unsigned)cand * 2654435761u) >> shift;
+  if (filter && v) {
+    for (int pr = 0; pr < kProbe; ++pr) {
+      const int t = tab[(h + pr) & (unsigned)mask];
+      if (t == cand) v = false;
+      if (t == cand || t == kEmpty) break;
+    }
+  }
+  if (__ballot(v)) {
+    for (int p = 0; p < c; ++p)
+      if (beam_id(bi[p]) == cand) v = false;
+  }
+  const unsigned long long bal = __ballot(v);
+  const int nrows = __popcll(bal);
+  if (nrows == 0) return 0;
+  if (filter && v) {
+    bool done = false;
+    for (int pr = 0; pr < kProbe && !done; ++pr) {
+      const int old = atomicCAS(&tab[(h + pr) & (unsigned)mask], kEmpty, cand);
+      done = old == kEmpty || old == cand;
+    }
+    if (!done) tab[h] = cand;  // a full neighbourhood: forget whoever sat at home
+  }
+  if (v) sid[__popcll(bal & ((1ULL << lane) - 1))] = cand;
+  wave_sync();
+  return nrows;
+}
+
+// The offer's entries (cd, my) of the lanes [0, nrows) into the beam of c entries, one at a time:
+// rank by ballot / popcount over the lanes' entries (lane l looks at positions l, l + 64, ...), the
+// tail shifted by one in LDS.
+__device__ __forceinline__ void beam_insert(double* bd, int* bi, int& c, int ef, int nj, int lane, int nrows,
+                                            double cd, int my) {
+  bool v = lane < nrows;
+  for (;;) {
+    if (c == ef) {  // a full beam: only what comes before its last entry can enter
+      const double td = bd[c - 1];
+      const int ti = beam_id(bi[c - 1]);
+      v = v && before(cd, my, td, ti);
+    }
+    const unsigned long long m = __ballot(v);
+    if (!m) break;
+    const int src = __ffsll((long long)m) - 1;
+    const double nd = __shfl(cd, src);
+    const int ni = __shfl(my, src);
+    if (lane == src) v = false;
+    double ed[kBeamJ];
+    int ei[kBeamJ];
+    int p = 0;
+    bool dup = false;
+#pragma unroll
+    for (int j = 0; j < kBeamJ; ++j)
+      if (j < nj) {
+        const int pos = j * 64 + lane;
+        const bool on = pos < c;
+        ed[j] = on ? bd[pos] : 0.0;
+        ei[j] = on ? bi[pos] : kEmpty;
+        dup |= on && beam_id(ei[j]) == ni;
+        p += __popcll(__ballot(on && before(ed[j], beam_id(ei[j]), nd, ni)));
+      }
+    if (__ballot(dup)) continue;  // the same id twice in one offer
+    const int newc = c < ef ? c + 1 : c;
+    wave_sync();  // every entry has been read
+#pragma unroll
+    for (int j = 0; j < kBeamJ; ++j)
+      if (j < nj) {
+        const int pos = j * 64 + lane;
+        if (pos >= p && pos < c && pos + 1 < newc) {
+          bd[pos + 1] = ed[j];
+          bi[pos + 1] = ei[j];
+        }
+      }
+    if (lane == 0) {
+      bd[p] = nd;
+      bi[p] = ni;
+    }
+    wave_sync();
+    c = newc;
+  }
+}
+
+// the answer of query qi: the first k of the beam, padded with id -1 and distance +inf
+__device__ __forceinline__ void beam_answer(const SearchArgs& a, int64_t qi, const double* bd, const int* bi,
+                                            int c, int lane) {
+  const int found = c < a.k ? c : a.k;
+  if (lane < a.k) {
+    const bool on = lane < found;
+    a.ids[qi * a.k + lane] = on ? beam_id(bi[lane]) : -1;
+    a.dist[qi * a.k + lane] = on ? bd[lane] : pos_inf();
+  }
+  if (lane == 0) a.count[qi] = found;
 }
 
 // ---- the reverse edges of a graph as a CSR, shared by the refinement (graph_refine.hip, per round)

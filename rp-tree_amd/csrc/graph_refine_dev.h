@@ -8,8 +8,8 @@
 namespace rpt {
 namespace {
 
-constexpr int kEmpty = (int)0x80000000;  // free slot of the hash set; a member c is stored as c
-                                         // (new) or ~c (i itself and F(i): never a candidate)
+// the hash set: a free slot is kEmpty (graph_dev.h); a member c is stored as c (new) or ~c (i itself
+// and F(i): never a candidate)
 
 struct RefineState {
   int32_t active;  // 0: an earlier round changed no row, the kernels of this round return at once

@@ -10,15 +10,13 @@
 // graph_search_kernel: one WAVE owns a query, four queries per workgroup.  Per wave in LDS:
 //   buf   R x kLS doubles    a chunk of kCW columns of up to R candidate rows (R = rows of one offer)
 //   qv    d doubles          the query, widened once (d <= kQMax; beyond, kCW doubles per chunk)
-//   bd/bi ef doubles / ints  the beam, sorted; bi holds id (unexpanded) or ~id (expanded)
-//   tab   H ints             the visited filter: a hash of evaluated ids, kProbe slots per id, a
-//                            full neighbourhood is overwritten (lossy)
-//   sid   R ints             the ids of the running offer that are evaluated
-// An offer: a candidate per lane, dropped when the filter or the beam (exactly) holds it, the rest
-// compacted, their rows staged chunk by chunk (wave_stage) and folded a candidate per lane, columns
-// ascending (fold_step / fold_finish: the reference's fold), then inserted one by one: rank by
-// ballot / popcount over the lanes' entries (lane l looks at positions l, l + 64, ...), the tail
-// shifted by one in LDS.  No atomics touch the beam; the filter's atomics only decide what is
+//   bd/bi, tab, sid          the beam, the visited filter and the running offer's ids (graph_dev.h)
+// An offer (graph_dev.h: beam_next_offer, beam_admit, beam_insert, shared with the CSR kernel of
+// graph_search_csr.hip): a candidate per lane, dropped when the filter or the beam (exactly) holds
+// it, the rest compacted, their rows staged chunk by chunk (wave_stage) and folded a candidate per
+// lane, columns ascending (fold_step / fold_finish: the reference's fold), then inserted one by
+// one: rank by ballot / popcount over the lanes' entries (lane l looks at positions l, l + 64, ...),
+// the tail shifted by one in LDS.  No atomics touch the beam; the filter's atomics only decide what is
 // evaluated twice.  The loops are bounded by the definition: ceil(s / R) seed offers, at most n
 // expansions.
 #include <algorithm>
@@ -28,39 +26,8 @@
 namespace rpt {
 namespace {
 
-constexpr int kEmpty = (int)0x80000000;  // free slot of the filter (never an id)
 constexpr int kLdsMax = 160 * 1024;
 constexpr int kQMax = 1024;  // columns up to which the query stays in LDS whole
-constexpr int kProbe = 8;    // slots of the filter an id may take
-constexpr int kBeamJ = RPT_GRAPH_SEARCH_MAX_EF / 64;  // beam entries a lane looks after
-
-struct SearchState {
-  unsigned long long expansions, evaluated;
-};
-
-struct SearchArgs {
-  int64_t n, nq;
-  int d, kg, s, k, ef;
-  int R, H, qres, vec, nofilter, wave_bytes;
-  const int32_t* gids;
-  const int32_t* gcount;
-  const int32_t* seeds;
-  const double* rn;  // dot(x, x) of the data rows (cosine)
-  const double* qn;  // ... of the queries
-  int32_t* ids;
-  double* dist;
-  int32_t* count;
-  SearchState* st;
-};
-
-__global__ void search_begin_kernel(SearchState* st) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    st->expansions = 0;
-    st->evaluated = 0;
-  }
-}
-
-__device__ inline int beam_id(int v) { return v < 0 ? ~v : v; }
 
 template <class TD, int M>
 __global__ __launch_bounds__(256) void graph_search_kernel(const TD* __restrict__ X,
@@ -75,8 +42,6 @@ __global__ __launch_bounds__(256) void graph_search_kernel(const TD* __restrict_
   int* bi = reinterpret_cast<int*>(bd + efp);
   int* tab = bi + efp;
   int* sid = tab + a.H;
-  const int mask = a.H - 1, shift = 32 - (31 - __clz(a.H));
-  const unsigned long long below = (1ULL << lane) - 1;
   const bool filter = a.nofilter == 0;
   unsigned long long n_exp = 0, n_eval = 0;
 
@@ -95,57 +60,13 @@ __global__ __launch_bounds__(256) void graph_search_kernel(const TD* __restrict_
     int s0 = 0;
     int64_t expanded = 0;
     for (;;) {
-      // ---- the next offer: a batch of seeds, then the row of the first unexpanded entry
-      int cand = -1;
-      if (s0 < a.s) {
-        if (lane < R && s0 + lane < a.s) cand = a.seeds[qi * a.s + s0 + lane];
-        s0 += R;
-      } else {
-        if (expanded >= a.n) break;  // every point at most once
-        int pos = -1;
-        for (int j = 0; j < nj && pos < 0; ++j) {
-          const int p = j * 64 + lane;
-          const unsigned long long bal = __ballot(p < c && bi[p] >= 0);
-          if (bal) pos = j * 64 + __ffsll((long long)bal) - 1;
-        }
-        if (pos < 0) break;
-        const int u = __builtin_amdgcn_readfirstlane(bi[pos]);
-        wave_sync();
-        if (lane == 0) bi[pos] = ~u;
-        wave_sync();
-        ++expanded;
-        const int g = a.gcount[u];
-        if (g >= 0 && g <= a.kg && lane < g) cand = a.gids[(int64_t)u * a.kg + lane];
-      }
-
-      // ---- drop what is outside [0, n), what the filter remembers, what the beam holds
-      bool v = cand >= 0 && (int64_t)cand < a.n;
-      const unsigned h = ((unsigned)cand * 2654435761u) >> shift;
-      if (filter && v) {
-        for (int pr = 0; pr < kProbe; ++pr) {
-          const int t = tab[(h + pr) & (unsigned)mask];
-          if (t == cand) v = false;
-          if (t == cand || t == kEmpty) break;
-        }
-      }
-      if (__ballot(v)) {
-        for (int p = 0; p < c; ++p)
-          if (beam_id(bi[p]) == cand) v = false;
-      }
-      const unsigned long long bal = __ballot(v);
-      const int nrows = __popcll(bal);
+      // ---- the next offer, without what is out of range, remembered by the filter or in the beam
+      int cand;
+      if (s0 >= a.s && expanded >= a.n) break;  // every point at most once
+      if (!beam_next_offer(a, qi, bi, c, nj, lane, s0, expanded, cand)) break;
+      const int nrows = beam_admit(a, bi, c, tab, sid, filter, lane, cand);
       if (nrows == 0) continue;
       n_eval += (unsigned long long)nrows;
-      if (filter && v) {
-        bool done = false;
-        for (int pr = 0; pr < kProbe && !done; ++pr) {
-          const int old = atomicCAS(&tab[(h + pr) & (unsigned)mask], kEmpty, cand);
-          done = old == kEmpty || old == cand;
-        }
-        if (!done) tab[h] = cand;  // a full neighbourhood: forget whoever sat at home
-      }
-      if (v) sid[__popcll(bal & below)] = cand;
-      wave_sync();
 
       // ---- the distances: a candidate per lane, columns ascending
       const int my = lane < nrows ? sid[lane] : -1;
@@ -167,63 +88,11 @@ __global__ __launch_bounds__(256) void graph_search_kernel(const TD* __restrict_
       if constexpr (M == kGraphCosine) nrm = lane < nrows ? a.rn[my] : 0.0;
       const double cd = fold_finish<M>(acc, qnorm, nrm);
 
-      // ---- into the beam, one at a time
-      v = lane < nrows;
-      for (;;) {
-        if (c == ef) {  // a full beam: only what comes before its last entry can enter
-          const double td = bd[c - 1];
-          const int ti = beam_id(bi[c - 1]);
-          v = v && before(cd, my, td, ti);
-        }
-        const unsigned long long m = __ballot(v);
-        if (!m) break;
-        const int src = __ffsll((long long)m) - 1;
-        const double nd = __shfl(cd, src);
-        const int ni = __shfl(my, src);
-        if (lane == src) v = false;
-        double ed[kBeamJ];
-        int ei[kBeamJ];
-        int p = 0;
-        bool dup = false;
-#pragma unroll
-        for (int j = 0; j < kBeamJ; ++j)
-          if (j < nj) {
-            const int pos = j * 64 + lane;
-            const bool on = pos < c;
-            ed[j] = on ? bd[pos] : 0.0;
-            ei[j] = on ? bi[pos] : kEmpty;
-            dup |= on && beam_id(ei[j]) == ni;
-            p += __popcll(__ballot(on && before(ed[j], beam_id(ei[j]), nd, ni)));
-          }
-        if (__ballot(dup)) continue;  // the same id twice in one offer
-        const int newc = c < ef ? c + 1 : c;
-        wave_sync();  // every entry has been read
-#pragma unroll
-        for (int j = 0; j < kBeamJ; ++j)
-          if (j < nj) {
-            const int pos = j * 64 + lane;
-            if (pos >= p && pos < c && pos + 1 < newc) {
-              bd[pos + 1] = ed[j];
-              bi[pos + 1] = ei[j];
-            }
-          }
-        if (lane == 0) {
-          bd[p] = nd;
-          bi[p] = ni;
-        }
-        wave_sync();
-        c = newc;
-      }
+      // ---- into the beam, one at a time, by the order of before()
+      beam_insert(bd, bi, c, ef, nj, lane, nrows, cd, my);
     }
     n_exp += (unsigned long long)expanded;
-
-    const int found = c < a.k ? c : a.k;
-    if (lane < a.k) {
-      const bool on = lane < found;
-      a.ids[qi * a.k + lane] = on ? beam_id(bi[lane]) : -1;
-      a.dist[qi * a.k + lane] = on ? bd[lane] : pos_inf();
-    }
-    if (lane == 0) a.count[qi] = found;
+    beam_answer(a, qi, bd, bi, c, lane);
   }
   if (lane == 0 && (n_exp | n_eval)) {
     atomicAdd(&a.st->expansions, n_exp);

@@ -571,6 +571,46 @@ inline KnnResult graphSearch(const RPForest& tts, const GraphResult& g, const Da
   return graphSearch(*tts.ctx, *tts.data, g, qs, k, ef, seeds, seed_k, metric, stats);
 }
 
+// graphSearch over SVector rows under L2 (rpt_graph_search_csr_host): data and qs are CSR data sets
+// of one d and dtype.  The distances are metricDDL2's left fold over the dense-ified query and row,
+// so the answer and the statistics are bit-equal to graphSearch's on the dense-ified data set and
+// queries with the same graph and seeds.  The rows' indices must ascend strictly.
+inline KnnResult graphSearchSV(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs, int k,
+                               int ef, const std::vector<int32_t>& seeds, int s, SearchStats* stats = nullptr) {
+  const size_t n = (size_t)data.n, nq = (size_t)qs.n;
+  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0))
+    throw RPTError(RPT_E_ARG, "graphSearchSV: a graph of another data set");
+  if (s < 1 || seeds.size() != nq * (size_t)s) throw RPTError(RPT_E_ARG, "graphSearchSV: seeds must be [nq][s]");
+  const int32_t none = -1;  // non-NULL pointers for empty inputs
+  KnnResult r;
+  r.k = k;
+  r.ids.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
+  r.dist.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
+  r.count.resize(nq + 1);
+  check(rpt_graph_search_csr_host(ctx.get(), data.get(), qs.get(), g.k, n ? g.ids.data() : &none,
+                                  n ? g.count.data() : &none, s, nq ? seeds.data() : &none, k, ef, 0, 0,
+                                  r.ids.data(), r.dist.data(), r.count.data()));
+  r.ids.resize(nq * (size_t)k);
+  r.dist.resize(nq * (size_t)k);
+  r.count.resize(nq);
+  if (stats) check(rpt_graph_search_last(ctx.get(), &stats->expansions, &stats->evaluated));
+  return r;
+}
+// ... the seeds taken from a batch forest over the CSR set, as graphSearch takes them
+inline KnnResult graphSearchSV(const RPForest& tts, const GraphResult& g, const Dataset& qs, int k, int ef,
+                               int seed_k = 8, SearchStats* stats = nullptr) {
+  const size_t nq = (size_t)qs.n;
+  if (seed_k < 1) throw RPTError(RPT_E_ARG, "graphSearchSV: seed_k must be at least 1");
+  std::vector<int32_t> seeds(nq * (size_t)seed_k + 1), cnt(nq + 1);
+  std::vector<double> dist(nq * (size_t)seed_k + 1);
+  check(rpt_knn_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), seed_k, RPT_KNN_DEDUP, seeds.data(),
+                     dist.data(), cnt.data()));
+  seeds.resize(nq * (size_t)seed_k);
+  for (size_t i = 0; i < nq; ++i)
+    for (int e = cnt[i]; e < seed_k; ++e) seeds[i * (size_t)seed_k + (size_t)e] = -1;
+  return graphSearchSV(*tts.ctx, *tts.data, g, qs, k, ef, seeds, seed_k, stats);
+}
+
 struct BruteResult {
   std::vector<int32_t> ids;  // [nq][k], -1 = unused slot
   std::vector<double> dist;  // [nq][k]

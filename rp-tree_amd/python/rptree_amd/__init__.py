@@ -41,7 +41,7 @@ __all__ = [
     "knnGraphRefine", "knnGraphRefineDev", "knnGraphRefineLast",
     "knnGraphMetric", "knnGraphMetricDev", "knnGraphRefineMetric", "knnGraphRefineMetricDev",
     "knnGraphSV", "knnGraphSVDev", "knnGraphRefineSV", "knnGraphRefineSVDev",
-    "graphSearch", "graphSearchDev", "graphSearchLast",
+    "graphSearch", "graphSearchDev", "graphSearchLast", "graphSearchSV", "graphSearchSVDev",
     "graphPrepare", "graphPrepareDev", "graphPrepareLast",
 ]
 
@@ -1046,8 +1046,52 @@ def graphSearchDev(data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, k, ef,
                                      C.c_void_p(count_ptr)))
 
 
+def graphSearchSV(graph, data, qs, k, ef=None, seeds=None, forest=None, seed_k=8, ctx=None):
+    """graphSearch over SVector (CSR) rows under L2 (rpt_graph_search_csr_host) -> (ids[nq][k],
+    dist[nq][k], count[nq]).  data: a CSR Dataset, or a forest over one; qs: SVectors, a CSR tuple
+    (rowptr, col, val, d) or a CSR Dataset of the same d and dtype.  The distances are metricDDL2's
+    left fold over the dense-ified query and row, so the answer (and graphSearchLast's numbers) is
+    bit-equal to graphSearch on the dense-ified data set and queries with the same graph and seeds.
+    With `forest` (a batch forest over the CSR set) the seeds are the ids of knnBatch(seed_k, forest,
+    qs, dedup=True).  Everything else as graphSearch."""
+    ds = _refine_data(data)
+    ctx = ctx or ds.ctx
+    gids = np.ascontiguousarray(graph[0], dtype=np.int32)
+    gcnt = np.ascontiguousarray(graph[-1], dtype=np.int32)
+    if gids.ndim != 2 or gids.shape[0] != ds.n or gcnt.shape != (ds.n,):
+        raise ValueError("graph must be (ids[n][kg], dist[n][kg], count[n]) over the data set's n rows")
+    if ef is None:
+        ef = max(int(k), 32)
+    if seeds is None and forest is None:
+        raise ValueError("graphSearchSV needs seeds or a forest to take them from")
+    qd, nq = _query_dataset(ctx, ds, qs)
+    if seeds is None:
+        sid, _, scnt = knnBatch(int(seed_k), forest, qd, dedup=True)
+        seeds = np.where(np.arange(sid.shape[1])[None, :] < scnt[:, None], sid, -1)
+    seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+    if seeds.ndim != 2 or seeds.shape[0] != nq:
+        raise ValueError("seeds must be [nq][s]")
+    ids = np.empty((nq, k), dtype=np.int32)
+    dist = np.empty((nq, k), dtype=np.float64)
+    cnt = np.empty(nq, dtype=np.int32)
+    check(lib().rpt_graph_search_csr_host(ctx._h, ds._h, qd._h, int(gids.shape[1]), _vp(gids), _vp(gcnt),
+                                          int(seeds.shape[1]), _vp(seeds), int(k), int(ef), 0, 0,
+                                          _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def graphSearchSVDev(data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, k, ef, ids_ptr, dist_ptr, count_ptr):
+    """graphSearchSV on device arrays (rpt_graph_search_csr_dev): data and queries are CSR Datasets;
+    the arrays and the synchronisation as graphSearchDev's."""
+    ds = _refine_data(data)
+    check(lib().rpt_graph_search_csr_dev(ds.ctx._h, ds._h, queries._h, int(kg), C.c_void_p(gids_ptr),
+                                         C.c_void_p(gcount_ptr), int(s), C.c_void_p(seeds_ptr), int(k), int(ef),
+                                         0, 0, C.c_void_p(ids_ptr), C.c_void_p(dist_ptr),
+                                         C.c_void_p(count_ptr)))
+
+
 def graphSearchLast(ctx=None):
-    """(expansions, evaluated) of the last graphSearch call on ctx (rpt_graph_search_last;
+    """(expansions, evaluated) of the last graphSearch / graphSearchSV call on ctx (rpt_graph_search_last;
     synchronises): beam entries expanded and distances computed, summed over the queries."""
     ctx = ctx or default_context()
     a, b = C.c_int64(), C.c_int64()

@@ -89,6 +89,8 @@ SYMBOLS = {
     "rpt_knn_graph_refine_csr_host": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "rpt_graph_search_csr_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "rpt_graph_search_csr_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_last": (i32, [vp, p_i64, p_i64]),
     "rpt_graph_prepare_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_prepare_host": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
