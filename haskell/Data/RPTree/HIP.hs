@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -58,6 +58,7 @@ foreign import ccall safe "rpt_knn_graph_refine_csr_host" c_knn_graph_refine_csr
 foreign import ccall safe "rpt_graph_search_host" c_graph_search_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_csr_host" c_graph_search_csr_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_host" c_graph_prepare_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_graph_prepare_csr_host" c_graph_prepare_csr_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
 -- multi-GPU (csrc/comm.hip on librccl): one process drives n devices; per-device arguments are
 -- arrays with one entry per device (Foreign.Marshal.Array.withArray)
@@ -371,6 +372,21 @@ graphPrepareHIP ctx ds m n k kout diversify reverse (i0, d0, c0) = do
   VS.unsafeWith i0 (\pi -> VS.unsafeWith d0 (\pd -> VS.unsafeWith c0 (\pc ->
     VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
       c_graph_prepare_host ctx ds (fromIntegral k) pi pd pc (fromIntegral kout) (metricFlag m) flags a b)))))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | 'graphPrepareHIP' over SVector rows under L2 (rpt_graph_prepare_csr_host): @ds@ is a CSR data set
+-- ('withDeviceDataSV'), the graph e.g. 'knnGraphSVHIP's or 'knnGraphRefineSVHIP's.  The pair distances
+-- of @diversify@ are metricDDL2's left fold over the dense-ified rows, so the answer is bit-equal to
+-- 'graphPrepareHIP' with 'MetricL2' on the dense-ified data set and the same graph.
+graphPrepareSVHIP :: Ptr Ctx -> Ptr Dataset -> Int -> Int -> Int -> Bool -> Bool
+                  -> (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+                  -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+graphPrepareSVHIP ctx ds n k kout diversify reverse (i0, d0, c0) = do
+  ids <- VSM.new (n * kout); dist <- VSM.new (n * kout); cnt <- VSM.new n
+  let flags = (if diversify then 1 else 0) + (if reverse then 2 else 0)
+  VS.unsafeWith i0 (\pi -> VS.unsafeWith d0 (\pd -> VS.unsafeWith c0 (\pc ->
+    VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
+      c_graph_prepare_csr_host ctx ds (fromIntegral k) pi pd pc (fromIntegral kout) 0 flags a b)))))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | SVector rows as a CSR dataset on the device (rpt_dataset_csr_host), for the extent of the

@@ -149,6 +149,10 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *                                  before a distance is computed (rpt_graph_search_*)
  *   graph_search_csr_stream (0 / 1)  graph search on CSR rows: every query passes through LDS in
  *                                  pieces, none stays resident (rpt_graph_search_csr_*)
+ *   graph_prepare_csr_resident (0, n, -1)  graph preparation on CSR rows: a point's neighbours are
+ *                                  staged in LDS when they hold at most this many entries together
+ *                                  (0 = the built-in cap of 1536, n > 0 = min(n, 1536), -1 = no point
+ *                                  is resident; rpt_graph_prepare_csr_*)
  *   brute_csr_tile (0 auto, n)     brute force over CSR rows: queries per workgroup (1, 2, 4 or 8; other
  *                                  values round down; halved while the tile does not fit LDS; auto
  *                                  takes up to 4)
@@ -707,6 +711,53 @@ int32_t rpt_graph_prepare_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
                                int32_t metric, int32_t flags, int32_t* out_ids_host, double* out_dist_host,
                                int32_t* out_count_host);
 int32_t rpt_graph_prepare_last(rpt_ctx* ctx, int64_t* pairs, int64_t* occluded, int64_t* capped);
+
+/* ---- prepare the kNN graph for the search on SVector (CSR) rows, under L2 ----
+ * rpt_graph_prepare_csr_* is rpt_graph_prepare_* for a CSR data set (rpt_dataset_csr_*, f64 or f32
+ * values); the parameter lists are the dense ones, `metric` included.  With dense(x) as
+ * rpt_knn_graph_csr_* defines it (absent columns are +0.0, f32 values are widened exactly, a stored
+ * zero is a zero), everything stated for rpt_graph_prepare_* carries over word for word with
+ * dist(e_l, e_m) = metricDDL2's left fold over dense(x_l), dense(x_m), no FMA, one sqrt: Kept(i) and
+ * its plain <, Union(i), the first kout by (distance, id) with NaN behind every number, unused slots
+ * (id -1, distance +inf), the three statistics, _host validating the graph before anything is
+ * uploaded (the same checks and messages) and synchronising, _dev clamping a count to [0, k] and
+ * skipping ids out of range without validating, the scratch from the context's pool (RPT_E_NOMEM),
+ * rpt_prof_* class 3, rpt_knn_last_* untouched, n = 0 and n = 1 valid.  rpt_graph_prepare_last serves
+ * both pairs of entry points: it reports the last call of either.
+ *   Bit-equal to the dense entry points  Only DIVERSIFY reads data rows.  Its kernel visits the
+ *                union of two neighbours' supports only: a column where both hold +0.0 contributes
+ *                acc + (+0.0), which is acc for every acc the fold can hold (it starts at +0.0 and,
+ *                a sum of squares, never becomes -0.0).  The fold over any ascending superset of the
+ *                union of the two supports gives the same bits, so the output and all three
+ *                statistics are bit-equal to rpt_graph_prepare_* on the dense-ified rows with the
+ *                same graph.  Two rows without nonzeros are at distance 0 (0 < 0 is false: kept).
+ *   metric       must be 0.  RPT_KNN_METRIC_COSINE and RPT_KNN_METRIC_INNER: RPT_E_UNSUPPORTED (the
+ *                parameter is there so that they need no new symbol); any other value, both bits
+ *                together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG.
+ *   The neighbours in LDS  A pair's distance is a two-pointer merge over the two rows' (column,
+ *                value) pairs.  Every neighbour row takes part in c - 1 pairs, so a point whose
+ *                neighbours hold at most 1536 entries together (12 bytes each: two workgroups of
+ *                four points fit a CU's 160 KB for every k) has them copied into LDS once, values
+ *                widened once, and its pairs merge out of LDS (resident); any other point's pairs
+ *                walk their rows through global loads, which needs no LDS per entry.  The choice is
+ *                per point, both paths fold the same entries in the same order.  The context option
+ *                graph_prepare_csr_resident lowers the cap (n > 0) or sends every point down the
+ *                second path (-1); the output and the statistics do not depend on it.  There is no
+ *                limit on a row's length or on d.
+ *   Ascending columns  A row's columns must ascend strictly; for rows that break the invariant the
+ *                answer is unspecified, but the kernel stays in bounds and terminates.
+ * Errors: a dense data set: RPT_E_ARG (the message names rpt_graph_prepare_*); k or kout outside
+ * [1, RPT_GRAPH_MAX_K], other flag bits: RPT_E_ARG, as the dense entry points.  A refused call writes
+ * nothing and leaves the statistics and the context usable.  rpt_graph_prepare_* keeps refusing CSR
+ * data (RPT_E_UNSUPPORTED). */
+int32_t rpt_graph_prepare_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
+                                  const double* dist_dev, const int32_t* count_dev, int32_t kout,
+                                  int32_t metric, int32_t flags, int32_t* out_ids_dev, double* out_dist_dev,
+                                  int32_t* out_count_dev);
+int32_t rpt_graph_prepare_csr_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_host,
+                                   const double* dist_host, const int32_t* count_host, int32_t kout,
+                                   int32_t metric, int32_t flags, int32_t* out_ids_host, double* out_dist_host,
+                                   int32_t* out_count_host);
 
 /* multi-GPU merge: G per-shard results (shard g holds trees [g*T/G, (g+1)*T/G)), gathered
  * shard-major as ids_dev[G][nq][k] etc. (e.g. by an RCCL all-gather), merged into the

@@ -244,6 +244,7 @@ const OptDesc kOptions[] = {
     {"graph_refine_general", &rpt_options::graph_refine_general},
     {"graph_search_nofilter", &rpt_options::graph_search_nofilter},
     {"graph_search_csr_stream", &rpt_options::graph_search_csr_stream},
+    {"graph_prepare_csr_resident", &rpt_options::graph_prepare_csr_resident},
     {"knn_shard_old", &rpt_options::knn_shard_old},
     {"brute_csr_tile", &rpt_options::brute_csr_tile},
     {"comm_force_exchange", &rpt_options::comm_force_exchange},
@@ -1557,17 +1558,69 @@ int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evalua
 
 // ---- a kNN graph made ready for the search -------------------------------------------------------
 namespace {
+// csr: the rpt_graph_prepare_csr_* entry points (CSR data, L2 only)
 int32_t check_prepare(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t kout, int32_t metric,
-                      int32_t flags) {
+                      int32_t flags, bool csr = false) {
   RPT_ARG(ctx && data, "NULL argument");
   RPT_ARG(data->ctx == ctx, "handles belong to another context");
   RPT_TRY(check_graph_metric(metric));
+  if (csr && metric != 0)
+    return fail(RPT_E_UNSUPPORTED,
+                "the graph preparation on CSR rows is built under metricL2 only (metric must be 0)");
   RPT_ARG((flags & ~(RPT_GRAPH_PREP_DIVERSIFY | RPT_GRAPH_PREP_REVERSE)) == 0,
           "flags must be an or of RPT_GRAPH_PREP_DIVERSIFY and RPT_GRAPH_PREP_REVERSE");
-  if (data->csr) return fail(RPT_E_UNSUPPORTED, "the graph preparation takes dense data only (not CSR rows)");
+  if (csr) RPT_ARG(data->csr, "rpt_graph_prepare_csr_* takes CSR data only (dense rows: rpt_graph_prepare_*)");
+  else if (data->csr) return fail(RPT_E_UNSUPPORTED, "the graph preparation takes dense data only (not CSR rows)");
   RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
   RPT_ARG(kout >= 1 && kout <= RPT_GRAPH_MAX_K, "kout must be in [1,64] (RPT_GRAPH_MAX_K)");
   RPT_ARG(data->n <= 0x7fffffff, "graph too large");
+  return RPT_OK;
+}
+
+int32_t prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
+                    const double* dist_dev, const int32_t* count_dev, int32_t kout, int32_t metric,
+                    int32_t flags, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev,
+                    bool csr) {
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags, csr));
+  RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
+  RPT_ARG(data->n == 0 || (out_ids_dev && out_dist_dev && out_count_dev), "NULL output");
+  RPT_HIP(hipSetDevice(ctx->device));
+  return graph_prepare_dev(ctx, data, k, ids_dev, dist_dev, count_dev, kout, metric, flags, out_ids_dev,
+                           out_dist_dev, out_count_dev);
+}
+
+int32_t prepare_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_host,
+                     const double* dist_host, const int32_t* count_host, int32_t kout, int32_t metric,
+                     int32_t flags, int32_t* out_ids_host, double* out_dist_host, int32_t* out_count_host,
+                     bool csr) {
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags, csr));
+  const int64_t n = data->n;
+  RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
+  RPT_ARG(n == 0 || (out_ids_host && out_dist_host && out_count_host), "NULL output");
+  RPT_TRY(check_graph_rows(n, k, ids_host, count_host));  // before anything is uploaded
+  RPT_HIP(hipSetDevice(ctx->device));
+  DevBuf<int32_t> ids, cnt, oids, ocnt;
+  DevBuf<double> dist, odist;
+  RPT_TRY(ids.alloc((size_t)n * k));
+  RPT_TRY(dist.alloc((size_t)n * k));
+  RPT_TRY(cnt.alloc((size_t)n));
+  RPT_TRY(oids.alloc((size_t)n * kout));
+  RPT_TRY(odist.alloc((size_t)n * kout));
+  RPT_TRY(ocnt.alloc((size_t)n));
+  if (n) {
+    RPT_HIP(hipMemcpy(ids.p, ids_host, (size_t)n * k * 4, hipMemcpyHostToDevice));
+    RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
+    RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  RPT_TRY(graph_prepare_dev(ctx, data, k, ids.p, dist.p, cnt.p, kout, metric, flags, oids.p, odist.p, ocnt.p));
+  RPT_HIP(stream_sync(ctx->stream));
+  if (n) {
+    RPT_HIP(hipMemcpy(out_ids_host, oids.p, (size_t)n * kout * 4, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(out_dist_host, odist.p, (size_t)n * kout * 8, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(out_count_host, ocnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  }
   return RPT_OK;
 }
 }  // namespace
@@ -1577,13 +1630,8 @@ int32_t rpt_graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, 
                               int32_t metric, int32_t flags, int32_t* out_ids_dev, double* out_dist_dev,
                               int32_t* out_count_dev) {
   return guarded([&]() -> int32_t {
-    if (ctx) dev_set_stream(ctx->stream);
-    RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags));
-    RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
-    RPT_ARG(data->n == 0 || (out_ids_dev && out_dist_dev && out_count_dev), "NULL output");
-    RPT_HIP(hipSetDevice(ctx->device));
-    return graph_prepare_dev(ctx, data, k, ids_dev, dist_dev, count_dev, kout, metric, flags, out_ids_dev,
-                             out_dist_dev, out_count_dev);
+    return prepare_dev(ctx, data, k, ids_dev, dist_dev, count_dev, kout, metric, flags, out_ids_dev,
+                       out_dist_dev, out_count_dev, false);
   });
 }
 
@@ -1592,34 +1640,28 @@ int32_t rpt_graph_prepare_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
                                int32_t metric, int32_t flags, int32_t* out_ids_host, double* out_dist_host,
                                int32_t* out_count_host) {
   return guarded([&]() -> int32_t {
-    if (ctx) dev_set_stream(ctx->stream);
-    RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags));
-    const int64_t n = data->n;
-    RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
-    RPT_ARG(n == 0 || (out_ids_host && out_dist_host && out_count_host), "NULL output");
-    RPT_TRY(check_graph_rows(n, k, ids_host, count_host));  // before anything is uploaded
-    RPT_HIP(hipSetDevice(ctx->device));
-    DevBuf<int32_t> ids, cnt, oids, ocnt;
-    DevBuf<double> dist, odist;
-    RPT_TRY(ids.alloc((size_t)n * k));
-    RPT_TRY(dist.alloc((size_t)n * k));
-    RPT_TRY(cnt.alloc((size_t)n));
-    RPT_TRY(oids.alloc((size_t)n * kout));
-    RPT_TRY(odist.alloc((size_t)n * kout));
-    RPT_TRY(ocnt.alloc((size_t)n));
-    if (n) {
-      RPT_HIP(hipMemcpy(ids.p, ids_host, (size_t)n * k * 4, hipMemcpyHostToDevice));
-      RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
-      RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    RPT_TRY(graph_prepare_dev(ctx, data, k, ids.p, dist.p, cnt.p, kout, metric, flags, oids.p, odist.p, ocnt.p));
-    RPT_HIP(stream_sync(ctx->stream));
-    if (n) {
-      RPT_HIP(hipMemcpy(out_ids_host, oids.p, (size_t)n * kout * 4, hipMemcpyDeviceToHost));
-      RPT_HIP(hipMemcpy(out_dist_host, odist.p, (size_t)n * kout * 8, hipMemcpyDeviceToHost));
-      RPT_HIP(hipMemcpy(out_count_host, ocnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    }
-    return RPT_OK;
+    return prepare_host(ctx, data, k, ids_host, dist_host, count_host, kout, metric, flags, out_ids_host,
+                        out_dist_host, out_count_host, false);
+  });
+}
+
+int32_t rpt_graph_prepare_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
+                                  const double* dist_dev, const int32_t* count_dev, int32_t kout,
+                                  int32_t metric, int32_t flags, int32_t* out_ids_dev,
+                                  double* out_dist_dev, int32_t* out_count_dev) {
+  return guarded([&]() -> int32_t {
+    return prepare_dev(ctx, data, k, ids_dev, dist_dev, count_dev, kout, metric, flags, out_ids_dev,
+                       out_dist_dev, out_count_dev, true);
+  });
+}
+
+int32_t rpt_graph_prepare_csr_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                   const int32_t* ids_host, const double* dist_host,
+                                   const int32_t* count_host, int32_t kout, int32_t metric, int32_t flags,
+                                   int32_t* out_ids_host, double* out_dist_host, int32_t* out_count_host) {
+  return guarded([&]() -> int32_t {
+    return prepare_host(ctx, data, k, ids_host, dist_host, count_host, kout, metric, flags, out_ids_host,
+                        out_dist_host, out_count_host, true);
   });
 }
 

@@ -170,6 +170,8 @@ struct rpt_options {
   int64_t graph_refine_general = 0;  // kNN graph refinement: one point per workgroup for every k and reverse
   int64_t graph_search_nofilter = 0;  // graph search: no visited filter (only the beam itself is checked before a distance)
   int64_t graph_search_csr_stream = 0;  // graph search on CSR rows: every query passes through LDS in pieces (none stays resident)
+  int64_t graph_prepare_csr_resident = 0;  // graph preparation on CSR rows: entries of a point's neighbours up to which they
+                                           // are staged in LDS (0 = the built-in cap, n = min(n, cap), -1 = no point resident)
   int64_t brute_csr_tile = 0;   // brute force on CSR rows: queries per workgroup (0 = auto; 1, 2, 4 or 8)
   int64_t knn_shard_old = 0;    // kNN: small shards keep the round-3 one-wave kernel (in-kernel traversal, fixed k')
   int64_t comm_force_exchange = 0;  // sharded kNN: a one-rank communicator runs record -> all-gather -> merge too
@@ -432,9 +434,10 @@ int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_da
 // synchronises the stream
 int32_t graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
 // ---- a kNN graph made ready for the search (graph_prepare.hip) ---------------------------------
-// arguments checked by the caller (dense data, k and kout <= 64, flags an or of
-// RPT_GRAPH_PREP_DIVERSIFY / _REVERSE; metric as knn_graph_dev's); the input arrays are read only
-// and not validated: entries out of range are skipped; enqueued on the ctx stream
+// arguments checked by the caller (k and kout <= 64, flags an or of RPT_GRAPH_PREP_DIVERSIFY /
+// _REVERSE; metric as knn_graph_dev's, 0 for CSR data: rows of f64 or f32 values, which take
+// graph_diversify_csr_kernel); the input arrays are read only and not validated: entries out of
+// range are skipped; enqueued on the ctx stream
 int32_t graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
                           const double* dist_dev, const int32_t* count_dev, int32_t kout, int32_t metric,
                           int32_t flags, int32_t* out_ids_dev, double* out_dist_dev,

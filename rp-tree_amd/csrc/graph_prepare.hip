@@ -1,4 +1,5 @@
-// graph_prepare.hip — a kNN graph made ready for the search (rpt_graph_prepare_*): occluded
+// graph_prepare.hip — a kNN graph made ready for the search (rpt_graph_prepare_* on dense rows,
+// rpt_graph_prepare_csr_* on SVector rows under L2): occluded
 // neighbours dropped (DIVERSIFY), reverse edges added (REVERSE), the degree capped at kout.
 //
 // Kept(i): the valid entries of row i; with DIVERSIFY, in stored order, e_m stays unless a kept
@@ -19,6 +20,19 @@
 //                          m are consecutive, so lane m cuts its word of m bits out of them and a
 //                          loop of c - 1 wave-uniform steps resolves the serial keep rule.  Kept
 //                          entries are compacted into a scratch graph.
+//   graph_diversify_csr_kernel (DIVERSIFY, rpt_graph_prepare_csr_*: SVector rows under L2) the same
+//                          frame: one wave per point, the compacted row, the pairs on the lanes, the
+//                          ballots, the keep rule (div_row / div_keep / div_store below, one
+//                          definition each).  Only the distance of a pair differs: a two-pointer merge
+//                          over the two neighbours' (column, value) pairs (pair_fold), +0.0 for the
+//                          absent side, which gives the bits of the dense fold over all d columns
+//                          (graph_search_csr.hip has the argument).  Every neighbour row takes part in
+//                          c - 1 pairs, so a point whose neighbours hold at most kResCap entries
+//                          together has them packed into the wave's LDS first (resident: a wave prefix
+//                          sum of the row lengths gives the offsets, the copy is coalesced row by row,
+//                          values are widened once); any other point's lanes walk their two rows
+//                          through global loads.  The choice is per point and wave-uniform, both paths
+//                          fold the same entries in the same order.
 //   rev_zero / _degree / _scan / _fill (REVERSE; graph_dev.h) the CSR of the reverse edges of Kept
 //   prep_merge_kernel      one wave per point holds the output row one entry per lane: Kept(i)
 //                          enters it (as it stands when it is sorted, else through wave_merge), then
@@ -62,6 +76,65 @@ __device__ inline void pair_of(int p, int& l, int& m) {
   l = p - m * (m - 1) / 2;
 }
 
+// ---- the frame of a diversify kernel, shared by graph_diversify_kernel (dense rows) and
+// graph_diversify_csr_kernel (CSR rows).  All 64 lanes of the wave call these together.
+
+// The entry of row i this lane looks at: false when it lies behind the clamped count or its id is no
+// row.  The caller compacts the valid entries in stored order: sid/sd[0 .. cc), cc = popcount(vm).
+__device__ __forceinline__ bool div_row(const int32_t* __restrict__ ids, const double* __restrict__ dist,
+                                        const int32_t* __restrict__ count, int64_t i, int k, int64_t n,
+                                        int lane, int& id, double& dv, unsigned long long& vm) {
+  int c = count[i];
+  c = c < 0 ? 0 : (c > k ? k : c);
+  id = -1;
+  dv = pos_inf();
+  if (lane < c) {
+    id = ids[i * k + lane];
+    dv = dist[i * k + lane];
+  }
+  const bool ok = lane < c && (unsigned)id < (unsigned long long)n;
+  vm = __ballot(ok);
+  return ok;
+}
+
+// The serial keep rule.  bal: the occlusion bits of the pairs in pair order (bit p: e_l occludes
+// e_m, p = m (m - 1) / 2 + l), one word more than the pairs fill.  The pairs of an m are consecutive,
+// so lane m cuts its word of m bits out of them, and c - 1 wave-uniform steps walk the row: e_m stays
+// unless a kept e_l occludes it.  -> the kept entries as a mask.
+__device__ __forceinline__ unsigned long long div_keep(const unsigned long long* bal, int cc, int lane) {
+  unsigned long long kept = 1ULL;
+  unsigned long long mine = 0;  // lane m: bit l of `mine` = e_l occludes e_m
+  if (lane >= 1 && lane < cc) {
+    const int start = lane * (lane - 1) / 2, w = start >> 6, sh = start & 63;
+    mine = bal[w] >> sh;
+    if (sh + lane > 64) mine |= bal[w + 1] << (64 - sh);
+    mine &= (1ULL << lane) - 1;
+  }
+  for (int m = 1; m < cc; ++m) {
+    const unsigned long long om = __shfl(mine, m);
+    if (!(om & kept)) kept |= 1ULL << m;
+  }
+  return kept;
+}
+
+// Kept(i) compacted into row i of the scratch graph, the rest of the row padded.  -> |Kept(i)|
+__device__ __forceinline__ int div_store(unsigned long long kept, int cc, const int* sid, const double* sd,
+                                         int64_t i, int k, int lane, int32_t* __restrict__ kids,
+                                         double* __restrict__ kdist, int32_t* __restrict__ kcount) {
+  const int kc = __popcll(kept);
+  if (lane < cc && ((kept >> lane) & 1)) {
+    const int pos = __popcll(kept & ((1ULL << lane) - 1));
+    kids[i * k + pos] = sid[lane];
+    kdist[i * k + pos] = sd[lane];
+  }
+  if (lane >= kc && lane < k) {
+    kids[i * k + lane] = -1;
+    kdist[i * k + lane] = pos_inf();
+  }
+  if (lane == 0) kcount[i] = kc;
+  return kc;
+}
+
 // dynamic LDS, per wave (wave_bytes): k * kLS doubles (a chunk of the neighbours' rows), k doubles
 // (stored distances), k doubles (dot(x, x), cosine), NA + 1 words (the ballots), k ints (ids)
 template <class TD, int M, int NA>
@@ -81,16 +154,10 @@ __global__ __launch_bounds__(256) void graph_diversify_kernel(
   unsigned long long n_pairs = 0, n_occ = 0;
 
   for (int64_t i = (int64_t)blockIdx.x * W + wave; i < n; i += (int64_t)gridDim.x * W) {
-    int c = count[i];
-    c = c < 0 ? 0 : (c > k ? k : c);
-    int id = -1;
-    double dv = pos_inf();
-    if (lane < c) {
-      id = ids[i * k + lane];
-      dv = dist[i * k + lane];
-    }
-    const bool ok = lane < c && (unsigned)id < (unsigned long long)n;
-    const unsigned long long vm = __ballot(ok);
+    int id;
+    double dv;
+    unsigned long long vm;
+    const bool ok = div_row(ids, dist, count, i, k, n, lane, id, dv, vm);
     const int cc = __popcll(vm);
     wave_sync();  // the last point's rows have been read
     if (ok) {
@@ -145,30 +212,207 @@ __global__ __launch_bounds__(256) void graph_diversify_kernel(
       }
       if (lane == 0) bal[NA] = 0;
       wave_sync();
-      // lane m: bit l of `mine` = e_l occludes e_m
-      unsigned long long mine = 0;
-      if (lane >= 1 && lane < cc) {
-        const int start = lane * (lane - 1) / 2, w = start >> 6, sh = start & 63;
-        mine = bal[w] >> sh;
-        if (sh + lane > 64) mine |= bal[w + 1] << (64 - sh);
-        mine &= (1ULL << lane) - 1;
+      kept = div_keep(bal, cc, lane);
+    }
+    const int kc = div_store(kept, cc, sid, sd, i, k, lane, kids, kdist, kcount);
+    n_pairs += (unsigned long long)P;
+    n_occ += (unsigned long long)(cc - kc);
+  }
+  if (lane == 0 && (n_pairs | n_occ)) {
+    atomicAdd(&st->pairs, n_pairs);
+    atomicAdd(&st->occluded, n_occ);
+  }
+}
+
+// ---- DIVERSIFY on SVector (CSR) rows ------------------------------------------------------------
+constexpr int kNoCol = 0x7fffffff;  // a cursor at its row's end (a column is below d <= INT_MAX)
+// Entries of a point's neighbours up to which they are staged in LDS, 12 B each (an int column, the
+// value widened to double).  Two workgroups per CU get 80 KB each of the 160 KB, a wave 20 480 B.
+// What a wave holds besides the entries is largest at k = 64: ids, stored distances, row lengths,
+// row positions and 33 ballot words, 1 800 B.  That leaves 18 680 B = 1 556 entries; 1 536 = 3 x 512
+// is the round number below, and a workgroup then takes 80 928 B at k = 64 (less for a smaller k:
+// 74 752 B at k = 10).  The C3 point (k = 10, rows of 784 x 0.19 = 149 entries: 1 490 +- 35 per point
+// if the neighbours were average rows) lies below the cap; measured there, neighbours are short
+// rows, 1 245 entries per point on average and 1 404 at the most.
+constexpr int kResCap = 1536;
+
+// where the rows of a pair are read: the entries staged in the wave's LDS, or the data set.
+// kReadBoth: pair_fold reads the entries under both cursors in every step (below).
+struct LdsRows {
+  static constexpr bool kReadBoth = true;
+  const int* c;
+  const double* v;
+  __device__ __forceinline__ int col(int p) const { return c[p]; }
+  __device__ __forceinline__ double val(int p) const { return v[p]; }
+};
+template <class TV>
+struct GlobalRows {
+  static constexpr bool kReadBoth = false;
+  const int32_t* __restrict__ c;
+  const TV* __restrict__ v;
+  __device__ __forceinline__ int col(int64_t p) const { return c[p]; }
+  __device__ __forceinline__ double val(int64_t p) const { return widen(v[p]); }
+};
+
+// The L2 accumulator of the rows [ap, ae) and [bp, be): a two-pointer merge, the steps of merge_piece
+// in graph_search_csr.hip.  Every step takes the entry of one side or of both (equal columns), the
+// absent side is +0.0, and the tail of the longer row is folded the same way: a cursor at its row's
+// end counts as column kNoCol.  A cursor is read only below its row's end and every step advances
+// one, also for rows whose columns do not ascend.  The steps, and so the bits, do not depend on how
+// the entries are fetched, which is chosen by what is cheap where they lie (C3, k = 10, ms of the
+// whole DIVERSIFY call, both ways measured on both paths):
+//   LDS     the entries under both cursors are read together at the top of every step, one round trip
+//           a step instead of one per side that moved (17.2 against 24.8 ms); a finished cursor reads
+//           entry 0, which exists whenever the loop runs, and its value is not used
+//   global  the entries are carried in registers and only a side that moved loads its next one (32.8
+//           against 44.0 ms: reading both every step doubles the loads)
+template <class R, class I>
+__device__ __forceinline__ double pair_fold(const R& r, I ap, I ae, I bp, I be) {
+  double acc = 0.0;
+  if constexpr (R::kReadBoth) {
+    while (ap < ae || bp < be) {
+      const bool ha = ap < ae, hb = bp < be;
+      const I ia = ha ? ap : (I)0, ib = hb ? bp : (I)0;
+      const int la = r.col(ia), lb = r.col(ib);
+      const double va = r.val(ia), vb = r.val(ib);
+      const int ca = ha ? la : kNoCol, cb = hb ? lb : kNoCol;
+      const bool take_a = ca <= cb, take_b = cb <= ca;
+      acc = fold_step<kGraphL2>(acc, take_a ? va : 0.0, take_b ? vb : 0.0);
+      ap += take_a ? 1 : 0;
+      bp += take_b ? 1 : 0;
+    }
+  } else {
+    int ca = kNoCol, cb = kNoCol;
+    double va = 0.0, vb = 0.0;
+    if (ap < ae) {
+      ca = r.col(ap);
+      va = r.val(ap);
+    }
+    if (bp < be) {
+      cb = r.col(bp);
+      vb = r.val(bp);
+    }
+    while (ap < ae || bp < be) {
+      const bool take_a = ca <= cb, take_b = cb <= ca;
+      acc = fold_step<kGraphL2>(acc, take_a ? va : 0.0, take_b ? vb : 0.0);
+      if (take_a) {
+        ++ap;
+        ca = kNoCol;
+        if (ap < ae) {
+          ca = r.col(ap);
+          va = r.val(ap);
+        }
       }
-      for (int m = 1; m < cc; ++m) {
-        const unsigned long long om = __shfl(mine, m);
-        if (!(om & kept)) kept |= 1ULL << m;
+      if (take_b) {
+        ++bp;
+        cb = kNoCol;
+        if (bp < be) {
+          cb = r.col(bp);
+          vb = r.val(bp);
+        }
       }
     }
-    const int kc = __popcll(kept);
-    if (lane < cc && ((kept >> lane) & 1)) {
-      const int pos = __popcll(kept & below);
-      kids[i * k + pos] = sid[lane];
-      kdist[i * k + pos] = sd[lane];
+  }
+  return acc;
+}
+
+// dynamic LDS, per wave (wave_bytes): cap doubles (staged values), k doubles (stored distances), k
+// 64-bit row positions (into the staged entries when the point is resident, else into col / val),
+// NA + 1 words (the ballots), cap ints (staged columns), k ints (ids), k ints (row lengths)
+template <class TV, int NA>
+__global__ __launch_bounds__(256) void graph_diversify_csr_kernel(
+    PrepState* st, const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+    const TV* __restrict__ val, int64_t n, int k, int cap, int wave_bytes,
+    const int32_t* __restrict__ ids, const double* __restrict__ dist,
+    const int32_t* __restrict__ count, int32_t* __restrict__ kids, double* __restrict__ kdist,
+    int32_t* __restrict__ kcount) {
+  extern __shared__ double smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
+  double* ev = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + (size_t)wave * wave_bytes);
+  double* sd = ev + cap;
+  long long* pos = reinterpret_cast<long long*>(sd + k);
+  unsigned long long* bal = reinterpret_cast<unsigned long long*>(pos + k);
+  int* ec = reinterpret_cast<int*>(bal + NA + 1);
+  int* sid = ec + cap;
+  int* rl = sid + k;
+  const unsigned long long below = (1ULL << lane) - 1;
+  unsigned long long n_pairs = 0, n_occ = 0;
+
+  for (int64_t i = (int64_t)blockIdx.x * W + wave; i < n; i += (int64_t)gridDim.x * W) {
+    int id;
+    double dv;
+    unsigned long long vm;
+    const bool ok = div_row(ids, dist, count, i, k, n, lane, id, dv, vm);
+    const int cc = __popcll(vm);
+    wave_sync();  // the last point's rows have been read
+    if (ok) {
+      const int at = __popcll(vm & below);
+      sid[at] = id;
+      sd[at] = dv;
     }
-    if (lane >= kc && lane < k) {
-      kids[i * k + lane] = -1;
-      kdist[i * k + lane] = pos_inf();
+    wave_sync();
+    const int P = cc * (cc - 1) / 2;
+
+    unsigned long long kept = cc > 0 ? 1ULL : 0ULL;
+    if (P > 0) {
+      // lane r < cc: the r-th neighbour's row; a wave prefix sum of the lengths (each clamped to
+      // cap + 1, so that the sum fits an int) places the rows in the staged entries
+      long long rb = 0;
+      int len = 0;
+      if (lane < cc) {
+        const int v = sid[lane];
+        rb = rowptr[v];
+        const long long l64 = rowptr[v + 1] - rb;
+        len = l64 < 0 ? 0 : (l64 > (long long)kNoCol ? kNoCol : (int)l64);
+      }
+      const int lc = len > cap ? cap + 1 : len;
+      int incl = lc;
+      for (int s = 1; s < 64; s <<= 1) {
+        const int t = __shfl_up(incl, s);
+        if (lane >= s) incl += t;
+      }
+      const int total = __shfl(incl, 63);
+      const bool resident = total <= cap;  // wave-uniform; cap = 0: no point that has an entry to stage
+      const int off = incl - lc;
+      if (lane < cc) {
+        pos[lane] = resident ? (long long)off : rb;
+        rl[lane] = len;
+      }
+      if (resident) {
+        for (int r = 0; r < cc; ++r) {  // row by row: consecutive lanes, consecutive entries
+          const long long b = __shfl(rb, r);
+          const int L = __shfl(len, r), o = __shfl(off, r);
+          for (int p = lane; p < L; p += 64) {
+            ec[o + p] = col[b + p];
+            ev[o + p] = widen(val[b + p]);
+          }
+        }
+      }
+      wave_sync();
+#pragma unroll
+      for (int a = 0; a < NA; ++a) {
+        const int p = lane + 64 * a;
+        int l = 0, m = 0;
+        double acc = 0.0;
+        if (p < P) {
+          pair_of(p, l, m);
+          if (resident) {
+            const int pa = (int)pos[l], pb = (int)pos[m];
+            acc = pair_fold(LdsRows{ec, ev}, pa, pa + rl[l], pb, pb + rl[m]);
+          } else {
+            const long long pa = pos[l], pb = pos[m];
+            acc = pair_fold(GlobalRows<TV>{col, val}, pa, pa + rl[l], pb, pb + rl[m]);
+          }
+        }
+        const bool occ = p < P && fold_finish<kGraphL2>(acc, 0.0, 0.0) < sd[m];
+        const unsigned long long b = __ballot(occ);
+        if (lane == 0) bal[a] = b;
+      }
+      if (lane == 0) bal[NA] = 0;
+      wave_sync();
+      kept = div_keep(bal, cc, lane);
     }
-    if (lane == 0) kcount[i] = kc;
+    const int kc = div_store(kept, cc, sid, sd, i, k, lane, kids, kdist, kcount);
     n_pairs += (unsigned long long)P;
     n_occ += (unsigned long long)(cc - kc);
   }
@@ -249,6 +493,7 @@ struct DivArgs {
   PrepState* st;
   const rpt_dataset* data;
   int k, wave_bytes;
+  int cap;  // CSR rows: entries of a point's neighbours that are staged in LDS (0: no point is resident)
   const int32_t *ids, *count;
   const double* dist;
   int32_t *kids, *kcount;
@@ -302,6 +547,35 @@ int32_t launch_diversify_metric(int m, int na, const DivArgs& a) {
   return launch_diversify_na<TD, kGraphL2>(na, a);
 }
 
+template <class TV, int NA>
+int32_t launch_diversify_csr(const DivArgs& a) {
+  static DeviceOnce attr_once;
+  RPT_TRY(attr_once.run(a.ctx->device, [&]() -> int32_t {
+    RPT_HIP(hipFuncSetAttribute((const void*)graph_diversify_csr_kernel<TV, NA>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
+    return RPT_OK;
+  }));
+  constexpr int W = 4;
+  const int64_t want = (a.data->n + W - 1) / W;
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)a.ctx->n_cu * 16));
+  hipLaunchKernelGGL((graph_diversify_csr_kernel<TV, NA>), dim3(grid), dim3(64 * W), (size_t)a.wave_bytes * W,
+                     a.ctx->stream, a.st, a.data->rowptr, a.data->col, static_cast<const TV*>(a.data->val),
+                     a.data->n, a.k, a.cap, a.wave_bytes, a.ids, a.dist, a.count, a.kids, a.kdist, a.kcount);
+  return RPT_OK;
+}
+
+template <class TV>
+int32_t launch_diversify_csr_na(int na, const DivArgs& a) {
+  switch (na) {
+    case 1: return launch_diversify_csr<TV, 1>(a);
+    case 2: return launch_diversify_csr<TV, 2>(a);
+    case 4: return launch_diversify_csr<TV, 4>(a);
+    case 8: return launch_diversify_csr<TV, 8>(a);
+    case 16: return launch_diversify_csr<TV, 16>(a);
+    default: return launch_diversify_csr<TV, 32>(a);
+  }
+}
+
 }  // namespace
 
 int32_t graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
@@ -319,7 +593,17 @@ int32_t graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, cons
   PrepState* st = static_cast<PrepState*>(ctx->prepare_state_dev);
   const int64_t n = data->n;
   const int na = pair_bucket(k);
-  const int wave_bytes = (int)(((size_t)(k * kLS + 2 * k + na + 1) * 8 + (size_t)k * 4 + 7) & ~(size_t)7);
+  int wave_bytes, cap = 0;
+  if (data->csr) {
+    // graph_prepare_csr_resident: 0 the built-in cap, n > 0 a smaller one, -1 no point resident.  Rows
+    // of ascending columns hold at most d entries each: no more LDS than k of them can fill.
+    const int64_t opt = ctx->opt.graph_prepare_csr_resident;
+    const int64_t want = opt < 0 ? 0 : (opt == 0 ? kResCap : std::min<int64_t>(opt, kResCap));
+    cap = (int)std::min<int64_t>(want, (int64_t)k * data->d);
+    wave_bytes = (int)(((size_t)(cap + 2 * k + na + 1) * 8 + (size_t)(cap + 2 * k) * 4 + 7) & ~(size_t)7);
+  } else {
+    wave_bytes = (int)(((size_t)(k * kLS + 2 * k + na + 1) * 8 + (size_t)k * 4 + 7) & ~(size_t)7);
+  }
   if (4 * wave_bytes > kLdsMax) return fail(RPT_E_INTERNAL, "prepare: the neighbours' rows do not fit LDS");
 
   DevBuf<int32_t> kids, kcount, deg, cur, rsrc;
@@ -344,11 +628,16 @@ int32_t graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, cons
     const double* gd = dist_dev;
     const int32_t* gc = count_dev;
     if (diversify) {
-      const DivArgs a{ctx, st, data, k, wave_bytes, ids_dev, count_dev, dist_dev, kids.p, kcount.p, kdist.p};
-      switch (data->dtype) {
-        case RPT_F64: RPT_TRY(launch_diversify_metric<double>(m, na, a)); break;
-        case RPT_F32: RPT_TRY(launch_diversify_metric<float>(m, na, a)); break;
-        default: RPT_TRY(launch_diversify_metric<uint16_t>(m, na, a));
+      const DivArgs a{ctx, st, data, k, wave_bytes, cap, ids_dev, count_dev, dist_dev, kids.p, kcount.p, kdist.p};
+      if (data->csr) {
+        if (data->dtype == RPT_F64) RPT_TRY(launch_diversify_csr_na<double>(na, a));
+        else RPT_TRY(launch_diversify_csr_na<float>(na, a));
+      } else {
+        switch (data->dtype) {
+          case RPT_F64: RPT_TRY(launch_diversify_metric<double>(m, na, a)); break;
+          case RPT_F32: RPT_TRY(launch_diversify_metric<float>(m, na, a)); break;
+          default: RPT_TRY(launch_diversify_metric<uint16_t>(m, na, a));
+        }
       }
       gi = kids.p;
       gd = kdist.p;

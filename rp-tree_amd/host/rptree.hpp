@@ -483,14 +483,17 @@ inline GraphResult knnGraphRefineSV(Context& ctx, const Dataset& data, const Gra
 struct PrepareStats {
   int64_t pairs = 0, occluded = 0, capped = 0;
 };
-inline GraphResult graphPrepare(Context& ctx, const Dataset& data, const GraphResult& g, Metric metric,
-                                int kout = -1, bool diversify = true, bool reverse = true,
-                                PrepareStats* stats = nullptr) {
+// graphPrepare / graphPrepareSV around their _host entry point
+using GraphPrepareEntry = int32_t (*)(rpt_ctx*, const rpt_dataset*, int32_t, const int32_t*, const double*,
+                                      const int32_t*, int32_t, int32_t, int32_t, int32_t*, double*, int32_t*);
+inline GraphResult graphPrepareVia(GraphPrepareEntry entry, const char* who, Context& ctx, const Dataset& data,
+                                   const GraphResult& g, int32_t metric, int kout, bool diversify, bool reverse,
+                                   PrepareStats* stats) {
   const size_t n = (size_t)data.n;
   if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0) || g.dist.size() != g.ids.size())
-    throw RPTError(RPT_E_ARG, "graphPrepare: a graph of another data set or k");
+    throw RPTError(RPT_E_ARG, std::string(who) + ": a graph of another data set or k");
   if (kout < 0) kout = 2 * g.k < RPT_GRAPH_MAX_K ? 2 * g.k : RPT_GRAPH_MAX_K;
-  if (kout < 1 || kout > RPT_GRAPH_MAX_K) throw RPTError(RPT_E_ARG, "graphPrepare: kout must be in [1,64]");
+  if (kout < 1 || kout > RPT_GRAPH_MAX_K) throw RPTError(RPT_E_ARG, std::string(who) + ": kout must be in [1,64]");
   const int32_t none = -1;  // non-NULL pointers for an empty data set
   const double nod = 0.0;
   GraphResult out;
@@ -498,19 +501,40 @@ inline GraphResult graphPrepare(Context& ctx, const Dataset& data, const GraphRe
   out.ids.resize(n * (size_t)kout + 1);
   out.dist.resize(n * (size_t)kout + 1);
   out.count.resize(n + 1);
-  check(rpt_graph_prepare_host(ctx.get(), data.get(), g.k, n ? g.ids.data() : &none, n ? g.dist.data() : &nod,
-                               n ? g.count.data() : &none, kout, metric_flags(metric),
-                               (diversify ? RPT_GRAPH_PREP_DIVERSIFY : 0) | (reverse ? RPT_GRAPH_PREP_REVERSE : 0),
-                               out.ids.data(), out.dist.data(), out.count.data()));
+  check(entry(ctx.get(), data.get(), g.k, n ? g.ids.data() : &none, n ? g.dist.data() : &nod,
+              n ? g.count.data() : &none, kout, metric,
+              (diversify ? RPT_GRAPH_PREP_DIVERSIFY : 0) | (reverse ? RPT_GRAPH_PREP_REVERSE : 0), out.ids.data(),
+              out.dist.data(), out.count.data()));
   out.ids.resize(n * (size_t)kout);
   out.dist.resize(n * (size_t)kout);
   out.count.resize(n);
   if (stats) check(rpt_graph_prepare_last(ctx.get(), &stats->pairs, &stats->occluded, &stats->capped));
   return out;
 }
+inline GraphResult graphPrepare(Context& ctx, const Dataset& data, const GraphResult& g, Metric metric,
+                                int kout = -1, bool diversify = true, bool reverse = true,
+                                PrepareStats* stats = nullptr) {
+  return graphPrepareVia(rpt_graph_prepare_host, "graphPrepare", ctx, data, g, metric_flags(metric), kout,
+                         diversify, reverse, stats);
+}
 inline GraphResult graphPrepare(Context& ctx, const Dataset& data, const GraphResult& g, int kout = -1,
                                 bool diversify = true, bool reverse = true, PrepareStats* stats = nullptr) {
   return graphPrepare(ctx, data, g, Metric::L2, kout, diversify, reverse, stats);
+}
+
+// graphPrepare over SVector rows under L2 (rpt_graph_prepare_csr_host): data is a CSR data set.  The
+// pair distances of diversify are metricDDL2's left fold over the dense-ified rows, so the graph and
+// the statistics are bit-equal to graphPrepare's on the dense-ified data set with the same graph.
+// The rows' indices must ascend strictly.
+inline GraphResult graphPrepareSV(Context& ctx, const Dataset& data, const GraphResult& g, int kout = -1,
+                                  bool diversify = true, bool reverse = true, PrepareStats* stats = nullptr) {
+  return graphPrepareVia(rpt_graph_prepare_csr_host, "graphPrepareSV", ctx, data, g, 0, kout, diversify, reverse,
+                         stats);
+}
+// ... over the data set of a forest
+inline GraphResult graphPrepareSV(const RPForest& tts, const GraphResult& g, int kout = -1, bool diversify = true,
+                                  bool reverse = true, PrepareStats* stats = nullptr) {
+  return graphPrepareSV(*tts.ctx, *tts.data, g, kout, diversify, reverse, stats);
 }
 
 // Query a kNN graph: best-first beam search (rpt_graph_search_host).  g: a graph over `data`

@@ -42,7 +42,7 @@ __all__ = [
     "knnGraphMetric", "knnGraphMetricDev", "knnGraphRefineMetric", "knnGraphRefineMetricDev",
     "knnGraphSV", "knnGraphSVDev", "knnGraphRefineSV", "knnGraphRefineSVDev",
     "graphSearch", "graphSearchDev", "graphSearchLast", "graphSearchSV", "graphSearchSVDev",
-    "graphPrepare", "graphPrepareDev", "graphPrepareLast",
+    "graphPrepare", "graphPrepareDev", "graphPrepareLast", "graphPrepareSV", "graphPrepareSVDev",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -1103,18 +1103,8 @@ def _prepare_flags(diversify, reverse):
     return (RPT_GRAPH_PREP_DIVERSIFY if diversify else 0) | (RPT_GRAPH_PREP_REVERSE if reverse else 0)
 
 
-def graphPrepare(graph, data, kout=None, diversify=True, reverse=True, metric=None, ctx=None):
-    """A kNN graph made ready for graphSearch (rpt_graph_prepare_host) -> new (ids[n][kout],
-    dist[n][kout], count[n]); the input tuple is not modified.  graph: (ids[n][k], dist[n][k],
-    count[n]) over `data`, e.g. knnGraph's or knnGraphRefine's; data: a dense Dataset, or a forest
-    (its .data is used).  diversify: walking a row in stored order, a neighbour is dropped when an
-    already kept neighbour of the row is nearer to it than the point itself is (a plain <; the pair
-    distance is metric's fold, bit for bit).  reverse: every point that lists i after that joins row
-    i, at the distance stored there.  The row is the first kout (None = min(64, 2 k)) of that set by
-    (distance, id); unused slots are id -1, distance +inf.  metric: None / metricL2, metricCosine or
-    metricInner, the one the graph was built under.  Under metricInner, which is no metric,
-    diversify costs recall: pass diversify=False there.  Deterministic; k and kout <= 64."""
-    metric_flag = _metric_flag(metric)
+def _graph_prepare(entry, graph, data, kout, diversify, reverse, metric_flag, ctx):
+    """graphPrepare / graphPrepareSV around their _host entry point"""
     ds = _refine_data(data)
     ctx = ctx or ds.ctx
     ids = np.ascontiguousarray(graph[0], dtype=np.int32)
@@ -1131,9 +1121,24 @@ def graphPrepare(graph, data, kout=None, diversify=True, reverse=True, metric=No
     oids = np.empty((ds.n, kout), dtype=np.int32)
     odist = np.empty((ds.n, kout), dtype=np.float64)
     ocnt = np.empty(ds.n, dtype=np.int32)
-    check(lib().rpt_graph_prepare_host(ctx._h, ds._h, int(k), _vp(ids), _vp(dist), _vp(cnt), kout, metric_flag,
-                                       _prepare_flags(diversify, reverse), _vp(oids), _vp(odist), _vp(ocnt)))
+    check(entry(ctx._h, ds._h, int(k), _vp(ids), _vp(dist), _vp(cnt), kout, metric_flag,
+                _prepare_flags(diversify, reverse), _vp(oids), _vp(odist), _vp(ocnt)))
     return oids, odist, ocnt
+
+
+def graphPrepare(graph, data, kout=None, diversify=True, reverse=True, metric=None, ctx=None):
+    """A kNN graph made ready for graphSearch (rpt_graph_prepare_host) -> new (ids[n][kout],
+    dist[n][kout], count[n]); the input tuple is not modified.  graph: (ids[n][k], dist[n][k],
+    count[n]) over `data`, e.g. knnGraph's or knnGraphRefine's; data: a dense Dataset, or a forest
+    (its .data is used).  diversify: walking a row in stored order, a neighbour is dropped when an
+    already kept neighbour of the row is nearer to it than the point itself is (a plain <; the pair
+    distance is metric's fold, bit for bit).  reverse: every point that lists i after that joins row
+    i, at the distance stored there.  The row is the first kout (None = min(64, 2 k)) of that set by
+    (distance, id); unused slots are id -1, distance +inf.  metric: None / metricL2, metricCosine or
+    metricInner, the one the graph was built under.  Under metricInner, which is no metric,
+    diversify costs recall: pass diversify=False there.  Deterministic; k and kout <= 64."""
+    return _graph_prepare(lib().rpt_graph_prepare_host, graph, data, kout, diversify, reverse,
+                          _metric_flag(metric), ctx)
 
 
 def graphPrepareDev(k, data, ids_ptr, dist_ptr, count_ptr, kout, out_ids_ptr, out_dist_ptr, out_count_ptr,
@@ -1151,8 +1156,29 @@ def graphPrepareDev(k, data, ids_ptr, dist_ptr, count_ptr, kout, out_ids_ptr, ou
                                       C.c_void_p(out_dist_ptr), C.c_void_p(out_count_ptr)))
 
 
+def graphPrepareSV(graph, data, kout=None, diversify=True, reverse=True, ctx=None):
+    """graphPrepare over SVector (CSR) rows under L2 (rpt_graph_prepare_csr_host) -> new (ids[n][kout],
+    dist[n][kout], count[n]).  data: a CSR Dataset, or a forest over one; graph: e.g. knnGraphSV's or
+    knnGraphRefineSV's.  The pair distances of diversify are metricDDL2's left fold over the
+    dense-ified rows, so the answer (and graphPrepareLast's numbers) is bit-equal to graphPrepare on
+    the dense-ified data set with the same graph.  kout: None = min(64, 2 k).  Everything else as
+    graphPrepare."""
+    return _graph_prepare(lib().rpt_graph_prepare_csr_host, graph, data, kout, diversify, reverse, 0, ctx)
+
+
+def graphPrepareSVDev(k, data, ids_ptr, dist_ptr, count_ptr, kout, out_ids_ptr, out_dist_ptr, out_count_ptr,
+                      diversify=True, reverse=True):
+    """graphPrepareSV on device arrays (rpt_graph_prepare_csr_dev): data is a CSR Dataset; the arrays
+    and the synchronisation as graphPrepareDev's."""
+    ds = _refine_data(data)
+    check(lib().rpt_graph_prepare_csr_dev(ds.ctx._h, ds._h, int(k), C.c_void_p(ids_ptr), C.c_void_p(dist_ptr),
+                                          C.c_void_p(count_ptr), int(kout), 0,
+                                          _prepare_flags(diversify, reverse), C.c_void_p(out_ids_ptr),
+                                          C.c_void_p(out_dist_ptr), C.c_void_p(out_count_ptr)))
+
+
 def graphPrepareLast(ctx=None):
-    """(pairs, occluded, capped) of the last graphPrepare call on ctx (rpt_graph_prepare_last;
+    """(pairs, occluded, capped) of the last graphPrepare / graphPrepareSV call on ctx (rpt_graph_prepare_last;
     synchronises): pair distances evaluated by diversify, entries it dropped, entries of the unions
     that the cap kout cut off, summed over the rows."""
     ctx = ctx or default_context()
