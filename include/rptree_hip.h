@@ -124,6 +124,12 @@ int32_t rpt_ctx_sync(rpt_ctx* ctx);
 /* device buffers released by the library are cached for reuse (multi-GB hipMalloc/hipFree per
  * build is slow); rpt_ctx_trim returns the cache to the driver (rpt_ctx_destroy does too). */
 int32_t rpt_ctx_trim(rpt_ctx* ctx);
+/* Allocator debugging aid.  RPT_POOL_POISON=<byte> in the environment (read once, at library load)
+ * fills every block the library's device allocator hands out with that byte, so that a kernel
+ * reading scratch nobody wrote computes garbage instead of passing by luck; RPT_NO_POOL wins over
+ * it.  The probe allocates nbytes (> 0) the way the kernels' scratch is allocated, copies them to
+ * out_host, frees the block and synchronises; *poison is the byte in force, -1 when poison is off. */
+int32_t rpt_debug_pool_probe(rpt_ctx* ctx, int64_t nbytes, uint8_t* out_host, int32_t* poison);
 /* the hipStream_t all work of this ctx is enqueued on (for HIP-event timing by the caller) */
 int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
 

@@ -46,19 +46,28 @@ size_t round_bytes(size_t b) {
 static hipError_t dev_alloc_impl(void** p, size_t bytes);
 // allocator debugging aids, read from the environment ONCE per process (library load):
 // RPT_NO_POOL = plain hipMalloc/hipFree, RPT_POOL_POISON=<byte> = fill every block handed out
-// (finds reads of uninitialised memory)
+// (finds reads of uninitialised memory: tests/test_gpu_pool_poison.py); RPT_NO_POOL wins
 static const bool g_no_pool = getenv("RPT_NO_POOL") != nullptr;
 static const int g_poison = getenv("RPT_POOL_POISON") ? atoi(getenv("RPT_POOL_POISON")) : -1;
 hipError_t dev_alloc(void** p, size_t bytes) {
   if (g_no_pool) return hipMalloc(p, bytes ? bytes : 1);
   const hipError_t e = dev_alloc_impl(p, bytes);
   if (e == hipSuccess && g_poison >= 0) {
+    // the whole block that is handed out, not just the request: a block is rounded up and a
+    // recycled one may be a quarter larger, and the "+ 16" slack reads land in that tail
+    size_t block = bytes ? bytes : 1;
+    {
+      std::lock_guard<std::mutex> lk(g_pool_mu);
+      auto it = g_pool_live.find(*p);
+      if (it != g_pool_live.end()) block = it->second.second;
+    }
     (void)hipDeviceSynchronize();
-    (void)hipMemset(*p, g_poison, bytes ? bytes : 1);
+    (void)hipMemset(*p, g_poison, block);
     (void)hipDeviceSynchronize();
   }
   return e;
 }
+static int dev_pool_poison() { return g_no_pool ? -1 : g_poison; }  // rpt_debug_pool_probe
 static hipError_t dev_alloc_impl(void** p, size_t bytes) {
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -391,6 +400,23 @@ int32_t rpt_ctx_trim(rpt_ctx* ctx) {
     RPT_HIP(hipSetDevice(ctx->device));
     RPT_HIP(stream_sync(ctx->stream));
     dev_trim();
+    return RPT_OK;
+  });
+}
+
+int32_t rpt_debug_pool_probe(rpt_ctx* ctx, int64_t nbytes, uint8_t* out_host, int32_t* poison) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ctx && out_host && poison, "NULL argument");
+    RPT_ARG(nbytes > 0, "nbytes must be positive");
+    RPT_HIP(hipSetDevice(ctx->device));
+    *poison = dev_pool_poison();
+    void* p = nullptr;
+    RPT_HIP(dev_alloc(&p, (size_t)nbytes));
+    const hipError_t e = hipMemcpyAsync(out_host, p, (size_t)nbytes, hipMemcpyDeviceToHost, ctx->stream);
+    dev_free(p);
+    RPT_HIP(e);
+    RPT_HIP(stream_sync(ctx->stream));   // the copy has landed; the block is reusable from here
     return RPT_OK;
   });
 }

@@ -3809,12 +3809,6 @@ __global__ void stream_init_kernel(unsigned long long* cmin, unsigned long long*
     poolcur[i] = 0u;
 }
 
-__global__ void fill_u64_kernel(unsigned long long* p, int64_t n, unsigned long long v) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = v;
-}
-
 // ---------------------------------------------------------------------------------------
 // HBM merge sort of arbitrary segments (rare path: pivot bins / leaves larger than LDS).
 // GSeg list lives in device memory; buf holds ids, sorted in place (tmp = scratch).

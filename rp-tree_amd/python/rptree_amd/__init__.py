@@ -171,6 +171,14 @@ class Context:
         check(lib().rpt_ctx_get_option(self._h, name.encode(), C.byref(v)))
         return v.value
 
+    def pool_probe(self, nbytes):
+        """(bytes, poison): what a fresh nbytes block of the device allocator holds, and the
+        RPT_POOL_POISON byte in force (-1 when poison is off) (rpt_debug_pool_probe)."""
+        buf = (C.c_uint8 * int(nbytes))()
+        poison = C.c_int32()
+        check(lib().rpt_debug_pool_probe(self._h, int(nbytes), buf, C.byref(poison)))
+        return bytes(buf), poison.value
+
     @property
     def stream(self):
         s = C.c_void_p()

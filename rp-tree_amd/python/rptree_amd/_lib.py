@@ -36,6 +36,7 @@ SYMBOLS = {
     "rpt_ctx_destroy": (i32, [vp]),
     "rpt_ctx_sync": (i32, [vp]),
     "rpt_ctx_trim": (i32, [vp]),
+    "rpt_debug_pool_probe": (i32, [vp, i64, vp, p_i32]),
     "rpt_ctx_stream": (i32, [vp, C.POINTER(vp)]),
     "rpt_ctx_set_option": (i32, [vp, C.c_char_p, i64]),
     "rpt_ctx_get_option": (i32, [vp, C.c_char_p, p_i64]),

@@ -103,6 +103,8 @@ def test_argument_errors_do_not_abort(rp):
     assert L.rpt_topology(10, 40, 1, None, 0, C.byref(cnt)) == -1      # RPT_E_ARG
     assert b"topology" in L.rpt_last_error()
     assert L.rpt_ctx_sync(None) == -1
+    poison = C.c_int32()
+    assert L.rpt_debug_pool_probe(None, 8, None, C.byref(poison)) == -1
 
 
 def test_int8_ranking_value_identity():
