@@ -38,6 +38,10 @@
 #include "common.h"
 #include "codes.h"
 
+// the device library's unsigned median of three: one v_med3_u32 (the sorting wave kernel's
+// cross-lane exchanges)
+extern "C" __device__ unsigned int __ockl_median3_u32(unsigned int, unsigned int, unsigned int);
+
 namespace rpt {
 namespace {
 
@@ -1202,19 +1206,31 @@ __global__ __launch_bounds__(256, 3) void wsub_kernel(
 // ---------------------------------------------------------------------------------------
 // wave-centric subtree kernel, SORT variant (round 3; replaces wsub_kernel's histogram select
 // on the default path, same interface, same results).  ONE WAVE per (tree, top node with
-// n <= kWCap), up to kWRmax levels.  The wave holds the node's <= 1024 points as 32-bit sort keys,
-// 16 CONSECUTIVE positions per lane (position = lane * 16 + r), and every level is ONE bitonic
-// sort of all of them:
-//     key = path of the point's node (left-aligned, depth + 1 bits) | monotone image of its
-//           projection on the level's hyperplane (21 - depth bits) | local index (10 bits)
-// so the nodes of the level stay where they are, each is sorted by projection, and the cut of
-// Internal.hs:495-505 is a matter of POSITION: left child = the first nh positions of the node,
-// thr / margins = the keys at positions nh, nh - 1, nh + 1, and the last level's sort leaves the
-// leaf buckets in the reference's order (children inherit the sorted order).  With consecutive
-// positions per lane the four closest exchange distances of the network are register-to-register
-// and only 21 of its 55 stages cross lanes (DPP quad permutes, ds_swizzle, v_permlane32_swap); a
-// lane whose block sorts descending keeps its keys complemented, so every exchange is a plain
-// min / max.  tools/micro/wsort_bench.hip: 0.105 ms per 32 768 sorts (C2's 32 x 1024 nodes).
+// n <= kWCap), up to kWRmax levels.  The wave holds 1024 positions as 32-bit sort keys, 16
+// CONSECUTIVE positions per lane (position = lane * 16 + r).  The node of depth d and index j owns
+// the ALIGNED block j of S = 1024 >> d positions: its n <= S points and S - n pads, and a level
+// is one bitonic sort INSIDE every block (ws_sort_blocks: phases 2 ... S of the 1024 network,
+// 55 / 45 / 36 / 28 / 21 stages at depths 0 ... 4) of
+//     point:  kSReal + (block index (depth bits) | monotone image of the projection on the
+//             level's hyperplane (21 - depth bits) | local index (10 bits))
+//     pad:    kSPadLo for S/2 - nh of the block's pads (nh = n >> 1), kSPadHi for the other
+//             S/2 - (n - nh); below and above every point, and equal to none in the bits above
+//             the local index
+// which leaves the block as [low pads | left child | right child | high pads]: the cut of
+// Internal.hs:495-505 falls on position S/2 of the block, each half-block holds one child and
+// is the child's block at the next depth, thr / margins are the keys at the fixed positions
+// S/2, S/2 - 1, S/2 + 1 (while the node has that many points), and the last level's sort leaves
+// the leaf buckets in the reference's order (children inherit the sorted order).  Pads have no
+// identity: every level hands a block's pads out anew, by position.  The block index in the key
+// orders nothing; it keeps equal images of neighbouring nodes apart in the tie pool below.  A
+// lane's sixteen positions lie in one block, so the node (size, first position of its points,
+// first output slot, leaf) is per-LANE state that one halving step per level takes to the child;
+// a leaf's points take their rank as the image, its pads stay in front of or behind them, so
+// the sorts of the deeper levels leave it alone.
+// With consecutive positions per lane the four closest exchange distances of the network are
+// register-to-register and only 21 of its 55 stages cross lanes (DPP quad permutes, ds_swizzle,
+// v_permlane32_swap); a lane whose block sorts descending keeps its keys complemented, so every
+// exchange is a plain min / max.  tools/micro/wsort_bench.hip times the block networks.
 // The image is weakly monotone (subtract, multiply by a positive scale, truncate), so a smaller
 // image means a smaller projection; positions whose image equals a neighbour's — about one pair
 // every third (wave, level) on continuous data, every real tie — are ordered EXACTLY afterwards:
@@ -1227,12 +1243,17 @@ __global__ __launch_bounds__(256, 3) void wsub_kernel(
 // ONE packed word per point (wpack_kernel below), gathered once, instead of a key gather per level.
 // Measured at C2 (32 x 1024 nodes of 977 points, 3 levels; rocprofv3, profiles/r03_*): 0.83 ms +
 // 0.19 ms (wpack) + 0.02 (wgeo) against wsub_kernel's 1.29 ms; without the packed words 1.25 ms:
-// the three key gathers per point (8.6 GB of sector traffic) bound both.  The PK kernel is VALU
-// bound: 9.4 k VALU instructions per wave (SQ_INSTS_VALU), 60 % of all SIMD cycles, 5.4 k of them
-// the three sorts.
+// the three key gathers per point (8.6 GB of sector traffic) bound both.  The PK kernel was VALU
+// bound when every level sorted all 1024 positions under a node-path prefix and an exchange was
+// min, max and a select: 9.4 k VALU instructions per wave (SQ_INSTS_VALU), 5.4 k of them the
+// three sorts, 0.68 ms.  Sorting inside the blocks: 0.62 ms; one v_med3_u32 per exchange on top:
+// 0.55 ms (profiles/wave_sort_blocks_*; the three sorts alone: 0.32 -> 0.18 ms in wsort_bench),
+// which leaves the kernel close to what its 2.2 GB of gathered sectors take.
 // grid = ceil(S*T/4) blocks of 256 threads.
 // ---------------------------------------------------------------------------------------
 constexpr int kSPool = 128;  // positions per level a wave can order exactly
+// sort keys: a point's 31 bits sit between the two pad keys, also in the bits above bit 9
+constexpr unsigned int kSReal = 0x40000000u, kSPadLo = 0u, kSPadHi = ~0u;
 constexpr int kPkBits = 21;  // image bits per level in a packed word (three levels per u64)
 constexpr int kPkLevels = 3;
 
@@ -1255,9 +1276,12 @@ __device__ __forceinline__ unsigned int ws_lane_xor(unsigned int v) {
   else return (unsigned int)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);
 }
 
-// ascending compare-exchange with the lane D away; upper = this lane keeps the larger key
+// ascending compare-exchange with the lane D away; upper = this lane keeps the larger key.
+// min(a, b) = med3(a, b, 0) and max(a, b) = med3(a, b, ~0): ONE v_med3_u32 per key with the
+// lane's side as its third operand, instead of min, max and a select
 template <int D>
 __device__ __forceinline__ void ws_cross(unsigned int (&k)[kWE], bool upper) {
+  const unsigned int side = upper ? ~0u : 0u;
 #pragma unroll
   for (int r = 0; r < kWE; ++r) {
     unsigned int a, b;
@@ -1269,8 +1293,7 @@ __device__ __forceinline__ void ws_cross(unsigned int (&k)[kWE], bool upper) {
       a = k[r];
       b = ws_lane_xor<D>(k[r]);
     }
-    const unsigned int mn = a < b ? a : b, mx = a < b ? b : a;
-    k[r] = upper ? mx : mn;
+    k[r] = __ockl_median3_u32(a, b, side);
   }
 }
 
@@ -1286,9 +1309,11 @@ __device__ __forceinline__ void ws_reg(unsigned int (&k)[kWE]) {
 }
 
 // phase KK of the bitonic network over index = lane * 16 + r: blocks of KK sorted, direction =
-// bit KK of the index (descending blocks are kept complemented)
+// bit KK of the index (descending blocks are kept complemented); the phase KK == S, the last one
+// of a sort inside aligned blocks of S, is ascending in every block
 template <int KK>
-__device__ __forceinline__ void ws_phase(unsigned int (&k)[kWE], int lane, unsigned int& flip) {
+__device__ __forceinline__ void ws_phase(unsigned int (&k)[kWE], int lane, unsigned int& flip,
+                                         int S) {
   if constexpr (KK < 16) {
 #pragma unroll
     for (int r = 0; r < kWE; ++r)
@@ -1300,7 +1325,7 @@ __device__ __forceinline__ void ws_phase(unsigned int (&k)[kWE], int lane, unsig
     for (int r = 0; r < kWE; ++r)
       if (r & KK) k[r] = ~k[r];
   } else {
-    const unsigned int want = (KK < 1024 && ((lane * 16) & KK)) ? ~0u : 0u;
+    const unsigned int want = ((lane * 16) & KK & (S - 1)) ? ~0u : 0u;  // KK & (S - 1): KK < S
     const unsigned int x = want ^ flip;
     flip = want;
 #pragma unroll
@@ -1318,36 +1343,30 @@ __device__ __forceinline__ void ws_phase(unsigned int (&k)[kWE], int lane, unsig
   }
 }
 
-__device__ __forceinline__ void ws_sort1024(unsigned int (&k)[kWE], int lane) {
+// Sorts every aligned block of S positions (S = 64 ... 1024, the same in all lanes) ascending:
+// phases 2 ... S of the 1024 network, 21 / 28 / 36 / 45 / 55 stages.  ONE chain of phases that
+// stops early — not one unrolled network per block size — so that the kernel's code stays the
+// size of a single network.
+__device__ __forceinline__ void ws_sort_blocks(unsigned int (&k)[kWE], int lane, int S) {
   unsigned int flip = 0;
-  ws_phase<2>(k, lane, flip);
-  ws_phase<4>(k, lane, flip);
-  ws_phase<8>(k, lane, flip);
-  ws_phase<16>(k, lane, flip);
-  ws_phase<32>(k, lane, flip);
-  ws_phase<64>(k, lane, flip);
-  ws_phase<128>(k, lane, flip);
-  ws_phase<256>(k, lane, flip);
-  ws_phase<512>(k, lane, flip);
-  ws_phase<1024>(k, lane, flip);  // ascending everywhere: the keys leave un-complemented
+  ws_phase<2>(k, lane, flip, S);
+  ws_phase<4>(k, lane, flip, S);
+  ws_phase<8>(k, lane, flip, S);
+  ws_phase<16>(k, lane, flip, S);
+  ws_phase<32>(k, lane, flip, S);
+  ws_phase<64>(k, lane, flip, S);
+  if (S >= 128) ws_phase<128>(k, lane, flip, S);
+  if (S >= 256) ws_phase<256>(k, lane, flip, S);
+  if (S >= 512) ws_phase<512>(k, lane, flip, S);
+  if (S >= 1024) ws_phase<1024>(k, lane, flip, S);
+  // the last phase was ascending everywhere: the keys leave un-complemented
 }
 
-// Node of a position, packed: offset inside the top node (bits 0-10) | size (11-21) | path,
-// left-aligned to the current depth (22-26) | leaf (27).  ws_step takes it one level down
-// (Internal.hs:289 leaf test, :495,503 halves); branch-free, a leaf only shifts its path.
-constexpr unsigned int kWsLeaf = 1u << 27;
-__device__ __forceinline__ unsigned int ws_step(unsigned int info, int p, int next_level, int L,
-                                                int min_leaf) {
-  const int off = (int)(info & 2047u), n = (int)((info >> 11) & 2047u);
-  const unsigned int path = (info >> 22) & 31u;
-  const bool leaf = (info & kWsLeaf) != 0;
-  const int nh = n >> 1;
-  const bool right = !leaf && p - off >= nh;
-  const int off2 = off + (right ? nh : 0);
-  const int n2 = leaf ? n : (right ? n - nh : nh);
-  const bool leaf2 = leaf || is_leaf_dev(next_level, n2, L, min_leaf);
-  return (unsigned int)off2 | ((unsigned int)n2 << 11) | ((2u * path + (right ? 1u : 0u)) << 22) |
-         (leaf2 ? kWsLeaf : 0u);
+// bits [a, b) of a lane's sixteen positions, for a range given relative to the lane's first one
+__device__ __forceinline__ unsigned int ws_range_mask(int a, int b) {
+  a = a < 0 ? 0 : (a > kWE ? kWE : a);
+  b = b < a ? a : (b > kWE ? kWE : b);
+  return (1u << b) - (1u << a);
 }
 
 // ---- packed images (PK): one u64 per point with the 21-bit images of the nl <= 3 levels a wave
@@ -1447,16 +1466,14 @@ __global__ __launch_bounds__(256, 3) void wsort_kernel(
     if constexpr (PK) W.store[i] = i < n_top ? packed[(int64_t)t * N + id] : 0ULL;
     else wids[i] = id;
   }
-  unsigned int k[kWE], info[kWE];
-  {
-    const unsigned int top = ((unsigned int)n_top << 11) |
-                             (is_leaf_dev(level0, n_top, L, min_leaf) ? kWsLeaf : 0u);
+  const int p0 = lane * kWE;  // the lane's first position
+  unsigned int k[kWE];
 #pragma unroll
-    for (int r = 0; r < kWE; ++r) {
-      k[r] = (unsigned int)(lane * kWE + r);
-      info[r] = top;
-    }
-  }
+  for (int r = 0; r < kWE; ++r) k[r] = (unsigned int)(p0 + r);
+  // the node of the lane's sixteen positions (one node: a block is at least 64 positions): size,
+  // first position of its points, their first output slot, leaf (the node, or an ancestor, is one)
+  int n = n_top, ra = 0, off = 0;
+  bool leaf = is_leaf_dev(level0, n_top, L, min_leaf);
   wsync();
 
   int depth = 0;
@@ -1464,11 +1481,11 @@ __global__ __launch_bounds__(256, 3) void wsort_kernel(
   for (; depth < kWRmax; ++depth) {
     const int level = level0 + depth;
     if (level >= L) break;
-    bool act = false;
-#pragma unroll
-    for (int r = 0; r < kWE; ++r) act = act || (lane * kWE + r < n_top && !(info[r] & kWsLeaf));
-    if (!__any(act)) break;
+    if (!__any(!leaf && n > 0)) break;
 
+    const int S = kWCap >> depth, B = p0 & ~(S - 1);  // the lane's block
+    // first position of the node's points after this level's sort: behind the low pads
+    const int lpB = leaf ? ra : B + (S >> 1) - (n >> 1);
     Keys<TK> K{Pt, N, level, nullptr};
     const TK* Pl = Pt + (int64_t)level * N;
     const int ib = 21 - depth;                  // image bits of this level's sort keys
@@ -1486,13 +1503,13 @@ __global__ __launch_bounds__(256, 3) void wsort_kernel(
       TK key[kWE];
 #pragma unroll
       for (int r = 0; r < kWE; ++r) {
-        const bool a = lane * kWE + r < n_top && !(info[r] & kWsLeaf);
+        const bool a = !leaf && (unsigned int)(p0 + r - ra) < (unsigned int)n;
         key[r] = a ? Pl[wids[k[r] & 1023u]] : (TK)0;
       }
       double kmn = __builtin_huge_val(), kmx = -__builtin_huge_val();
 #pragma unroll
       for (int r = 0; r < kWE; ++r)
-        if (lane * kWE + r < n_top && !(info[r] & kWsLeaf)) {
+        if (!leaf && (unsigned int)(p0 + r - ra) < (unsigned int)n) {
           const double v = (double)key[r];
           kmn = v < kmn ? v : kmn;
           kmx = v > kmx ? v : kmx;
@@ -1511,18 +1528,26 @@ __global__ __launch_bounds__(256, 3) void wsort_kernel(
         img[r] = c < imax ? c : imax;
       }
     }
-    // ---- b. sort keys: node path | image | local index; a leaf keeps its order ----
+    // ---- b. sort keys.  A point: kSReal + (block | image | local index); a leaf's points take
+    // their rank as the image and keep their order.  The block's other positions are pads: the
+    // first S/2 - nh of them (all those in front of a leaf's points) sort below every point, the
+    // rest above ----
+    {
+      const unsigned int kb = kSReal + ((unsigned int)(p0 >> (10 - depth)) << (ib + 10));
 #pragma unroll
-    for (int r = 0; r < kWE; ++r) {
-      const int p = lane * kWE + r;
-      const unsigned int path = (info[r] >> 22) & 31u;
-      const unsigned int im = (info[r] & kWsLeaf) ? (unsigned int)(p - (int)(info[r] & 2047u)) : img[r];
-      k[r] = p < n_top ? (path << (ib + 10)) | (im << 10) | (k[r] & 1023u)
-                       : ~0u;  // padding: behind every real key (their top bit is 0)
+      for (int r = 0; r < kWE; ++r) {
+        const int p = p0 + r, rel = p - ra;
+        const unsigned int im = leaf ? (unsigned int)rel : img[r];
+        const bool low = p < (rel < 0 ? lpB : lpB + n);
+        k[r] = (unsigned int)rel < (unsigned int)n ? kb + (im << 10) + (k[r] & 1023u)
+                                                   : (low ? kSPadLo : kSPadHi);
+      }
     }
-    ws_sort1024(k, lane);
+    ws_sort_blocks(k, lane, S);
+    ra = lpB;  // [low pads | left child | right child | high pads]: the cut sits on S/2
     // ---- c. positions whose image equals a neighbour's: exact order inside those runs ----
     {
+      const unsigned int rmask = ws_range_mask(ra - p0, ra - p0 + n);  // the lane's points
       unsigned int bits = 0;
       const unsigned int up = (unsigned int)__shfl_up((int)k[kWE - 1], 1);
       const unsigned int dn = (unsigned int)__shfl_down((int)k[0], 1);
@@ -1532,8 +1557,9 @@ __global__ __launch_bounds__(256, 3) void wsort_kernel(
         const bool eqp = r > 0 ? (k[r > 0 ? r - 1 : 0] >> 10) == me : (lane > 0 && (up >> 10) == me);
         const bool eqn = r + 1 < kWE ? (k[r + 1 < kWE ? r + 1 : r] >> 10) == me
                                      : (lane < 63 && (dn >> 10) == me);
-        if (k[r] != ~0u && (eqp || eqn)) bits |= 1u << r;
+        if (eqp || eqn) bits |= 1u << r;
       }
+      bits &= rmask;  // pads equal only each other in these bits
       if (__any(bits != 0)) {
         const int cnt = __popc(bits);
         int inc = cnt;
@@ -1583,28 +1609,20 @@ __global__ __launch_bounds__(256, 3) void wsort_kernel(
     }
     // ---- d. thresholds and margins: the keys at positions nh, nh - 1, nh + 1 of every node
     // (Internal.hs:496-501; n == 2 -> (p'[0], p'[1]); n == 1 -> p'[0] for all three).  One lane
-    // per (node, value): it works out the node's range from (n_top, depth, j) — the nodes of a
-    // depth are all Bins or all beyond a Tip of an ancestor, and sizes differ by at most one —,
-    // fetches the sort key at the position it needs by sixteen lane reads (its register index is
-    // data) and the true key by id ----
+    // per (node, value): node j is block j, so it takes the node's size and first position from
+    // the first lane of that block, fetches the sort key at the position it needs by sixteen
+    // lane reads (its register index is data) and the true key by id.  Position nh of the node
+    // is position S/2 of the block ----
     {
       const int j = lane / 3, which = lane - 3 * j;
-      int off = 0, n = n_top;
-      bool bin = lane < (3 << depth);
-      for (int b = depth - 1; b >= 0; --b) {  // the path of node j from the top node
-        bin = bin && !is_leaf_dev(level - 1 - b, n, L, min_leaf);
-        const int nhb = n >> 1;
-        if ((j >> b) & 1) {
-          off += nhb;
-          n -= nhb;
-        } else {
-          n = nhb;
-        }
-      }
-      bin = bin && !is_leaf_dev(level, n, L, min_leaf);
-      const int nh = n >> 1;
-      const int il = nh > 0 ? nh - 1 : 0, ih = nh + 1 < n ? nh + 1 : n - 1;
-      const int pt = off + (which == 0 ? nh : which == 1 ? il : ih);
+      const unsigned int sj = (unsigned int)__shfl(
+          (int)((unsigned int)n | ((unsigned int)ra << 11) | (leaf ? 1u << 22 : 0u)),
+          (j << (6 - depth)) & 63);
+      const int nj = (int)(sj & 2047u), raj = (int)((sj >> 11) & 2047u);
+      const bool bin = lane < (3 << depth) && !(sj >> 22) && nj > 0;
+      const int nh = nj >> 1;
+      const int il = nh > 0 ? nh - 1 : 0, ih = nh + 1 < nj ? nh + 1 : nj - 1;
+      const int pt = raj + (which == 0 ? nh : which == 1 ? il : ih);
       const int srcl = bin ? pt >> 4 : lane, srcr = pt & 15;
       unsigned int kt = 0;
 #pragma unroll
@@ -1624,9 +1642,19 @@ __global__ __launch_bounds__(256, 3) void wsort_kernel(
       const double vthr = __shfl(v, j * 3 < 64 ? j * 3 : 0), vlo = __shfl(v, j * 3 + 1 < 64 ? j * 3 + 1 : 0);
       if (bin && which == 0 && nh > 0 && !(vlo < vthr)) atomicAdd(tie_count, 1ULL);
     }
-    // ---- e. every position one level down ----
-#pragma unroll
-    for (int r = 0; r < kWE; ++r) info[r] = ws_step(info[r], lane * kWE + r, level + 1, L, min_leaf);
+    // ---- e. every lane to its half-block, a child of its node (Internal.hs:289 leaf test,
+    // :495,503 halves): the left child's points end at S/2, the right child's start there ----
+    if (!leaf) {
+      const int nh = n >> 1;
+      if (p0 & (S >> 1)) {
+        off += nh;
+        n -= nh;
+        ra = B + (S >> 1);
+      } else {
+        n = nh;
+      }
+      leaf = is_leaf_dev(level + 1, n, L, min_leaf);
+    }
     wsync();
   }
   if (overflow) {
@@ -1636,18 +1664,19 @@ __global__ __launch_bounds__(256, 3) void wsort_kernel(
     }
     return;
   }
-  // ---- every point to its slot: position = slot.  Leaves go to the final perm (in their final
-  // order), nodes still active after kWRmax levels to nxt.  Through LDS, so that the stores are
-  // coalesced ----
+  // ---- every point to its slot: the node's first slot + the point's rank in the node; pads
+  // have none.  Leaves go to the final perm (in their final order), nodes still active after
+  // kWRmax levels to nxt.  Through LDS, so that the stores are coalesced ----
   int idr[kWE];
 #pragma unroll
   for (int r = 0; r < kWE; ++r) {
-    const bool real = lane * kWE + r < n_top;
-    idr[r] = (real ? id_of(k[r] & 1023u) : 0) | ((info[r] & kWsLeaf) ? 0 : (int)0x80000000);
+    const bool real = (unsigned int)(p0 + r - ra) < (unsigned int)n;
+    idr[r] = (real ? id_of(k[r] & 1023u) : 0) | (leaf ? 0 : (int)0x80000000);
   }
   wsync();
 #pragma unroll
-  for (int r = 0; r < kWE; ++r) wids[lane * kWE + r] = idr[r];
+  for (int r = 0; r < kWE; ++r)
+    if ((unsigned int)(p0 + r - ra) < (unsigned int)n) wids[off + (p0 + r - ra)] = idr[r];
   wsync();
   int32_t* of = F + (int64_t)t * N + sg.off;
   int32_t* on = nxt + (int64_t)t * N + sg.off;

@@ -1,7 +1,9 @@
 // Cost of sorting 1024 u32 keys held 16 per lane by ONE wave (index = lane * 16 + r: the four
 // closest exchange distances are register-to-register, the other six cross lanes), the core of
-// the sort-based wave subtree kernel (split.hip).  Prints ms for `waves` independent sorts x `reps`
-// sorts per wave and checks the result of the last one on the host.
+// the sort-based wave subtree kernel (split.hip), as a whole and inside aligned blocks of 512 ...
+// 64 keys (the kernel's levels below the first: phases 2 ... S of the same network).  Prints, for
+// every block size, ms for `waves` independent sorts x `reps` sorts per wave and checks the result
+// of one sort on the host.
 //   hipcc -O3 --offload-arch=gfx950 wsort_bench.hip -o wsort_bench && ./wsort_bench
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -10,10 +12,23 @@
 #include <vector>
 
 constexpr int E = 16;
+// the device library's unsigned median of three: one v_med3_u32
+extern "C" __device__ unsigned int __ockl_median3_u32(unsigned int, unsigned int, unsigned int);
 
+// VARIANT 0: __shfl_xor exchanges; 1: DPP / ds_swizzle / v_permlane32_swap, then min, max and a
+// select; 2 (the kernel's): the same exchanges, then one v_med3_u32 (min = med3(a, b, 0), max =
+// med3(a, b, ~0))
 #ifndef VARIANT
-#define VARIANT 1
+#define VARIANT 2
 #endif
+__device__ __forceinline__ unsigned int pick(unsigned int a, unsigned int b, bool upper) {
+#if VARIANT == 2
+  return __ockl_median3_u32(a, b, upper ? ~0u : 0u);
+#else
+  const unsigned int mn = a < b ? a : b, mx = a < b ? b : a;
+  return upper ? mx : mn;
+#endif
+}
 template <int D>
 __device__ __forceinline__ unsigned int lane_xor(unsigned int v) {
 #if VARIANT == 0
@@ -31,14 +46,12 @@ __device__ __forceinline__ unsigned int lane_xor(unsigned int v) {
 // compare-exchange across lanes at lane distance D; upper = this lane keeps the larger key
 template <int D>
 __device__ __forceinline__ void cross_stage(unsigned int (&k)[E], bool upper) {
-#if VARIANT == 1
+#if VARIANT >= 1
   if constexpr (D == 32) {  // v_permlane32_swap: both halves see (low half's key, high half's key)
 #pragma unroll
     for (int r = 0; r < E; ++r) {
       const auto sw = __builtin_amdgcn_permlane32_swap(k[r], k[r], false, false);
-      const unsigned int a = sw[0], b = sw[1];
-      const unsigned int mn = a < b ? a : b, mx = a < b ? b : a;
-      k[r] = upper ? mx : mn;
+      k[r] = pick(sw[0], sw[1], upper);
     }
     return;
   }
@@ -46,8 +59,7 @@ __device__ __forceinline__ void cross_stage(unsigned int (&k)[E], bool upper) {
 #pragma unroll
   for (int r = 0; r < E; ++r) {
     const unsigned int o = lane_xor<D>(k[r]);
-    const unsigned int mn = k[r] < o ? k[r] : o, mx = k[r] < o ? o : k[r];
-    k[r] = upper ? mx : mn;
+    k[r] = pick(k[r], o, upper);
   }
 }
 
@@ -63,9 +75,10 @@ __device__ __forceinline__ void reg_stage(unsigned int (&k)[E]) {
 }
 
 // keys of lanes whose block sorts descending are kept complemented, so every exchange is an
-// ascending one; phase KK (block size) decides the direction: bit KK of index = lane * 16 + r
+// ascending one; phase KK (block size) decides the direction: bit KK of index = lane * 16 + r,
+// except in the last phase of a sort inside blocks of S (KK == S), ascending in every block
 template <int KK>
-__device__ __forceinline__ void phase(unsigned int (&k)[E], int lane, unsigned int& flip) {
+__device__ __forceinline__ void phase(unsigned int (&k)[E], int lane, unsigned int& flip, int S) {
   if constexpr (KK < 16) {
     // direction depends on r only: descending blocks are handled by swapping the roles
 #pragma unroll
@@ -79,7 +92,7 @@ __device__ __forceinline__ void phase(unsigned int (&k)[E], int lane, unsigned i
     for (int r = 0; r < E; ++r)
       if (r & KK) k[r] = ~k[r];
   } else {
-    const unsigned int want = (KK < 1024 && ((lane * 16) & KK)) ? ~0u : 0u;
+    const unsigned int want = ((lane * 16) & KK & (S - 1)) ? ~0u : 0u;
     const unsigned int x = want ^ flip;
     flip = want;
 #pragma unroll
@@ -97,22 +110,25 @@ __device__ __forceinline__ void phase(unsigned int (&k)[E], int lane, unsigned i
   }
 }
 
-__device__ __forceinline__ void sort1024(unsigned int (&k)[E], int lane) {
+// every aligned block of S keys ascending (S = 64 ... 1024): one chain of phases that stops early
+__device__ __forceinline__ void sort_blocks(unsigned int (&k)[E], int lane, int S) {
   unsigned int flip = 0;
-  phase<2>(k, lane, flip);
-  phase<4>(k, lane, flip);
-  phase<8>(k, lane, flip);
-  phase<16>(k, lane, flip);
-  phase<32>(k, lane, flip);
-  phase<64>(k, lane, flip);
-  phase<128>(k, lane, flip);
-  phase<256>(k, lane, flip);
-  phase<512>(k, lane, flip);
-  phase<1024>(k, lane, flip);  // want = 0: keys leave un-complemented
+  phase<2>(k, lane, flip, S);
+  phase<4>(k, lane, flip, S);
+  phase<8>(k, lane, flip, S);
+  phase<16>(k, lane, flip, S);
+  phase<32>(k, lane, flip, S);
+  phase<64>(k, lane, flip, S);
+  if (S >= 128) phase<128>(k, lane, flip, S);
+  if (S >= 256) phase<256>(k, lane, flip, S);
+  if (S >= 512) phase<512>(k, lane, flip, S);
+  if (S >= 1024) phase<1024>(k, lane, flip, S);
+  // the last phase had want = 0: keys leave un-complemented
 }
 
 __global__ __launch_bounds__(256) void bench(const unsigned int* __restrict__ in,
-                                             unsigned int* __restrict__ out, int reps) {
+                                             unsigned int* __restrict__ out, int reps,
+                                             int S) {
   const int lane = threadIdx.x & 63;
   const size_t w = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   unsigned int k[E];
@@ -130,7 +146,7 @@ __global__ __launch_bounds__(256) void bench(const unsigned int* __restrict__ in
 #pragma unroll
       for (int r = 0; r < E; ++r) k[r] = k[r] * 2654435761u + (unsigned int)(lane * 16 + r);
     }
-    sort1024(k, lane);
+    sort_blocks(k, lane, S);
   }
   uint4* o = reinterpret_cast<uint4*>(out + w * 1024 + lane * 16);
 #pragma unroll
@@ -153,24 +169,29 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
-  for (int pass = 0; pass < 3; ++pass) {
-    hipEventRecord(e0, 0);
-    hipLaunchKernelGGL(bench, dim3(waves / 4), dim3(256), 0, 0, din, dout, reps);
-    hipEventRecord(e1, 0);
-    hipEventSynchronize(e1);
-    float ms = 0;
-    hipEventElapsedTime(&ms, e0, e1);
-    printf("waves %d, %d sorts of 1024 u32 per wave: %.3f ms\n", waves, reps, ms);
-  }
-  hipLaunchKernelGGL(bench, dim3(waves / 4), dim3(256), 0, 0, din, dout, 1);
   std::vector<unsigned int> o(h.size());
-  hipMemcpy(o.data(), dout, o.size() * 4, hipMemcpyDeviceToHost);
   size_t bad = 0;
-  for (int w = 0; w < waves; ++w) {
-    std::vector<unsigned int> ref(h.begin() + (size_t)w * 1024, h.begin() + (size_t)(w + 1) * 1024);
-    std::sort(ref.begin(), ref.end());
-    for (int i = 0; i < 1024; ++i) bad += ref[i] != o[(size_t)w * 1024 + i];
+  for (int S = 1024; S >= 64; S >>= 1) {
+    for (int pass = 0; pass < 3; ++pass) {
+      hipEventRecord(e0, 0);
+      hipLaunchKernelGGL(bench, dim3(waves / 4), dim3(256), 0, 0, din, dout, reps, S);
+      hipEventRecord(e1, 0);
+      hipEventSynchronize(e1);
+      float ms = 0;
+      hipEventElapsedTime(&ms, e0, e1);
+      printf("waves %d, %d sorts of 1024 u32 in blocks of %d per wave: %.3f ms\n", waves, reps, S, ms);
+    }
+    hipLaunchKernelGGL(bench, dim3(waves / 4), dim3(256), 0, 0, din, dout, 1, S);
+    if (hipMemcpy(o.data(), dout, o.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+      printf("blocks of %d: the device reported an error\n", S);
+      return 2;
+    }
+    size_t b = 0;
+    std::vector<unsigned int> ref(h);
+    for (size_t i = 0; i < ref.size(); i += S) std::sort(ref.begin() + i, ref.begin() + i + S);
+    for (size_t i = 0; i < ref.size(); ++i) b += ref[i] != o[i];
+    printf("blocks of %d: mismatches after one sort: %zu\n", S, b);
+    bad += b;
   }
-  printf("mismatches after one sort: %zu\n", bad);
   return bad != 0;
 }
