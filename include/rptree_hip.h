@@ -299,16 +299,27 @@ int32_t rpt_knnh_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
 
 /* Dense f64 data: the distances returned are metricDDL2's left fold of (u - v)^2 (Internal.hs:
  * 403-406) with every square correctly rounded, and the results are selected and ordered on those
- * values: candidates are RANKED on a lane-parallel sum (the same value to an ulp), the best
- * k + 8 of them (or the certified k + max(6, k/2) of the f32 prefilter) are evaluated again as the
- * fold and the k best of those by (distance, candidate position) are returned — more than 8
- * DIFFERENT rows within a few ulp of the k-th distance would be needed to change the membership
- * (copies of one row keep their order under both sums).
+ * values, on every query path: the answer is the k best of ALL candidates by (fold distance, NaN
+ * last, candidate position) under the duplicate rule, ids and distance bits.
+ * How: candidates are RANKED on a lane-parallel sum of the same squares (the same value to a few
+ * ulp).  The entries of the best k + 8 DIFFERENT ids by that value (copies of one id, the same point
+ * found by several trees, do not count against the 8; at most as many entries as the kernel's list
+ * holds), or the kept entries of a prefilter tier, are evaluated again as the fold and the k best of
+ * those are written.  Then the cut is certified per query: both sums add the same d non-negative
+ * products, so they differ by less than (d + 4) 2^-53 relative, and when the k-th fold distance is
+ * strictly below the lane-parallel value of the last kept entry less that bound, no candidate left
+ * out can belong to the answer.  A query that is not certified (more different rows tie at the
+ * cut than were kept, +inf or NaN at the cut) is answered again by an exact kernel that ranks every
+ * candidate on the fold itself, one thread per row, with no margin; so is a query whose prefilter
+ * cut could not be certified.  rpt_knn_last_uncertified counts both; the context option
+ * knn_l2_exact sends every query to the exact kernel.  rpt_brute_knn_*, the truth of
+ * rpt_recall_hits_host included, follow the same rule.  RPT_KNN_VOTE alone keeps the uncertified
+ * margin of 8 (the exact kernel does not vote).
  * `(** 2)` is libm's pow in a GHC build: where pow(t, 2) is correctly rounded these are its bits;
  * glibc >= 2.28 returns a neighbouring double for about 9 arguments in 10 000, which moves the last
  * bit of about one distance in a thousand (tests/test_oracle_kat.py measures it on the test box).
- * RPT_KNN_DEDUP_DISTANCE collapses entries whose distances are equal under both sums; two rows one
- * ulp apart under one of them and equal under the other may or may not collapse. */
+ * RPT_KNN_DEDUP_DISTANCE collapses entries whose FOLD distances are equal (knnPQ's nub on the values
+ * returned): k entries when the candidates hold k different values, strictly ascending. */
 /* knn (RPTree.hs:168-176) with distf = metricL2 (Internal.hs:318, metricDDL2 :403-406 /
  * true Euclidean distance for CSR data, evaluated as |q|^2 + sum over the row's nonzeros of
  * ((x_j - q_j)^2 - q_j^2): absolute error about 1e-8 |q|): per query the k best (distance, id), stable in
@@ -336,10 +347,12 @@ int32_t rpt_knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
                     double* dist_dev, int32_t* count_dev);
 /* statistics of the last rpt_knn_* call: total candidates visited (sum over queries) */
 int32_t rpt_knn_last_candidates(rpt_ctx* ctx, int64_t* total);
-/* ... and how many of its queries the f32 prefilter could not certify (equal distances at its
- * cut) and were answered again with all-f64 distances; 0 when the prefilter was not used.  After
- * an RPT_KNN_METRIC_COSINE / _INNER call: the queries whose cut could not be certified and that the
- * exact kernel answered (all of them with the option knn_metric_exact); this reads the count from
+/* ... and how many of its queries were answered again exactly because their cut could not be
+ * certified: on dense f64 rows under L2 the queries of a prefilter tier (equal distances at its
+ * cut) and of the all-f64 kernels (different rows that tie at the cut) that the exact kernel answered
+ * (every query with the option knn_l2_exact); on f32 / CSR rows the prefilter's, answered by the
+ * all-exact kernel.  After an RPT_KNN_METRIC_COSINE / _INNER call: the queries the metric's exact
+ * kernel answered (all of them with the option knn_metric_exact).  This may read the count from
  * the device, so it waits for the call's kernels to finish */
 int32_t rpt_knn_last_uncertified(rpt_ctx* ctx, int64_t* total);
 /* ... and how many took the in-kernel second attempt (a cut the first, narrower selection could not

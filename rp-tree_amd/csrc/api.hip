@@ -246,6 +246,7 @@ const OptDesc kOptions[] = {
     {"knn_kp16", &rpt_options::knn_kp16},
     {"knn_no_pre8", &rpt_options::knn_no_pre8},
     {"knn_kp8", &rpt_options::knn_kp8},
+    {"knn_l2_exact", &rpt_options::knn_l2_exact},
     {"knn_metric_exact", &rpt_options::knn_metric_exact},
     {"knn_csr_pre32", &rpt_options::knn_csr_pre32},
     {"knn_general", &rpt_options::knn_general},

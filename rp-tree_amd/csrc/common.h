@@ -163,6 +163,7 @@ struct rpt_options {
   int64_t knn_kp16 = 0;         // kNN: entries the f16 prefilter keeps (0 = k + max(8, k / 2))
   int64_t knn_no_pre8 = 0;      // kNN: never rank on the int8 shadow (the half shadow is the first tier)
   int64_t knn_kp8 = 0;          // kNN: entries the int8 prefilter keeps (0 = k + max(48, k), capped by the kernel variant)
+  int64_t knn_l2_exact = 0;      // kNN, L2 on dense f64 rows: every query on the exact kernel (no certified cut)
   int64_t knn_metric_exact = 0;  // kNN, cosine / inner product: every query on the exact kernel (no certified cut)
   int64_t knn_csr_pre32 = 0;    // kNN: rank CSR f64 rows on their (u16 column, f32 value) shadow
   int64_t knn_general = 0;      // kNN: unfused general path

@@ -552,15 +552,42 @@ __device__ inline double leftfold_distance(const double* __restrict__ x, const d
   return sqrt(acc);
 }
 
-// Entries a dense f64 path that RANKS on butterfly sums keeps beyond k before the final selection:
-// the k + kLfMargin best by (butterfly distance, position) are re-evaluated as the reference's left
-// fold and the k best of THOSE by (fold distance, position) are the answer, so a candidate whose
-// two sums round differently near the k-th distance cannot change the membership of the result
-// (RPTree.hs:174 ranks ALL candidates on the fold).  It would take more than kLfMargin DIFFERENT
-// rows within a few ulp of the k-th distance to defeat this (copies of one row — the same point
-// found by several trees — have equal sums of both kinds and keep their order); the prefiltered
-// path certifies its cut per query instead.
+// Dense f64 rows under L2: the batched distance passes RANK on butterfly sums, the answer is defined
+// on the reference's left fold (RPTree.hs:174 ranks ALL candidates on the fold).  A ranking path
+// keeps the entries of the best k + kLfMargin DIFFERENT ids by (butterfly distance, position) — copies
+// of one id, the same point found by several trees, have one value under either sum and must not
+// use the margin up — at most the capacity of its list; those are evaluated again as the fold and
+// the k best of THOSE by (fold distance, position) are written.  Then the cut is CERTIFIED per query
+// (l2_cut_certified); a query that is not certified is answered again by the exact kernel
+// (knn_metric_kernel<double, kMetricL2, true>: every candidate on the fold, no margin), so the
+// answer is the definition however many different rows tie at the k-th distance.
 constexpr int kLfMargin = 8;
+
+// The certified cut.  Both sums of a row add the SAME rounded, non-negative products p_j = t_j t_j,
+// t_j = fl(x_j - q_j) (-ffp-contract=off: no FMA), from +0 in different orders.  Whatever the order,
+// the d terms are merged by d - 1 additions that round (adding a zero is exact), so a term passes
+// through at most d - 1 of them, and with no cancellation the computed sum is S (1 + t), S = sum p_j
+// exactly, |t| <= g = (d - 1) u / (1 - (d - 1) u), u = 2^-53 (Higham, Accuracy and Stability, (4.4)).
+// Underflow adds nothing: the products are the same numbers in both sums, an addition whose result
+// is subnormal is exact, and so is the root's operand.  The root is correctly rounded: fold = sqrt(S
+// (1 + t1)) (1 + e1), butterfly = sqrt(S (1 + t2)) (1 + e2), |e| <= u, hence
+//     fold / butterfly >= sqrt((1 - g) / (1 + g)) (1 - u) / (1 + u) >= 1 - g - 2 g^2 - 2 u
+//                      >= 1 - (d + 2) u            (d <= 2^20: g <= (d - 1) u + u / 2, 2 g^2 <= u / 2).
+// With E = (d + 4) u, 1 - E is exact (a multiple of 2^-53 below 1) and the product b (1 - E) rounds
+// once: fl(b (1 - E)) <= b (1 - (d + 3) u).  Every candidate left out of the kept set has a
+// butterfly value >= b, the value of the LAST kept entry, so its fold is >= b (1 - (d + 2) u), which
+// is above fl(b (1 - E)).  A query is certified when nothing was left out (copies of a kept id under
+// a duplicate rule aside: one id, one value), or when k entries were written and the k-th of them,
+// by the fold, is STRICTLY below fl(b (1 - E)): no candidate left out can belong to the answer nor,
+// under dedup 2, equal a value in it.  b must be finite (+inf, also what a NaN is ranked as, orders
+// nothing among those left out) and a NaN fold value fails the comparison: such a query is not certified.
+__device__ inline bool l2_cut_certified(bool cut, int written, int k, double kth_fold, double b, int d) {
+  if (!cut) return true;
+  if (written != k || d > (1 << 20) || !(b < __longlong_as_double(0x7ff0000000000000LL))) return false;
+  return kth_fold < b * (1.0 - (double)(d + 4) * 0x1p-53);
+}
+
+__device__ int merge_distinct(Entry* buf, int filled, int kk, int cap, bool ided, int* scratch, int* s_out);
 
 // ---- cosine and inner-product metrics (RPT_KNN_METRIC_COSINE / _INNER) ----
 // The reference's knn takes the distance as an argument (RPTree.hs:168-176); these two are
@@ -573,7 +600,8 @@ constexpr int kMetricL2 = 0, kMetricCosine = 1, kMetricInner = 2;
 
 template <int METRIC>
 __device__ __forceinline__ double metric_value(double dot, double xx, double qq) {
-  if constexpr (METRIC == kMetricInner) return -dot;
+  if constexpr (METRIC == kMetricL2) return dot;  // (the exact L2 kernel: the value is the fold itself)
+  else if constexpr (METRIC == kMetricInner) return -dot;
   else return 1.0 - dot / (sqrt(xx) * sqrt(qq));
 }
 
@@ -670,12 +698,16 @@ __global__ __launch_bounds__(256) void topk_dense_kernel(
     const TD* __restrict__ X, int d, const TD* __restrict__ Q, const int32_t* __restrict__ perm,
     const Range* __restrict__ ranges, const int64_t* __restrict__ rng_off, int T, int64_t N,
     int identity, int k, int dedup, int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
-    int32_t* __restrict__ out_cnt) {
+    int32_t* __restrict__ out_cnt, int32_t* __restrict__ unc /* f64: the queries whose cut is not certified */,
+    unsigned long long* __restrict__ unc_count) {
   typedef typename AccOf<TD>::type TA;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Entry* buf = reinterpret_cast<Entry*>(smem);                       // [kBuf]
   int* scratch = reinterpret_cast<int*>(smem + sizeof(Entry) * kBuf);  // [kBuf]
   TA* qs = reinterpret_cast<TA*>(smem + (sizeof(Entry) + 4) * kBuf);   // [d]
+  __shared__ int s_merge[2], s_w;
+  __shared__ double s_last;
+  constexpr bool F64 = std::is_same<TD, double>::value;
   const int64_t q = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int j = threadIdx.x; j < d; j += blockDim.x) qs[j] = ld<TD>(Q + q * d + j);
@@ -684,8 +716,18 @@ __global__ __launch_bounds__(256) void topk_dense_kernel(
   int best = 0;    // valid best entries at buf[0, best)
   int filled = 0;  // entries in buf (block-uniform)
   const int cap = kBuf;
-  // f64: the running list keeps kLfMargin entries more than k (see kLfMargin)
-  const int kk = std::is_same<TD, double>::value ? (k + kLfMargin < kBuf / 2 ? k + kLfMargin : kBuf / 2) : k;
+  // f64: the running list keeps the entries of k + kLfMargin different ids (see kLfMargin)
+  const int kk = F64 ? (k + kLfMargin < kBuf / 2 ? k + kLfMargin : kBuf / 2) : k;
+  bool cut = false;  // f64: some candidate was left out of the list (other than a same-id copy)
+  auto merge = [&]() -> int {
+    if constexpr (F64) {
+      const int w = merge_distinct(buf, filled, kk, kBuf / 2, dedup != 0, scratch, s_merge);
+      cut = cut || s_merge[1] != 0;
+      return w;
+    } else {
+      return merge_best(buf, filled, kk, dedup, scratch);
+    }
+  };
   const int64_t r0 = identity ? 0 : rng_off[q * T];
   const int64_t r1 = identity ? 1 : rng_off[(q + 1) * T];
   for (int64_t r = r0; r < r1; ++r) {
@@ -730,23 +772,24 @@ __global__ __launch_bounds__(256) void topk_dense_kernel(
       done += take;
       __syncthreads();
       if (filled == cap) {
-        best = merge_best(buf, filled, kk, dedup, scratch);
+        best = merge();
         filled = best;
         __syncthreads();
       }
     }
   }
   if (filled > best || best == 0) {
-    best = merge_best(buf, filled, kk, dedup, scratch);
+    best = merge();
     __syncthreads();
   }
-  if constexpr (std::is_same<TD, double>::value) {
+  if constexpr (F64) {
     // the kept entries' distances again as the reference's left fold, the k best of those in the
     // order of those values (ties by candidate position): finalize_leftfold
     double* lf = reinterpret_cast<double*>(scratch);  // [kBuf] ints = kBuf / 2 doubles >= kk
     int* ids2 = reinterpret_cast<int*>(buf + kBuf / 2);  // the upper half of buf is free now:
     int* pos2 = ids2 + kBuf / 2;                          // 3 x kBuf / 2 ints fit its 16 KB
     int* order = pos2 + kBuf / 2;
+    const double blast = best > 0 ? buf[best - 1].dist : 0.0;  // (buf's lower half stays)
     for (int i = threadIdx.x; i < best; i += blockDim.x) {
       ids2[i] = buf[i].id;
       pos2[i] = buf[i].pos;
@@ -754,7 +797,10 @@ __global__ __launch_bounds__(256) void topk_dense_kernel(
     __syncthreads();
     finalize_leftfold(reinterpret_cast<const double*>(X), d, reinterpret_cast<const double*>(qs), best, k,
                       dedup, lf, order, ids2, pos2, (int)threadIdx.x, (int)blockDim.x,
-                      [] { __syncthreads(); }, q, out_ids, out_dist, out_cnt);
+                      [] { __syncthreads(); }, q, out_ids, out_dist, out_cnt, nullptr, 0.0, &s_w, &s_last);
+    // (thread 0 wrote the answer and s_w / s_last)
+    if (threadIdx.x == 0 && !l2_cut_certified(cut, s_w, k, s_last, blast, d))
+      unc[atomicAdd(unc_count, 1ULL)] = (int32_t)q;
     return;
   }
   for (int i = threadIdx.x; i < k; i += blockDim.x) {
@@ -1011,6 +1057,9 @@ __device__ int merge_distinct(Entry* buf, int filled, int kk, int cap, bool ided
 // (metric_cut_slack); when it is not, q is appended to the list unc (*unc_count entries).
 //   EXACT = true (the queries of that list, grid-stride; unc == nullptr: all nq): every value is the left fold (one
 // thread per row) and merge_best selects on those with no margin; the answer is the definition.
+//   METRIC = kMetricL2 (f64 rows, EXACT only): the values are metricDDL2's fold, leftfold_distance.  It
+// answers the queries whose cut no L2 path on dense f64 rows could certify (see kLfMargin), the
+// prefilter tiers' among them, and every query under the option knn_l2_exact.
 // LDS: buf [nbuf] entries (a power of two >= kk + kMB), scratch [nbuf] ints, the batch (kMB x 16 B),
 // the query [d] doubles.
 template <class TD, int METRIC, bool EXACT>
@@ -1078,7 +1127,11 @@ __global__ __launch_bounds__(256) void knn_metric_kernel(
         }
       }
       __syncthreads();
-      if constexpr (EXACT) {
+      if constexpr (METRIC == kMetricL2) {  // (f64 rows, EXACT only: metricDDL2 itself)
+        static_assert(METRIC != kMetricL2 || (EXACT && std::is_same<TD, double>::value), "L2: the exact variant on f64 rows");
+        for (int i = threadIdx.x; i < nb; i += blockDim.x)
+          cd[i] = leftfold_distance(reinterpret_cast<const double*>(X) + (int64_t)cid[i] * d, qs, d);
+      } else if constexpr (EXACT) {
         for (int i = threadIdx.x; i < nb; i += blockDim.x) cd[i] = leftfold_dot<TD>(X + (int64_t)cid[i] * d, qs, d);
       } else {
         batch_distances<TD, double, 8, false, double, true>(X, d, cid, cd, qs, 0, nb, wave, 4, lane);
@@ -1710,6 +1763,8 @@ __global__ __launch_bounds__(256, 3) void knn_fused_kernel(
       (reinterpret_cast<uintptr_t>(qs32 + d) + 15) & ~(uintptr_t)15);  // [kVoteCap]
   __shared__ int s_nr, s_nc;
   __shared__ double s_qn;
+  __shared__ int s_fw;         // finalize_leftfold: entries written ...
+  __shared__ double s_flast;   // ... and the last of them (the certificate of the f64 L2 cut)
   __shared__ double s_red_d[8];
   __shared__ int s_red_p[8], s_red_i[8];
   __shared__ int s_wk[4];
@@ -2031,7 +2086,11 @@ __global__ __launch_bounds__(256, 3) void knn_fused_kernel(
     __syncthreads();  // s_mm is the next batch's threshold exchange
     return nvalid < ksel ? nvalid : ksel;
   };
-  auto select = [&](int fill, int ksel, int dedup) -> int {
+  // kdist > 0 (dense f64 rows, see kLfMargin): keep the entries of the best kdist DIFFERENT ids, at
+  // most ksel entries; l2cut is set when a candidate is left out for that (a same-id copy under a
+  // duplicate rule is not one; a full list counts as a cut: the batch may hold more)
+  bool l2cut = false;
+  auto select = [&](int fill, int ksel, int dedup, int kdist) -> int {
     constexpr int E = kFC / 256;
     double dd[E];
     int pp[E];
@@ -2044,7 +2103,7 @@ __global__ __launch_bounds__(256, 3) void knn_fused_kernel(
       if (dd[e] != dd[e]) dd[e] = __longlong_as_double(0x7ff0000000000000LL);
       pp[e] = i < fill ? cpos[i] : -1;
     }
-    int nb = 0, par = 0;
+    int nb = 0, par = 0, nd = 0;
     double last_d = -1.0;
     while (nb < ksel) {
       double bd = __longlong_as_double(0x7ff0000000000000LL);
@@ -2085,11 +2144,19 @@ __global__ __launch_bounds__(256, 3) void knn_fused_kernel(
 #pragma unroll
       for (int e = 0; e < E; ++e)
         if (bi == tid + 256 * e) pp[e] = -1;  // consumed
-      bool keep = true;
+      bool keep = true, copy = false;
       if (dedup == 2 && nb > 0 && bd == last_d) keep = false;  // knnPQ: one per distance
-      else if (dedup && bd == last_d)  // same id => same distance: duplicates are among equal dist
+      else if ((dedup || kdist > 0) && bd == last_d)  // same id => same distance: duplicates are among equal dist
         for (int j = nb - 1; j >= 0 && bdist[j] == bd; --j)
-          if (bid[j] == cid[bi]) keep = false;
+          if (bid[j] == cid[bi]) copy = true;
+      if (dedup && copy) keep = false;
+      if (keep && kdist > 0 && !copy) {
+        if (nd == kdist) {  // one different id more than the kept set holds (uniform)
+          l2cut = true;
+          break;
+        }
+        ++nd;
+      }
       if (keep) {
         if (tid == 0) {
           bdist[nb] = bd;
@@ -2100,6 +2167,7 @@ __global__ __launch_bounds__(256, 3) void knn_fused_kernel(
         last_d = bd;
       }
     }
+    if (kdist > 0 && nb == ksel) l2cut = true;
     __syncthreads();  // the winners are visible; cdist / cid / cpos may be refilled
     return nb;
   };
@@ -2242,10 +2310,15 @@ retry_wider:
       batch_distances<TD, TA, (sizeof(TD) < 8 ? 16 : 8)>(X, d, cid, cdist, qs, first_new, fill, wave, 4, lane);
     __syncthreads();
     KSTAMP();  // distances
-    // dense f64 rows ranked on butterfly sums keep kLfMargin entries more (finalize_leftfold)
-    const int ksel = (!CSR && std::is_same<TD, double>::value) ? k + kLfMargin : k;
+    // dense f64 rows ranked on butterfly sums keep the entries of k + kLfMargin different ids (see
+    // kLfMargin; duplicates kept: as many entries as the list holds): the duplicate rule while
+    // streaming is "each id once" (dedup 2 collapses on the FOLD values, in finalize_leftfold).
+    // Voting mode: the ids are distinct, the margin is the uncertified one (no exact variant votes).
+    constexpr bool L2F64 = !PRE32 && !CSR && std::is_same<TD, double>::value;
+    const int kdist = L2F64 && vote == 0 ? k + kLfMargin : 0;
+    const int ksel = L2F64 ? (kdist > 0 && dedup == 0 ? kBKx : k + kLfMargin) : k;
     const int nb = PRE32 ? select_packed(fill, k1, best, pb0) : pack32 ? select_packed(fill, k, best, pb0)
-                                                                    : select(fill, ksel, dedup);
+                                                                    : select(fill, ksel, kdist > 0 && dedup ? 1 : dedup, kdist);
     best = nb;
     KSTAMP();  // selection
     if (vote > 0 ? vsrc >= nc_tot : pos_base >= nc_tot) break;
@@ -2270,7 +2343,7 @@ retry_wider:
     batch_distances_csr<TD>(csr.rowptr, csr.col, static_cast<const TD*>(csr.val), csr.nnz, cid,
                             cdist, qsd, s_qn, 0, m, wave, lane);
     __syncthreads();
-    best = select(m, k, 0);
+    best = select(m, k, 0, 0);
     if (cut && best > 0) {
       const double u = 5.9604644775390625e-08;
       const double chain = (double)(4 * ((csr.max_rowlen + 63) / 64) + 5);
@@ -2376,7 +2449,8 @@ retry_wider:
           __syncthreads();
           goto retry_wider;
         }
-        if (tid == 0) {  // flag 2: the host re-runs this query with the all-f64 kernel
+        if (tid == 0) {  // flag 2: the host answers this query again exactly (f64 rows: the exact
+                         // kernel over the plan, see kLfMargin; f32 rows: the all-exact fused kernel)
           ovf_flags[q] = 2u;
           atomicAdd(cand_total + 1, 1ULL);
         }
@@ -2388,9 +2462,16 @@ retry_wider:
     // f64 rows ranked on butterfly sums: the k + kLfMargin kept entries again as the reference's
     // left fold, the k best of THOSE in the order of those values (finalize_leftfold)
     __syncthreads();
+    const double blast = best > 0 ? bdist[best - 1] : 0.0;  // the butterfly value of the last kept entry
     finalize_leftfold(reinterpret_cast<const double*>(X), d, reinterpret_cast<const double*>(qs), best, k,
                       dedup, cdist, cpos, bid, bpos, tid, 256, [] { __syncthreads(); }, q, out_ids,
-                      out_dist, out_cnt);
+                      out_dist, out_cnt, nullptr, 0.0, &s_fw, &s_flast);
+    // (thread 0 wrote the answer, s_fw and s_flast.)  Flag 2: the host answers this query again
+    // with the exact kernel (l2_cut_certified)
+    if (tid == 0 && vote == 0 && !l2_cut_certified(l2cut, s_fw, k, s_flast, blast, d)) {
+      ovf_flags[q] = 2u;
+      atomicAdd(cand_total + 1, 1ULL);
+    }
     return;
   }
   for (int i = tid; i < k; i += 256) {
@@ -2654,7 +2735,9 @@ __global__ __launch_bounds__(256, 3) void knn_fused_wave_kernel(
     wave_sync();
     return nb;
   };
-  auto wselect = [&](int fill, int first_new, int pb0, int ksel, int dedup) -> int {
+  // kdist > 0: the entries of the best kdist different ids, l2cut (knn_fused_kernel's select)
+  bool l2cut = false;
+  auto wselect = [&](int fill, int first_new, int pb0, int ksel, int dedup, int kdist) -> int {
     // ---- the lane's entries: distance and candidate position (-1 = none / consumed) ----
     double dd[E];
     int pp[E];
@@ -2667,7 +2750,7 @@ __global__ __launch_bounds__(256, 3) void knn_fused_wave_kernel(
     }
     wave_sync();  // bpos is rewritten below
     // ---- selection: k rounds of wave-wide arg-min by (distance, position) ----
-    int nb = 0;
+    int nb = 0, nd = 0;
     double last_d = -1.0;
     while (nb < ksel) {
       double bd = kInf;
@@ -2692,11 +2775,19 @@ __global__ __launch_bounds__(256, 3) void knn_fused_wave_kernel(
 #pragma unroll
       for (int s = 0; s < E; ++s)
         if (bi == lane + 64 * s) pp[s] = -1;  // consumed
-      bool keep = true;
+      bool keep = true, copy = false;
       if (dedup == 2 && nb > 0 && bd == last_d) keep = false;  // knnPQ: one per distance
-      else if (dedup && bd == last_d)  // same id => same distance: duplicates are among equal dist
+      else if ((dedup || kdist > 0) && bd == last_d)  // same id => same distance: duplicates are among equal dist
         for (int j = nb - 1; j >= 0 && bdist[j] == bd; --j)
-          if (bid[j] == cid[bi]) keep = false;
+          if (bid[j] == cid[bi]) copy = true;
+      if (dedup && copy) keep = false;
+      if (keep && kdist > 0 && !copy) {
+        if (nd == kdist) {  // one different id more than the kept set holds (wave-uniform)
+          l2cut = true;
+          break;
+        }
+        ++nd;
+      }
       if (keep) {
         if (lane == 0) {
           bdist[nb] = bd;
@@ -2708,6 +2799,7 @@ __global__ __launch_bounds__(256, 3) void knn_fused_wave_kernel(
         last_d = bd;
       }
     }
+    if (kdist > 0 && nb == ksel) l2cut = true;
     return nb;
   };
 
@@ -2763,10 +2855,14 @@ __global__ __launch_bounds__(256, 3) void knn_fused_wave_kernel(
       batch_distances<TD, TA, (sizeof(TD) < 8 ? 16 : 8)>(X, d, cid, cdist, qs, first_new, fill, 0, 1, lane);
     wave_sync();
     KSTAMP();  // distances
-    const int ksel = std::is_same<TD, double>::value ? k + kLfMargin : k;  // see kLfMargin
+    // f64 rows: the entries of k + kLfMargin different ids, as many as the list holds when duplicates
+    // are kept; "each id once" while streaming (see knn_fused_kernel and kLfMargin)
+    constexpr bool L2F64 = !PRE32 && std::is_same<TD, double>::value;
+    const int kdist = L2F64 ? k + kLfMargin : 0;
+    const int ksel = L2F64 ? (dedup == 0 ? kFKx : k + kLfMargin) : k;
     const int nb = PRE32 ? wselect_packed(fill, first_new, pb0, k1)
                  : pack32 ? wselect_packed(fill, first_new, pb0, k)
-                          : wselect(fill, first_new, pb0, ksel, dedup);
+                          : wselect(fill, first_new, pb0, ksel, L2F64 && dedup ? 1 : dedup, kdist);
     best = nb;
     KSTAMP();  // selection
     if (pos_base >= nc_tot) break;
@@ -2830,9 +2926,17 @@ __global__ __launch_bounds__(256, 3) void knn_fused_wave_kernel(
   }
   if constexpr (!PRE32 && std::is_same<TD, double>::value) {  // see knn_fused_kernel
     wave_sync();
+    const double blast = best > 0 ? bdist[best - 1] : 0.0;  // the butterfly value of the last kept entry
+    int fw = 0;         // (lane 0's: it writes the answer)
+    double flast = 0.0;
     finalize_leftfold(reinterpret_cast<const double*>(X), d, reinterpret_cast<const double*>(qs), best, k,
                       dedup, cdist, cid, bid, bpos, lane, 64, [] { wave_sync(); }, q, out_ids, out_dist,
-                      out_cnt);
+                      out_cnt, nullptr, 0.0, &fw, &flast);
+    // flag 2: the host answers this query again with the exact kernel (l2_cut_certified)
+    if (lane == 0 && !l2_cut_certified(l2cut, fw, k, flast, blast, d)) {
+      ovf_flags[q] = 2u;
+      atomicAdd(cand_total + 1, 1ULL);
+    }
     return;
   }
   for (int i = lane; i < k; i += 64) {
@@ -3636,7 +3740,8 @@ template <class TD>
 static int32_t launch_topk_dense(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
                                  const int32_t* perm, const Range* ranges, const int64_t* rng_off,
                                  int T, int identity, int k, int dedup, int32_t* ids,
-                                 double* dist, int32_t* cnt) {
+                                 double* dist, int32_t* cnt, int32_t* unc = nullptr,
+                                 unsigned long long* unc_count = nullptr /* f64: see launch_l2_f64 */) {
   typedef typename AccOf<TD>::type TA;
   const size_t smem = topk_smem(data->d, sizeof(TA));
   if (smem > 64 * 1024)
@@ -3645,7 +3750,7 @@ static int32_t launch_topk_dense(rpt_ctx* ctx, const rpt_dataset* data, const rp
   ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
   hipLaunchKernelGGL(topk_dense_kernel<TD>, dim3((unsigned)q->n), dim3(256), smem, ctx->stream,
                      (const TD*)data->X, data->d, (const TD*)q->X, perm, ranges, rng_off, T,
-                     data->n, identity, k, dedup, ids, dist, cnt);
+                     data->n, identity, k, dedup, ids, dist, cnt, unc, unc_count);
   RPT_HIP(hipGetLastError());
   return RPT_OK;
 }
@@ -3954,9 +4059,10 @@ static int32_t launch_metric_v(rpt_ctx* ctx, const rpt_dataset* data, const rpt_
   ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
   hipLaunchKernelGGL((knn_metric_kernel<TD, METRIC, EXACT>), dim3((unsigned)grid), dim3(256), smem,
                      ctx->stream, (const TD*)data->X, data->d, (const TD*)q->X, q->n, perm, ranges, rng_off, T,
-                     data->n, identity, nbuf, k, dedup, (const double*)data->sqnorm,
-                     reinterpret_cast<const unsigned long long*>(data->sqnorm + data->n), unc, unc_count, ids,
-                     dist, cnt);
+                     data->n, identity, nbuf, k, dedup, METRIC == kMetricL2 ? nullptr : (const double*)data->sqnorm,
+                     METRIC == kMetricL2 ? nullptr
+                                         : reinterpret_cast<const unsigned long long*>(data->sqnorm + data->n),
+                     unc, unc_count, ids, dist, cnt);
   RPT_HIP(hipGetLastError());
   return RPT_OK;
 }
@@ -3982,6 +4088,37 @@ static int32_t launch_metric_t(rpt_ctx* ctx, const rpt_dataset* data, const rpt_
   }
   return launch_metric_v<TD, METRIC, true>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, unc, uc,
                                            ids, dist, cnt);
+}
+
+// Dense f64 rows under L2 over a query plan or, with identity, the whole dataset (the brute force):
+// topk_dense_kernel ranks on butterfly sums and lists the queries whose cut it cannot certify, the
+// exact kernel answers those again (all of them, alone, with knn_l2_exact).  The count is read
+// lazily (rpt_knn_last_uncertified).  unc: [q->n] ints of device scratch that lives until the kernels are done.
+static int32_t launch_l2_f64(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, const int32_t* perm,
+                             const Range* ranges, const int64_t* rng_off, int T, int identity, int k, int dedup,
+                             int32_t* unc, int32_t* ids, double* dist, int32_t* cnt) {
+  unsigned long long* uc = nullptr;
+  RPT_TRY(metric_unc_count(ctx, &uc));
+  if (ctx->opt.knn_l2_exact) {
+    unc = nullptr;  // every query
+    ctx->last_uncertified = q->n;
+    ctx->metric_unc_pending = false;
+  } else {
+    RPT_HIP(hipMemsetAsync(uc, 0, 8, ctx->stream));
+    RPT_TRY(launch_topk_dense<double>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, ids, dist, cnt,
+                                      unc, uc));
+    ctx->metric_unc_pending = true;
+  }
+  return launch_metric_v<double, kMetricL2, true>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, unc,
+                                                  uc, ids, dist, cnt);
+}
+
+// the queries a fused launch flagged 2 (a cut that could not be certified), as the exact kernel's list
+__global__ __launch_bounds__(256) void collect_flagged_kernel(const unsigned int* __restrict__ flags, int64_t nq,
+                                                              int32_t* __restrict__ unc,
+                                                              unsigned long long* __restrict__ unc_count) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q < nq && flags[q] == 2u) unc[atomicAdd(unc_count, 1ULL)] = (int32_t)q;
 }
 
 template <class TD>
@@ -4451,6 +4588,7 @@ static int32_t knn_general(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
   if (q->n == 0) return RPT_OK;
   const int dedup = flags & 3;
   const int refm = (flags & RPT_KNN_METRIC_REFERENCE) ? 1 : 0;
+  DevBuf<int32_t> unc;  // dense f64 rows: the queries the exact kernel answers again (launch_l2_f64)
   if (data->csr) {
     const size_t smem = topk_smem(data->d, 8);
     ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
@@ -4473,8 +4611,9 @@ static int32_t knn_general(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
     }
     RPT_HIP(hipGetLastError());
   } else if (data->dtype == RPT_F64) {
-    RPT_TRY(launch_topk_dense<double>(ctx, data, q, f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, 0,
-                                      k, dedup, ids_dev, dist_dev, count_dev));
+    RPT_TRY(unc.alloc((size_t)q->n));
+    RPT_TRY(launch_l2_f64(ctx, data, q, f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, 0, k, dedup, unc.p, ids_dev,
+                          dist_dev, count_dev));
   } else if (data->dtype == RPT_F32) {
     RPT_TRY(launch_topk_dense<float>(ctx, data, q, f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, 0,
                                      k, dedup, ids_dev, dist_dev, count_dev));
@@ -4504,7 +4643,10 @@ int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_
   // (the fused kernels walk the implicit batch topology: streamed forests take the general path;
   // so do SVector rows under the reference's own truncating metric)
   const bool refm = data->csr && (flags & RPT_KNN_METRIC_REFERENCE);
-  const bool fused = k <= kFK && f->T <= 1024 && (!ctx->opt.knn_general || vote > 0) &&
+  ctx->last_uncertified = 0;
+  // (knn_l2_exact: every query of dense f64 rows on the exact kernel, which the general path launches)
+  const bool l2_exact = ctx->opt.knn_l2_exact && data->dtype == RPT_F64 && !data->csr && vote == 0;
+  const bool fused = k <= kFK && f->T <= 1024 && ((!ctx->opt.knn_general && !l2_exact) || vote > 0) &&
                      (size_t)data->d * 8 <= 32 * 1024 && !f->xtopo && !refm;
   if (vote > 0 && (!fused || data->csr))
     return fail(RPT_E_UNSUPPORTED, "RPT_KNN_VOTE: dense data, k <= 64 and at most 1024 trees");
@@ -4594,7 +4736,7 @@ int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_
   if (tot[1] * 4 > (unsigned long long)nq) {
     if (tier == 3) f->pre8_off = true;
     else if (tier == 2) f->pre16_off = true;
-    else f->prefilter_off = true;
+    else if (tier == 1) f->prefilter_off = true;  // (tier 0: the count is the f64 kernels' own)
   }
   ctx->last_tier = tier;
   // a batch in which more than an eighth of the queries needed the wider second attempt: the next
@@ -4602,7 +4744,23 @@ int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_
   ctx->last_retries = (int64_t)hctl[4];
   if (tier == 3 && (unsigned long long)hctl[4] * 8 > (unsigned long long)nq && f->kp8_boost < 4.0)
     f->kp8_boost *= 1.5;
-  if (tot[1]) {  // queries with equal distances at the prefilter's cut: the all-f64 kernel, them only
+  if (tot[1] && data->dtype == RPT_F64 && !data->csr) {
+    // dense f64 rows whose cut no kernel could certify (different rows that tie at the cut, to the
+    // last bits or exactly): the exact kernel over the query plan, them only — the definition
+    QueryPlan pl;
+    RPT_TRY(make_plan(ctx, f, q, pl));
+    DevBuf<int32_t> unc;
+    RPT_TRY(unc.alloc((size_t)nq));
+    unsigned long long* uc = nullptr;
+    RPT_TRY(metric_unc_count(ctx, &uc));
+    RPT_HIP(hipMemsetAsync(uc, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(collect_flagged_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
+                       ovf_p + 1, nq, unc.p, uc);
+    RPT_HIP(hipGetLastError());
+    RPT_TRY((launch_metric_v<double, kMetricL2, true>(ctx, data, q, f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, 0,
+                                                      k, dedup & 3, unc.p, uc, ids_dev, dist_dev, count_dev)));
+    RPT_HIP(stream_sync(ctx->stream));  // the plan, unc and ovf are released on return
+  } else if (tot[1]) {  // f32 / CSR rows with equal distances at the prefilter's cut: the exact kernel, them only
     RPT_TRY(launch(true));
     RPT_HIP(stream_sync(ctx->stream));  // Pq / ovf are released on return
   }
@@ -5192,9 +5350,13 @@ int32_t brute_knn_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* 
     return launch_metric(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, metric, unc.p, ids_dev,
                          dist_dev, cnt.p);
   }
-  if (data->dtype == RPT_F64)
-    return launch_topk_dense<double>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, ids_dev,
-                                     dist_dev, cnt.p);
+  if (data->dtype == RPT_F64) {
+    ctx->last_uncertified = 0;
+    ctx->metric_unc_pending = false;
+    DevBuf<int32_t> unc;
+    RPT_TRY(unc.alloc((size_t)nq));
+    return launch_l2_f64(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, unc.p, ids_dev, dist_dev, cnt.p);
+  }
   if (data->dtype == RPT_F32)
     return launch_topk_dense<float>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, ids_dev,
                                     dist_dev, cnt.p);

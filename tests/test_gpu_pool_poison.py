@@ -36,6 +36,7 @@ _A = "tests/test_gpu_abi.py::"
 _C = "tests/test_gpu_configs.py::"
 _M = "tests/test_gpu_knn_metrics.py::"
 _MC = "tests/test_gpu_knn_metric_cut.py::"
+_LC = "tests/test_gpu_knn_l2_cut.py::"
 _B = "tests/test_gpu_brute_csr.py::"
 _G = "tests/test_gpu_knn_graph.py::"
 _GM = "tests/test_gpu_knn_graph_metric.py::"
@@ -135,6 +136,9 @@ FAMILIES = {
         _P + "test_knnh_sparse_matches_oracle",
         _P + "test_knnpq_collapses_equal_distances",
         _A + "test_knn_vote_matches_keep_counts[f64]",
+        _LC + "test_cut_inside_a_band_of_permutations[d37-no_pre32]",   # the exact L2 kernel and its list
+        _LC + "test_cut_inside_the_copies_of_a_pair[12-general]",
+        _LC + "test_tie_at_the_prefilter_cut_ends_on_the_definition",
     ]),
     "knn_tiers": (4.2, 120, [
         _P + "test_knn_int8_tier_is_exact[ties-shape2]",
