@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/rptree_hip.h"
+#include "knn_plan.h"
 
 namespace rpt {
 
@@ -93,6 +94,20 @@ struct DeviceOnce {
     return s;
   }
 };
+
+// Launch of a kernel with dynamic LDS: more than 64 KB has to be allowed per kernel first (on every
+// such call: the attribute belongs to the device's copy of the code object, see DeviceOnce).
+// Every kernel argument is given: a kernel's default arguments do not pass through its address.
+template <class... P, class... A>
+inline hipError_t launch_dyn(void (*kernel)(P...), dim3 grid, dim3 block, size_t smem, hipStream_t stream,
+                             A... args) {
+  if (smem > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, smem, stream, args...);
+  return hipGetLastError();
+}
 
 // simple owned device buffer
 template <class T>
@@ -184,6 +199,19 @@ struct rpt_options {
   int64_t debug_host = 0;       // stderr: host-side phase times of a build
   int64_t debug_stamps = 0;     // device time stamps of the wave kernel
 };
+
+// the options the fused kNN's plan reads (knn_plan.h), by value
+inline void fused_input_options(rpt::FusedIn& in, const rpt_options& o) {
+  in.knn_wave = o.knn_wave;
+  in.knn_kp = o.knn_kp;
+  in.knn_kp16 = o.knn_kp16;
+  in.knn_kp8 = o.knn_kp8;
+  in.knn_no_pre32 = o.knn_no_pre32 != 0;
+  in.knn_no_pre16 = o.knn_no_pre16 != 0;
+  in.knn_no_pre8 = o.knn_no_pre8 != 0;
+  in.knn_csr_pre32 = o.knn_csr_pre32 != 0;
+  in.knn_shard_old = o.knn_shard_old != 0;
+}
 
 struct rpt_ctx {
   rpt_options opt;
@@ -312,13 +340,7 @@ struct rpt_forest {
   int32_t pdtype = RPT_F64;  // type of proj
   int32_t dtype = RPT_F64;   // element type of the dataset the forest was built on / imported for
   int32_t mode = RPT_PROJ_AUTO;  // projection mode used by the build (queries reuse it)
-  // set when a query batch had more than a quarter of its f32-prefilter cuts uncertified (many
-  // equal distances: e.g. the queries are data points, found once per tree): later batches on this
-  // forest go straight to the all-f64 kernel
-  bool prefilter_off = false;
-  bool pre8_off = false;   // ... and one more: the int8 shadow failed too many cuts here
-  bool pre16_off = false;  // ... the same one tier up: the f16 shadow failed too many cuts here
-  double kp8_boost = 1.0;  // int8 tier: factor on the kept entries, raised when a batch retried often
+  rpt::TierState tiers;  // what the fused kNN has learnt from its batches on this forest (knn_plan.h)
   int64_t nodes = 0;         // 2^L - 1
   rpt::DevBuf<int32_t> perm;  // [T][N] final leaf-ordered permutation
   rpt::DevBuf<double> thr, mglo, mghi;  // [T][nodes]

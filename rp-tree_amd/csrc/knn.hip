@@ -552,17 +552,6 @@ __device__ inline double leftfold_distance(const double* __restrict__ x, const d
   return sqrt(acc);
 }
 
-// Dense f64 rows under L2: the batched distance passes RANK on butterfly sums, the answer is defined
-// on the reference's left fold (RPTree.hs:174 ranks ALL candidates on the fold).  A ranking path
-// keeps the entries of the best k + kLfMargin DIFFERENT ids by (butterfly distance, position) — copies
-// of one id, the same point found by several trees, have one value under either sum and must not
-// use the margin up — at most the capacity of its list; those are evaluated again as the fold and
-// the k best of THOSE by (fold distance, position) are written.  Then the cut is CERTIFIED per query
-// (l2_cut_certified); a query that is not certified is answered again by the exact kernel
-// (knn_metric_kernel<double, kMetricL2, true>: every candidate on the fold, no margin), so the
-// answer is the definition however many different rows tie at the k-th distance.
-constexpr int kLfMargin = 8;
-
 // The certified cut.  Both sums of a row add the SAME rounded, non-negative products p_j = t_j t_j,
 // t_j = fl(x_j - q_j) (-ffp-contract=off: no FMA), from +0 in different orders.  Whatever the order,
 // the d terms are merged by d - 1 additions that round (adding a zero is exact), so a term passes
@@ -1699,21 +1688,13 @@ __device__ __forceinline__ void batch_distances_ell16(const uint32_t* __restrict
 // their original candidate positions, so the order (distance, position) is global.
 // k <= kFK: k rounds of block-wide arg-min; larger k or a range list that does not fit the
 // LDS slab -> the query is flagged and the host falls back to the general path.
+// (kFC, kFR, kFK, kBK, kVoteCap: knn_plan.h)
 // ---------------------------------------------------------------------------------------
-constexpr int kFC = 2048;     // candidates per batch
-constexpr int kFR = 512;      // leaf ranges per query in LDS
-constexpr int kFK = 64;       // largest k served by the arg-min selection
-constexpr int kFKx = kFK + kLfMargin;  // capacity of the running best list (see kLfMargin)
-// the workgroup kernel's prefilter tiers may keep more than that: the threshold selection costs
-// the same whatever it keeps, and the int8 tier needs a wide margin at the cut (see Sh8)
-constexpr int kBK = 224;
-constexpr int kBKx = kBK + kLfMargin;
 #ifndef RPT_CONSEC_FILL
 #define RPT_CONSEC_FILL 0
 #endif
 constexpr bool kConsecFill = RPT_CONSEC_FILL != 0;  // consecutive-slot fill in the non-WIDE instantiations too
 constexpr int kSelList = 512;  // select_packed's candidate list (in the idle distance slab)
-constexpr int kVoteCap = 16384;  // candidates of one query the voting mode can count (64 KB of LDS)
 
 template <class TD, class TK, bool PRE32, bool CSR = false, bool I8 = false /* PRE32 on the int8 shadow */>
 // (three workgroups per CU is what the 52 KB slab allows: keep the registers at that occupancy)
@@ -2497,27 +2478,12 @@ retry_wider:
 // pass only if a tree outgrew its slots), batches of kWC candidates, the wave's own entries of
 // the batch in registers during the k arg-min rounds.  Same total order (distance, candidate
 // position) and the same distance reduction as the workgroup variant: identical results.
+// (kWC, kWR, kWT and the LDS bytes of a wave, fused_wave_bytes: knn_plan.h)
 // ---------------------------------------------------------------------------------------
-constexpr int kWC = 512;  // candidates per batch of one wave
-constexpr int kWR = 128;  // leaf ranges per query
-constexpr int kWT = 64;   // trees (lane = tree)
-// the variant is chosen when trees x minLeaf (~ candidates per query) is at most this
-// (round 3: trees x the leaf size the topology gives, at most 700 — it was trees x minLeaf <= 1024.
-// With the threshold selection, the single traversal and the in-kernel retry the workgroup kernel
-// answers an 8-tree shard of C2 (8 x 122 candidates) in 0.67 ms, this one in 0.96; the 8 x 76 of a
-// C4 shard stay here: 3.2 against 5.9 ms per 100 000 queries)
-constexpr int64_t kWaveCandidates = 700;
-constexpr int64_t kShardCandidates = 2100;  // ... and the round-4 shard kernels (see launch_fused)
-
 __device__ inline void wave_sync() {  // LDS writes of the wave visible to all its lanes
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__host__ __device__ inline size_t fused_wave_bytes(int d, size_t acc_size) {
-  const size_t b = (size_t)kWC * 12 + (size_t)kWR * 24 + (size_t)kFKx * 16 + (size_t)d * (acc_size + 4);
-  return (b + 15) & ~(size_t)15;
 }
 
 template <class TD, class TK, bool PRE32, bool I8 = false /* PRE32 on the int8 shadow */>
@@ -2975,7 +2941,7 @@ __global__ __launch_bounds__(256, 3) void knn_fused_wave_kernel(
 //     certified by construction: no fixed k' (the one-wave kernel kept k + 37 rows for every query to
 //     certify the worst of ten thousand: 48 KB of f64 rows per query against 63 KB of int8 rows; the
 //     band at the cut holds ~ 9), no uncertified re-runs except a list that outgrows its 128 slots.
-constexpr int kSKmax = 48;  // largest k the shard kernel serves (the carried list must hold k and its band)
+// (kSKmax, the largest k the shard kernel serves, and shard_wave_bytes: knn_plan.h)
 
 template <class TK>
 __global__ __launch_bounds__(256) void shard_ranges_kernel(
@@ -3053,12 +3019,6 @@ __global__ __launch_bounds__(256) void shard_ranges_kernel(
   }
   for (int o = 32; o > 0; o >>= 1) visited += __shfl_xor(visited, o);
   if (lane == 0 && visited) atomicAdd(cand_total, visited);
-}
-
-__host__ __device__ inline size_t shard_wave_bytes(int d, size_t acc_size, int kSL, int WC) {
-  const size_t b = (size_t)WC * 8 + (size_t)kWR * 8 + (size_t)(kWR + 4) * 4 + (size_t)kSL * 20 + 16 +
-                   (((size_t)d * acc_size + 15) & ~(size_t)15) + (size_t)d * 4;
-  return (b + 15) & ~(size_t)15;
 }
 
 // TIER: 1 = f32 shadow, 2 = IEEE-half shadow, 3 = int8 shadow (Sh8)
@@ -3744,19 +3704,14 @@ static int32_t launch_topk_dense(rpt_ctx* ctx, const rpt_dataset* data, const rp
                                  unsigned long long* unc_count = nullptr /* f64: see launch_l2_f64 */) {
   typedef typename AccOf<TD>::type TA;
   const size_t smem = topk_smem(data->d, sizeof(TA));
-  if (smem > 64 * 1024)
-    RPT_HIP(hipFuncSetAttribute((const void*)topk_dense_kernel<TD>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
-  hipLaunchKernelGGL(topk_dense_kernel<TD>, dim3((unsigned)q->n), dim3(256), smem, ctx->stream,
+  RPT_HIP(launch_dyn(topk_dense_kernel<TD>, dim3((unsigned)q->n), dim3(256), smem, ctx->stream,
                      (const TD*)data->X, data->d, (const TD*)q->X, perm, ranges, rng_off, T,
-                     data->n, identity, k, dedup, ids, dist, cnt, unc, unc_count);
-  RPT_HIP(hipGetLastError());
+                     data->n, identity, k, dedup, ids, dist, cnt, unc, unc_count));
   return RPT_OK;
 }
 
 constexpr int kMergeMax = 4096;  // entries of one merge launch (LDS)
-static inline int prefilter_keep(int k) { return k + (k / 2 > 6 ? k / 2 : 6); }
 
 // f32 shadow of a dense f64 dataset + its largest row norm (one wave per row)
 __global__ __launch_bounds__(256) void shadow32_kernel(const double* __restrict__ X, int64_t n, int d,
@@ -4050,20 +4005,16 @@ static int32_t launch_metric_v(rpt_ctx* ctx, const rpt_dataset* data, const rpt_
   const int nbuf = k + kLfMargin + kMB <= 1024 ? 1024 : kBuf;
   const size_t smem = metric_smem(nbuf, data->d);
   RPT_ARG(smem <= 150 * 1024, "d too large");
-  if (smem > 64 * 1024)
-    RPT_HIP(hipFuncSetAttribute((const void*)knn_metric_kernel<TD, METRIC, EXACT>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   // the exact variant strides over its list of queries (blocks beyond its length return at once)
   int64_t grid = q->n;
   if (EXACT && grid > (int64_t)ctx->n_cu * 4) grid = (int64_t)ctx->n_cu * 4;
   ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
-  hipLaunchKernelGGL((knn_metric_kernel<TD, METRIC, EXACT>), dim3((unsigned)grid), dim3(256), smem,
+  RPT_HIP(launch_dyn(knn_metric_kernel<TD, METRIC, EXACT>, dim3((unsigned)grid), dim3(256), smem,
                      ctx->stream, (const TD*)data->X, data->d, (const TD*)q->X, q->n, perm, ranges, rng_off, T,
                      data->n, identity, nbuf, k, dedup, METRIC == kMetricL2 ? nullptr : (const double*)data->sqnorm,
                      METRIC == kMetricL2 ? nullptr
                                          : reinterpret_cast<const unsigned long long*>(data->sqnorm + data->n),
-                     unc, unc_count, ids, dist, cnt);
-  RPT_HIP(hipGetLastError());
+                     unc, unc_count, ids, dist, cnt));
   return RPT_OK;
 }
 
@@ -4340,28 +4291,43 @@ static int32_t ensure_shadow_ell(rpt_ctx* ctx, const rpt_dataset* data) {
   return RPT_OK;
 }
 
+// what fused_shadows_wanted and fused_plan read of a call (knn_plan.h)
+static void fused_input_shadows(FusedIn& in, const rpt_dataset* data) {
+  in.shadow8 = data->shadow8 != nullptr;
+  in.shadow16 = data->shadow16 != nullptr;
+  in.shadow32 = data->shadow32 != nullptr;
+  in.shadow_col16 = data->shadow_col16 != nullptr;
+  in.shadow_ell = data->shadow_ell != nullptr;
+}
+
+static FusedIn fused_input(const rpt_ctx* ctx, const rpt_forest* f, const rpt_dataset* data, int k, int dedup,
+                           int vote) {
+  const auto elem = [](int32_t dt) { return dt == RPT_F64 ? Elem::F64 : dt == RPT_F32 ? Elem::F32 : Elem::BF16; };
+  FusedIn in;
+  in.elem = elem(data->dtype);
+  in.proj = elem(f->pdtype);
+  in.csr = data->csr;
+  in.d = data->d;
+  in.k = k;
+  in.dedup = dedup;
+  in.vote = vote;
+  in.T = f->T;
+  in.L = f->L;
+  in.min_leaf = f->min_leaf;
+  in.n = f->n;
+  in.tiers = f->tiers;
+  fused_input_options(in, ctx->opt);
+  fused_input_shadows(in, data);
+  return in;
+}
+
+// launches what the plan says: one kernel (the shard family: its traversal kernel first)
 template <class TD, class TK>
-static int32_t launch_fused(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
-                            const rpt_dataset* q, const void* Pq, int32_t k, int dedup,
-                            int32_t* ids, double* dist, int32_t* cnt, unsigned int* ovf,
-                            unsigned long long* cand_total, bool rerun = false,
-                            int* tier = nullptr /* out: 0 exact, 1 f32 shadow, 2 half shadow */) {
-  typedef typename AccOf<TD>::type TA;
-  // small shards (few trees => a few hundred candidates per query): one wave per query
-  const int64_t force = ctx->opt.knn_wave;  // -1 auto
-  const size_t wbytes = fused_wave_bytes(data->d, sizeof(TA));
-  const int vote = dedup >> 8;  // voting mode: the workgroup kernel, all-exact distances
-  int64_t leaf = f->n;  // the size splitting stops at: the first level's node size <= minLeaf, or depth L
-  for (int l = 0; l < f->L && leaf > (int64_t)f->min_leaf; ++l) leaf -= leaf / 2;
-  const int64_t est_cand = (int64_t)f->T * (leaf > 0 ? leaf : 1);
-  bool wave = f->T >= 1 && f->T <= kWT && wbytes <= 16 * 1024 && est_cand <= kWaveCandidates;
-  // the round-4 shard kernels (traversal as its own launch, adaptive certified set) stay ahead of the
-  // workgroup kernel for longer: an 8-tree C2 shard (980 candidates) 0.42 against 0.65 ms per 10 000
-  // queries, 16 trees (1950) 0.73 against 0.86 (5.7 against 7.9 ms per 100 000); at 32 trees the
-  // workgroup kernel is level or ahead
-  bool wave_shard = f->T >= 1 && f->T <= kWT && wbytes <= 16 * 1024 && est_cand <= kShardCandidates;
-  if (force >= 0) wave = wave_shard = force == 1 && f->T >= 1 && f->T <= kWT && wbytes <= 40 * 1024;
-  if (vote > 0 || data->csr) wave = wave_shard = false;
+static int32_t launch_fused(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                            const void* Pq, const FusedIn& in, const FusedPlan& p, int32_t* ids, double* dist,
+                            int32_t* cnt, unsigned int* ovf, unsigned long long* cand_total) {
+  constexpr bool kF64 = std::is_same<TD, double>::value, kBf16 = std::is_same<TD, __hip_bfloat16>::value;
+  const int k = in.k, dedup = in.dedup | in.vote << 8;  // (the kernels take the vote threshold with the duplicate rule)
   // debug_stamps: phase clocks of one wave of the wave kernel, printed after the launch
   DevBuf<unsigned long long> dbgdev;
   unsigned long long* dbg = nullptr;
@@ -4381,74 +4347,21 @@ static int32_t launch_fused(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data
     }
   } dbgprint{ctx, nullptr};
   ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
-  // f64 data, duplicates kept, small k: rank the candidates on the f32 shadow (half the row
-  // bytes), exact distances for the best k' only, cut certified per query (see the kernels)
-  const int kp_env = (int)ctx->opt.knn_kp;
-  // entries the f32 pass keeps: every one costs a selection round per batch (16 of them: 0.75 ms
-  // per 10 000 queries at C2), too few and cuts fail their certificate (re-run per query): k + 6
-  // certifies 10 000 of 10 000 C2 queries
-  int kp = kp_env > k && kp_env < kFK ? kp_env : prefilter_keep(k);
-  const bool pre32 = std::is_same<TD, double>::value && dedup == 0 && kp + 1 <= kFK &&
-                     !ctx->opt.knn_no_pre32 && data->shadow32 && !rerun && !f->prefilter_off &&
-                     (!data->csr || data->shadow_col16);
-  // first tier: rank on the HALF shadow (a quarter of the f64 bytes); its rounding is coarser, so it
-  // keeps a few more entries for the exact pass: k + max(8, k / 2) (C2: 10 000 of 10 000 queries
-  // certified with 18 kept, 2.55 ms per batch against 4.10 ms on the f32 shadow; 26 kept 2.70 ms)
-  const int kp16_env = (int)ctx->opt.knn_kp16;
-  const int kp16 = kp16_env > k && kp16_env < kFK ? kp16_env : k + (k / 2 > 8 ? k / 2 : 8);
-  // (f32 data: the half shadow is the only ranking tier; the kept rows are refined with the very
-  // f32 distance the all-f32 kernel ranks on, so the answers are identical)
-  const bool base16 = !data->csr && data->shadow16 && !ctx->opt.knn_no_pre16 && !f->pre16_off &&
-                      kp16 + 1 <= kFK && dedup == 0 && !rerun && !ctx->opt.knn_no_pre32;
-  const bool sh16 = base16 && (pre32 || std::is_same<TD, float>::value);
-  // SVector rows: the fixed-width half table is their first tier (the f32 CSR shadow is opt-in)
-  const bool ell = std::is_same<TD, double>::value && data->csr && data->shadow_ell &&
-                   !ctx->opt.knn_no_pre16 && !f->pre16_off && !f->prefilter_off && kp16 + 1 <= kFK &&
-                   dedup == 0 && !rerun && !ctx->opt.knn_no_pre32;
-  if (sh16 || ell) kp = kp16;
-  // ... or, before that, on the INT8 shadow (an eighth of the f64 bytes; integer ranking values, the
-  // cut certified through the triangle inequality, see Sh8): coarser again, k + max(48, k) kept
-  const int kp8_env = (int)ctx->opt.knn_kp8;
-  // (the one-wave kernel takes its threshold from the 64 per-lane minima: beyond the 48th of them
-  // the candidate list outgrows its 128 slots)
-  const int kcap8 = wave ? 48 : kBK;
-  // (the width of the band at the cut grows with the square root of the row length: sqrt(d / 128)
-  // times the margin that certifies C2's 128-element rows)
-  // ... and with the number of candidates (the band holds a share of them: 48 certify C2's 3922 and a
-  // C4 forest's 3686 per query, not the 4915 of C4's 64 trees, where most queries took the in-kernel
-  // retry — a second pass over all candidates: 3.5 ms per 10 000 queries against 2.0 with 100 kept),
-  // and with what the forest's earlier batches reported (kp8_boost: retries counted by the kernel)
-  const double cand_scale = est_cand > 4000 ? (double)est_cand / 4000.0 : 1.0;
-  const int margin8 = (int)((k > 48 ? k : 48) * (data->d > 128 ? std::sqrt((double)data->d / 128.0) : 1.0) *
-                            cand_scale * f->kp8_boost);
-  int kp8 = kp8_env > k && kp8_env < kcap8 ? kp8_env : k + margin8;
-  if (kp8 > kcap8 - 1) kp8 = kcap8 - 1;
-  const bool sh8 = !data->csr && data->shadow8 && !ctx->opt.knn_no_pre8 && !f->pre8_off &&
-                   kp8 >= k + 8 && dedup == 0 && !rerun && !ctx->opt.knn_no_pre32 &&
-                   !ctx->opt.knn_no_pre16 && !f->pre16_off && !f->prefilter_off &&
-                   (std::is_same<TD, double>::value || std::is_same<TD, float>::value ||
-                    (std::is_same<TD, __hip_bfloat16>::value && !wave));  // (bf16: the workgroup kernel only)
-  if (sh8) kp = kp8;
-  const Sh8 s8 = sh8 ? Sh8{data->s8_scale, data->s8_emax} : Sh8{0.0, 0.0};
-  if (tier) *tier = sh8 ? 3 : (sh16 || ell) ? 2 : pre32 ? 1 : 0;
-  const void* shadow = sh8    ? (const void*)data->shadow8
-                       : sh16 ? (const void*)data->shadow16
-                              : (const void*)data->shadow32;
-  if constexpr (!std::is_same<TD, __hip_bfloat16>::value) {
-    if (wave_shard && !wave && !((pre32 || sh16 || sh8) && k <= kSKmax && !ctx->opt.knn_shard_old))
-      wave_shard = false;  // (only the prefiltered instantiations have the shard kernels)
-    // (a forced wave variant on very long rows: the shard kernels' slab must fit the CU's LDS)
-    if (wave_shard && 4 * shard_wave_bytes(data->d, sizeof(TA), 256, 640) > 160 * 1024) wave_shard = false;
-  } else {
-    wave_shard = false;
-  }
-  if (wave || wave_shard) {
-    dbgprint.p = dbg;
-    const size_t smem = 4 * wbytes;
-    if constexpr (!std::is_same<TD, __hip_bfloat16>::value) {
+  // what a dense tier ranks on (CSR rows: see CsrPtrs) and what its certificate reads
+  const void* shadow = data->csr || p.tier == 0 ? nullptr
+                       : p.tier == 3            ? (const void*)data->shadow8
+                       : p.tier == 2            ? (const void*)data->shadow16
+                                                : (const void*)data->shadow32;
+  const double xmax = p.tier > 0 ? data->max_norm : 0.0;
+  const Sh8 s8 = p.tier == 3 ? Sh8{data->s8_scale, data->s8_emax} : Sh8{0.0, 0.0};
+  const dim3 block(256);
+  // (the if constexpr guards: which instantiations exist — bf16 rows have no wave or shard tiers and
+  // no CSR form, f32 rows no CSR shadow; the plan never asks for one of those)
+  switch (p.family) {
+    case Family::Shard:
       // round 4: traversal as its own launch, exact distances for an adaptive certified set
-      // (shard_ranges_kernel / knn_shard_wave_kernel); knn_shard_old = 1 keeps the round-3 kernel
-      if (wave_shard && (pre32 || sh16 || sh8) && k <= kSKmax && !ctx->opt.knn_shard_old) {
+      // (shard_ranges_kernel / knn_shard_wave_kernel)
+      if constexpr (!kBf16) {
         const int64_t nq = q->n;
         DevBuf<int2> hdr;
         DevBuf<int64_t> roff;
@@ -4457,126 +4370,66 @@ static int32_t launch_fused(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data
         RPT_TRY(roff.alloc((size_t)nq * kWR));
         RPT_TRY(rlen.alloc((size_t)nq * kWR));
         const int qpw = 64 / f->T;
-        hipLaunchKernelGGL(shard_ranges_kernel<TK>, dim3((unsigned)((nq + 4 * qpw - 1) / (4 * qpw))), dim3(256), 0,
+        hipLaunchKernelGGL(shard_ranges_kernel<TK>, dim3((unsigned)((nq + 4 * qpw - 1) / (4 * qpw))), block, 0,
                            ctx->stream, f->thr.p, f->mglo.p, f->mghi.p, f->nodes, (const TK*)Pq, nq, f->T, f->L,
                            f->min_leaf, f->n, hdr.p, roff.p, rlen.p, ovf + 1, ovf, cand_total);
         RPT_HIP(hipGetLastError());
-        const bool one_batch = (int64_t)f->T * (leaf > 0 ? leaf : 1) <= kWC;
-        const size_t smem2 = 4 * (one_batch ? shard_wave_bytes(data->d, sizeof(TA), 128, 512)
-                                            : shard_wave_bytes(data->d, sizeof(TA), 256, 640));
-        auto kern = sh8    ? (one_batch ? knn_shard_wave_kernel<TD, 3, 128, 4, 512> : knn_shard_wave_kernel<TD, 3, 256, 3, 640>)
-                    : sh16 ? (one_batch ? knn_shard_wave_kernel<TD, 2, 128, 4, 512> : knn_shard_wave_kernel<TD, 2, 256, 3, 640>)
-                           : (one_batch ? knn_shard_wave_kernel<TD, 1, 128, 4, 512> : knn_shard_wave_kernel<TD, 1, 256, 3, 640>);
-        if (smem2 > 64 * 1024)
-          RPT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2));
+        auto kern = p.tier == 3   ? (p.one_batch ? knn_shard_wave_kernel<TD, 3, 128, 4, 512> : knn_shard_wave_kernel<TD, 3, 256, 3, 640>)
+                    : p.tier == 2 ? (p.one_batch ? knn_shard_wave_kernel<TD, 2, 128, 4, 512> : knn_shard_wave_kernel<TD, 2, 256, 3, 640>)
+                                  : (p.one_batch ? knn_shard_wave_kernel<TD, 1, 128, 4, 512> : knn_shard_wave_kernel<TD, 1, 256, 3, 640>);
         const int r1_pct = 110;  // (100 / 110 / 130 measured: 0.281 / 0.279 / 0.283 ms per 10 000 queries)
-        hipLaunchKernelGGL(kern, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem2, ctx->stream, (const TD*)data->X,
+        dbgprint.p = dbg;
+        RPT_HIP(launch_dyn(kern, dim3((unsigned)((nq + 3) / 4)), block, p.smem, ctx->stream, (const TD*)data->X,
                            data->d, (const TD*)q->X, f->perm.p, nq, k, hdr.p, roff.p, rlen.p, ids, dist, cnt,
-                           ovf + 1, cand_total, shadow, data->max_norm, s8, r1_pct, dbg);
-        RPT_HIP(hipGetLastError());
+                           ovf + 1, cand_total, shadow, xmax, s8, r1_pct, dbg));
         return RPT_OK;
       }
-      if (pre32 || sh16 || sh8) {
-        auto kern = sh8 ? knn_fused_wave_kernel<TD, TK, true, true> : knn_fused_wave_kernel<TD, TK, true, false>;
-        if (smem > 64 * 1024)
-          RPT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)smem));
-        hipLaunchKernelGGL(kern, dim3((unsigned)((q->n + 3) / 4)),
-                           dim3(256), smem, ctx->stream, (const TD*)data->X, data->d,
-                           (const TD*)q->X, f->perm.p, f->thr.p, f->mglo.p, f->mghi.p, f->nodes,
-                           (const TK*)Pq, q->n, f->T, f->L, f->min_leaf, f->n, k, dedup, ids, dist,
-                           cnt, ovf + 1, ovf, cand_total, shadow, data->max_norm, kp + 1, dbg,
-                           sh16 ? 1 : 0, s8);
-        RPT_HIP(hipGetLastError());
-        return RPT_OK;
+      break;
+    case Family::Wave: {
+      decltype(&knn_fused_wave_kernel<TD, TK, false>) kern = nullptr;
+      if constexpr (!kBf16) {
+        if (p.tier > 0) kern = p.tier == 3 ? knn_fused_wave_kernel<TD, TK, true, true> : knn_fused_wave_kernel<TD, TK, true, false>;
       }
-    }
-    if (smem > 64 * 1024)
-      RPT_HIP(hipFuncSetAttribute((const void*)knn_fused_wave_kernel<TD, TK, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL((knn_fused_wave_kernel<TD, TK, false>), dim3((unsigned)((q->n + 3) / 4)),
-                       dim3(256), smem, ctx->stream, (const TD*)data->X, data->d,
-                       (const TD*)q->X, f->perm.p, f->thr.p, f->mglo.p, f->mghi.p, f->nodes,
-                       (const TK*)Pq, q->n, f->T, f->L, f->min_leaf, f->n, k, dedup, ids, dist,
-                       cnt, ovf + 1, ovf, cand_total, (const void*)nullptr, 0.0, rerun ? -1 : 0, dbg);
-    RPT_HIP(hipGetLastError());
-    return RPT_OK;
-  }
-  const size_t smem = (size_t)kFC * 16 + (size_t)kFR * 12 + 2048 * 4 + (size_t)kBKx * 16 +
-                      (size_t)data->d * (sizeof(TA) + 4) + 64 +
-                      (vote > 0 ? (size_t)kVoteCap * 4 + 16 : 0);
-  if constexpr (!std::is_same<TD, double>::value) {
-    if (sh16 || sh8) {  // f32 rows ranked on their half / int8 shadow, bf16 rows on their int8 shadow
-      auto kern = sh8 ? knn_fused_kernel<TD, TK, true, false, true> : knn_fused_kernel<TD, TK, true, false, false>;
-      if (smem > 64 * 1024)
-        RPT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)smem));
-      hipLaunchKernelGGL(kern, dim3((unsigned)q->n), dim3(256), smem,
-                         ctx->stream, (const TD*)data->X, data->d, (const TD*)q->X, f->perm.p,
-                         f->thr.p, f->mglo.p, f->mghi.p, f->nodes, (const TK*)Pq, q->n, f->T, f->L,
-                         f->min_leaf, f->n, k, dedup, ids, dist, cnt, ovf + 1, ovf, cand_total,
-                         shadow, data->max_norm, kp + 1, CsrPtrs{}, 1, s8, (unsigned long long*)nullptr);
-      RPT_HIP(hipGetLastError());
-      return RPT_OK;
-    }
-  }
-  if constexpr (std::is_same<TD, double>::value) {
-    if ((pre32 || ell) && data->csr) {  // SVector rows ranked on their half table / (u16, f32) shadow
-      const CsrPtrs cp{data->rowptr, data->col, data->val, data->nnz, q->rowptr, q->col, q->val,
-                       data->shadow_col16, data->shadow32, ell ? (int64_t)data->ell_w : data->max_rowlen,
-                       data->shadow_ell, data->ell_w};
-      if (smem > 64 * 1024)
-        RPT_HIP(hipFuncSetAttribute((const void*)knn_fused_kernel<TD, TK, true, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      hipLaunchKernelGGL((knn_fused_kernel<TD, TK, true, true>), dim3((unsigned)q->n), dim3(256),
-                         smem, ctx->stream, (const TD*)nullptr, data->d, (const TD*)nullptr,
-                         f->perm.p, f->thr.p, f->mglo.p, f->mghi.p, f->nodes, (const TK*)Pq, q->n,
-                         f->T, f->L, f->min_leaf, f->n, k, dedup, ids, dist, cnt, ovf + 1, ovf,
-                         cand_total, (const void*)nullptr, data->max_norm, kp + 1, cp, ell ? 1 : 0);
-      RPT_HIP(hipGetLastError());
-      return RPT_OK;
-    }
-    if (pre32 || sh8) {
-      auto kern = sh8 ? knn_fused_kernel<TD, TK, true, false, true> : knn_fused_kernel<TD, TK, true, false, false>;
-      if (smem > 64 * 1024)
-        RPT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)smem));
-      hipLaunchKernelGGL(kern, dim3((unsigned)q->n), dim3(256), smem,
-                         ctx->stream, (const TD*)data->X, data->d, (const TD*)q->X, f->perm.p,
-                         f->thr.p, f->mglo.p, f->mghi.p, f->nodes, (const TK*)Pq, q->n, f->T, f->L,
-                         f->min_leaf, f->n, k, dedup, ids, dist, cnt, ovf + 1, ovf, cand_total,
-                         shadow, data->max_norm, kp + 1, CsrPtrs{}, sh16 ? 1 : 0, s8, dbg);
+      if (p.tier == 0) kern = knn_fused_wave_kernel<TD, TK, false>;
+      if (!kern) break;
       dbgprint.p = dbg;
-      RPT_HIP(hipGetLastError());
+      RPT_HIP(launch_dyn(kern, dim3((unsigned)((q->n + 3) / 4)), block, p.smem, ctx->stream, (const TD*)data->X,
+                         data->d, (const TD*)q->X, f->perm.p, f->thr.p, f->mglo.p, f->mghi.p, f->nodes,
+                         (const TK*)Pq, q->n, f->T, f->L, f->min_leaf, f->n, k, dedup, ids, dist, cnt, ovf + 1, ovf,
+                         cand_total, shadow, xmax, p.k1, dbg, p.sh16 ? 1 : 0, s8));
+      return RPT_OK;
+    }
+    case Family::Workgroup: {
+      // dense rows, every distance exact; or ranked on a shadow (f32 rows: their half / int8 one, bf16
+      // rows: their int8 one); SVector rows: the same kernel, distances over CSR rows, exact or ranked
+      // on their half table / (u16, f32) shadow
+      decltype(&knn_fused_kernel<TD, TK, false>) kern = nullptr;
+      if constexpr (kF64) {
+        if (data->csr && p.tier > 0) kern = knn_fused_kernel<TD, TK, true, true>;
+      }
+      if (!data->csr && p.tier > 0)
+        kern = p.tier == 3 ? knn_fused_kernel<TD, TK, true, false, true> : knn_fused_kernel<TD, TK, true, false, false>;
+      if constexpr (!kBf16) {
+        if (data->csr && p.tier == 0) kern = knn_fused_kernel<TD, TK, false, true>;
+      }
+      if (!data->csr && p.tier == 0) kern = knn_fused_kernel<TD, TK, false>;
+      if (!kern) break;
+      const CsrPtrs cp = data->csr ? CsrPtrs{data->rowptr, data->col, data->val, data->nnz, q->rowptr, q->col, q->val,
+                                             data->shadow_col16, data->shadow32,
+                                             p.csr_rank == CsrRank::Ell ? (int64_t)data->ell_w : data->max_rowlen,
+                                             data->shadow_ell, data->ell_w}
+                                   : CsrPtrs{};
+      // (the stamps of the workgroup kernel: dense f64 rows on a ranking tier)
+      unsigned long long* wdbg = kF64 && !data->csr && p.tier > 0 ? dbg : nullptr;
+      dbgprint.p = wdbg;
+      RPT_HIP(launch_dyn(kern, dim3((unsigned)q->n), block, p.smem, ctx->stream, (const TD*)data->X, data->d,
+                         (const TD*)q->X, f->perm.p, f->thr.p, f->mglo.p, f->mghi.p, f->nodes, (const TK*)Pq, q->n,
+                         f->T, f->L, f->min_leaf, f->n, k, dedup, ids, dist, cnt, ovf + 1, ovf, cand_total, shadow,
+                         xmax, p.k1, cp, p.sh16 ? 1 : 0, s8, wdbg));
       return RPT_OK;
     }
   }
-  if constexpr (!std::is_same<TD, __hip_bfloat16>::value) {
-    if (data->csr) {  // SVector rows: the same kernel, distances over CSR rows
-      const CsrPtrs cp{data->rowptr, data->col, data->val, data->nnz, q->rowptr, q->col, q->val,
-                       nullptr, nullptr, 0, nullptr, 0};
-      if (smem > 64 * 1024)
-        RPT_HIP(hipFuncSetAttribute((const void*)knn_fused_kernel<TD, TK, false, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      hipLaunchKernelGGL((knn_fused_kernel<TD, TK, false, true>), dim3((unsigned)q->n), dim3(256),
-                         smem, ctx->stream, (const TD*)nullptr, data->d, (const TD*)nullptr,
-                         f->perm.p, f->thr.p, f->mglo.p, f->mghi.p, f->nodes, (const TK*)Pq, q->n,
-                         f->T, f->L, f->min_leaf, f->n, k, dedup, ids, dist, cnt, ovf + 1, ovf,
-                         cand_total, (const void*)nullptr, 0.0, rerun ? -1 : 0, cp);
-      RPT_HIP(hipGetLastError());
-      return RPT_OK;
-    }
-  }
-  if (smem > 64 * 1024)
-    RPT_HIP(hipFuncSetAttribute((const void*)knn_fused_kernel<TD, TK, false>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  hipLaunchKernelGGL((knn_fused_kernel<TD, TK, false>), dim3((unsigned)q->n), dim3(256), smem,
-                     ctx->stream, (const TD*)data->X, data->d, (const TD*)q->X, f->perm.p,
-                     f->thr.p, f->mglo.p, f->mghi.p, f->nodes, (const TK*)Pq, q->n, f->T, f->L,
-                     f->min_leaf, f->n, k, dedup, ids, dist, cnt, ovf + 1, ovf, cand_total,
-                     (const void*)nullptr, 0.0, rerun ? -1 : 0, CsrPtrs{});
-  RPT_HIP(hipGetLastError());
-  return RPT_OK;
+  return fail(RPT_E_UNSUPPORTED, "fused kNN: no kernel for the plan");
 }
 
 static int32_t knn_general(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
@@ -4593,23 +4446,16 @@ static int32_t knn_general(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
     const size_t smem = topk_smem(data->d, 8);
     ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
     if (data->dtype == RPT_F64) {
-      if (smem > 64 * 1024)
-        RPT_HIP(hipFuncSetAttribute((const void*)topk_csr_kernel<double>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      hipLaunchKernelGGL(topk_csr_kernel<double>, dim3((unsigned)q->n), dim3(256), smem,
+      RPT_HIP(launch_dyn(topk_csr_kernel<double>, dim3((unsigned)q->n), dim3(256), smem,
                          ctx->stream, data->rowptr, data->col, (const double*)data->val, data->nnz, data->d,
                          q->rowptr, q->col, (const double*)q->val, f->perm.p, pl.ranges.p,
-                         pl.rng_off.p, f->T, k, dedup, refm, ids_dev, dist_dev, count_dev);
+                         pl.rng_off.p, f->T, k, dedup, refm, ids_dev, dist_dev, count_dev));
     } else {
-      if (smem > 64 * 1024)
-        RPT_HIP(hipFuncSetAttribute((const void*)topk_csr_kernel<float>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      hipLaunchKernelGGL(topk_csr_kernel<float>, dim3((unsigned)q->n), dim3(256), smem,
+      RPT_HIP(launch_dyn(topk_csr_kernel<float>, dim3((unsigned)q->n), dim3(256), smem,
                          ctx->stream, data->rowptr, data->col, (const float*)data->val, data->nnz, data->d,
                          q->rowptr, q->col, (const float*)q->val, f->perm.p, pl.ranges.p,
-                         pl.rng_off.p, f->T, k, dedup, refm, ids_dev, dist_dev, count_dev);
+                         pl.rng_off.p, f->T, k, dedup, refm, ids_dev, dist_dev, count_dev));
     }
-    RPT_HIP(hipGetLastError());
   } else if (data->dtype == RPT_F64) {
     RPT_TRY(unc.alloc((size_t)q->n));
     RPT_TRY(launch_l2_f64(ctx, data, q, f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, 0, k, dedup, unc.p, ids_dev,
@@ -4652,7 +4498,6 @@ int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_
     return fail(RPT_E_UNSUPPORTED, "RPT_KNN_VOTE: dense data, k <= 64 and at most 1024 trees");
   if (!fused || q->n == 0) return knn_general(ctx, f, data, q, k, flags, ids_dev, dist_dev, count_dev);
   const int64_t nq = q->n;
-  const int dedup = (flags & 3) | (vote << 8);
   DevBuf<char> Pq;
   // one control block, one memset, one read-back: u64 candidates visited, u64 queries whose
   // prefilter cut was not certified, u32 queries that overflowed the range slab, pad, flags[nq]
@@ -4667,51 +4512,27 @@ int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_
     ProfScope ps(ctx, RPT_PROF_KNN_PLAN);
     if (f->L > 0) RPT_TRY(project_columns(ctx, q, f->R.p, f->T * f->L, f->mode, Pq.p));
   }
-  if (f->pdtype == RPT_F64 && dedup == 0 && prefilter_keep(k) < kFK && !ctx->opt.knn_no_pre32 &&
-      !f->prefilter_off) {  // (dedup carries the vote threshold too: no prefilter when voting)
-    if (!data->csr) {
-      // the int8 shadow first; the f32 and half ones (+75 % of the dataset) only when it cannot rank
-      // this call: rows that are not a multiple of 16 elements, k beyond what the tier keeps in the
-      // one-wave kernel, no memory, or a forest that has dropped the tier (once per dataset each)
-      const bool want8 = !ctx->opt.knn_no_pre16 && !f->pre16_off && !ctx->opt.knn_no_pre8 && !f->pre8_off;
-      if (want8) RPT_TRY(ensure_shadow8(ctx, data));
-      if (!(want8 && data->shadow8 && k + 8 <= 47)) {
-        RPT_TRY(ensure_shadow(ctx, data));
-        if (data->shadow32 && !ctx->opt.knn_no_pre16 && !f->pre16_off) RPT_TRY(ensure_shadow16(ctx, data));
-      }
-    }
-    // CSR rows: the (u16, f32) shadow halves the bytes of the ranking pass but NOT its time — at C3
-    // the exact kernel already gathers rows at 6.4 TB/s and the f32 pass, with its 17 selection
-    // rounds per batch, is bound by its serial phases (14.3 ms against 13.8 ms per 10 000 queries):
-    // opt-in (knn_csr_pre32), kept for bandwidth-poorer configurations and pinned by a test
-    else if (data->dtype == RPT_F64 && data->d <= 65536) {
-      if (ctx->opt.knn_csr_pre32) RPT_TRY(ensure_shadow_csr(ctx, data));
-      if (!ctx->opt.knn_no_pre16 && !f->pre16_off) RPT_TRY(ensure_shadow_ell(ctx, data));
-    }
+  // the shadows the call ranks on, each built once per dataset (an ensure_* may leave its shadow absent)
+  FusedIn in = fused_input(ctx, f, data, k, flags & 3, vote);
+  for (unsigned tried = 0, want; (want = fused_shadows_wanted(in, tried)) != 0; tried |= want) {
+    if (want & kShadow8) RPT_TRY(ensure_shadow8(ctx, data));
+    if (want & kShadow32) RPT_TRY(ensure_shadow(ctx, data));
+    if (want & kShadow16) RPT_TRY(ensure_shadow16(ctx, data));
+    if (want & kShadowCsr32) RPT_TRY(ensure_shadow_csr(ctx, data));
+    if (want & kShadowEll) RPT_TRY(ensure_shadow_ell(ctx, data));
+    fused_input_shadows(in, data);
   }
   int tier = 0;
-  if (data->dtype == RPT_F32 && !data->csr && dedup == 0 && !ctx->opt.knn_no_pre16 &&
-      !ctx->opt.knn_no_pre32 && !f->pre16_off) {
-    const bool want8 = !ctx->opt.knn_no_pre8 && !f->pre8_off;
-    if (want8) RPT_TRY(ensure_shadow8(ctx, data));
-    if (!(want8 && data->shadow8 && k + 8 <= 47)) RPT_TRY(ensure_shadow16(ctx, data));
-  }
-  // bf16 rows: the int8 tier exists (identical answers, tested) but is OPT-IN (knn_kp8 > 0): at C5
-  // (10 M x 768, k = 50) the cut needs 200 kept rows to certify 99 % of the queries and the pass is
-  // then no faster than the plain bf16 kernel (82 against 68 ms per 100 000 queries) — its 768-byte
-  // rows keep half the bytes in flight per wave — while the shadow costs 7.7 GB
-  if (data->dtype == RPT_BF16 && !data->csr && dedup == 0 && ctx->opt.knn_kp8 > 0 && !ctx->opt.knn_no_pre16 &&
-      !ctx->opt.knn_no_pre32 && !ctx->opt.knn_no_pre8 && !f->pre16_off && !f->pre8_off && !f->prefilter_off)
-    RPT_TRY(ensure_shadow8(ctx, data));
   auto launch = [&](bool rerun) -> int32_t {
+    in.rerun = rerun;
+    const FusedPlan p = fused_plan(in);
+    if (!rerun) tier = p.tier;
     if (f->pdtype == RPT_F64)
-      return launch_fused<double, double>(ctx, f, data, q, Pq.p, k, dedup, ids_dev, dist_dev,
-                                          count_dev, ovf_p, ctot_p, rerun, rerun ? nullptr : &tier);
+      return launch_fused<double, double>(ctx, f, data, q, Pq.p, in, p, ids_dev, dist_dev, count_dev, ovf_p, ctot_p);
     if (data->dtype == RPT_F32)
-      return launch_fused<float, float>(ctx, f, data, q, Pq.p, k, dedup, ids_dev, dist_dev,
-                                        count_dev, ovf_p, ctot_p, rerun, rerun ? nullptr : &tier);
-    return launch_fused<__hip_bfloat16, float>(ctx, f, data, q, Pq.p, k, dedup, ids_dev, dist_dev,
-                                               count_dev, ovf_p, ctot_p, rerun, rerun ? nullptr : &tier);
+      return launch_fused<float, float>(ctx, f, data, q, Pq.p, in, p, ids_dev, dist_dev, count_dev, ovf_p, ctot_p);
+    return launch_fused<__hip_bfloat16, float>(ctx, f, data, q, Pq.p, in, p, ids_dev, dist_dev, count_dev, ovf_p,
+                                               ctot_p);
   };
   RPT_TRY(launch(false));
   // (read back into the pinned arena: a pageable destination makes the copy a staged, blocking one)
@@ -4731,19 +4552,9 @@ int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_
                 "RPT_KNN_VOTE: a query reaches more than 16384 candidates or 512 leaves");
   if (novf)  // some query reached more leaf ranges than the LDS slab holds: general path
     return knn_general(ctx, f, data, q, k, flags, ids_dev, dist_dev, count_dev);
-  // too many uncertified cuts: one tier down for the later batches on this forest (half -> f32
-  // shadow -> all-f64)
-  if (tot[1] * 4 > (unsigned long long)nq) {
-    if (tier == 3) f->pre8_off = true;
-    else if (tier == 2) f->pre16_off = true;
-    else if (tier == 1) f->prefilter_off = true;  // (tier 0: the count is the f64 kernels' own)
-  }
   ctx->last_tier = tier;
-  // a batch in which more than an eighth of the queries needed the wider second attempt: the next
-  // batches on this forest start wider (the int8 tier's kept entries; capped by the kernel's list)
   ctx->last_retries = (int64_t)hctl[4];
-  if (tier == 3 && (unsigned long long)hctl[4] * 8 > (unsigned long long)nq && f->kp8_boost < 4.0)
-    f->kp8_boost *= 1.5;
+  fused_after_batch(f->tiers, tier, (uint64_t)nq, tot[1], hctl[4]);
   if (tot[1] && data->dtype == RPT_F64 && !data->csr) {
     // dense f64 rows whose cut no kernel could certify (different rows that tie at the cut, to the
     // last bits or exactly): the exact kernel over the query plan, them only — the definition
@@ -4758,7 +4569,7 @@ int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_
                        ovf_p + 1, nq, unc.p, uc);
     RPT_HIP(hipGetLastError());
     RPT_TRY((launch_metric_v<double, kMetricL2, true>(ctx, data, q, f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, 0,
-                                                      k, dedup & 3, unc.p, uc, ids_dev, dist_dev, count_dev)));
+                                                      k, flags & 3, unc.p, uc, ids_dev, dist_dev, count_dev)));
     RPT_HIP(stream_sync(ctx->stream));  // the plan, unc and ovf are released on return
   } else if (tot[1]) {  // f32 / CSR rows with equal distances at the prefilter's cut: the exact kernel, them only
     RPT_TRY(launch(true));
@@ -4861,40 +4672,28 @@ int32_t knn_h(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_da
     const size_t smem = (size_t)data->d * 8;
     RPT_ARG(smem <= 150 * 1024, "d too large");
     if (data->dtype == RPT_F64) {
-      if (smem > 64 * 1024)
-        RPT_HIP(hipFuncSetAttribute((const void*)dist_sel_csr_kernel<double>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      hipLaunchKernelGGL(dist_sel_csr_kernel<double>, dim3((unsigned)nq), dim3(256), smem, st,
+      RPT_HIP(launch_dyn(dist_sel_csr_kernel<double>, dim3((unsigned)nq), dim3(256), smem, st,
                          data->rowptr, data->col, (const double*)data->val, data->d, q->rowptr,
                          q->col, (const double*)q->val, f->perm.p, dsel.p, dsel_off.p, dout_off.p,
-                         ids.p, dist.p);
+                         ids.p, dist.p));
     } else {
-      if (smem > 64 * 1024)
-        RPT_HIP(hipFuncSetAttribute((const void*)dist_sel_csr_kernel<float>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      hipLaunchKernelGGL(dist_sel_csr_kernel<float>, dim3((unsigned)nq), dim3(256), smem, st,
+      RPT_HIP(launch_dyn(dist_sel_csr_kernel<float>, dim3((unsigned)nq), dim3(256), smem, st,
                          data->rowptr, data->col, (const float*)data->val, data->d, q->rowptr,
                          q->col, (const float*)q->val, f->perm.p, dsel.p, dsel_off.p, dout_off.p,
-                         ids.p, dist.p);
+                         ids.p, dist.p));
     }
   } else {
     const size_t smem = (size_t)data->d * (data->dtype == RPT_F64 ? 8 : 4);
     RPT_ARG(smem <= 150 * 1024, "d too large");
 #define RPT_DIST_SEL(TD)                                                                      \
-  do {                                                                                        \
-    if (smem > 64 * 1024)                                                                     \
-      RPT_HIP(hipFuncSetAttribute((const void*)dist_sel_dense_kernel<TD>,                     \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));    \
-    hipLaunchKernelGGL(dist_sel_dense_kernel<TD>, dim3((unsigned)nq), dim3(256), smem, st,    \
-                       (const TD*)data->X, data->d, (const TD*)q->X, f->perm.p, dsel.p,       \
-                       dsel_off.p, dout_off.p, ids.p, dist.p);                                \
-  } while (0)
+  RPT_HIP(launch_dyn(dist_sel_dense_kernel<TD>, dim3((unsigned)nq), dim3(256), smem, st,      \
+                     (const TD*)data->X, data->d, (const TD*)q->X, f->perm.p, dsel.p,         \
+                     dsel_off.p, dout_off.p, ids.p, dist.p))
     if (data->dtype == RPT_F64) RPT_DIST_SEL(double);
     else if (data->dtype == RPT_F32) RPT_DIST_SEL(float);
     else RPT_DIST_SEL(__hip_bfloat16);
 #undef RPT_DIST_SEL
   }
-  RPT_HIP(hipGetLastError());
   RPT_HIP(stream_sync(st));
   RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)*total * 4, hipMemcpyDeviceToHost));
   RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)*total * 8, hipMemcpyDeviceToHost));
@@ -4908,12 +4707,8 @@ static int32_t launch_merge(rpt_ctx* ctx, const int32_t* ids, const double* dist
   int np = 1;
   while (np < G * k) np <<= 1;
   const size_t smem = (sizeof(Entry) + 4) * (size_t)np;
-  if (smem > 64 * 1024)
-    RPT_HIP(hipFuncSetAttribute((const void*)merge_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  hipLaunchKernelGGL(merge_kernel, dim3((unsigned)nq), dim3(256), smem, ctx->stream, ids, dist,
-                     cnt, is, ds, cs, G, nq, k, flags & 3, out_ids, out_dist, out_count);
-  RPT_HIP(hipGetLastError());
+  RPT_HIP(launch_dyn(merge_kernel, dim3((unsigned)nq), dim3(256), smem, ctx->stream, ids, dist,
+                     cnt, is, ds, cs, G, nq, k, flags & 3, out_ids, out_dist, out_count));
   return RPT_OK;
 }
 
@@ -5186,16 +4981,12 @@ static int32_t launch_brute_csr_t(rpt_ctx* ctx, const rpt_dataset* data, const r
                                   int refm, int64_t rows_per_block, int nblk, int32_t* ids,
                                   double* dist, int32_t* cnt) {
   const size_t smem = brute_csr_smem(data->d, QT, k);
-  if (smem > 64 * 1024)
-    RPT_HIP(hipFuncSetAttribute((const void*)brute_csr_kernel<TD, QT>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   const int64_t tiles = (q->n + QT - 1) / QT;
-  hipLaunchKernelGGL((brute_csr_kernel<TD, QT>), dim3((unsigned)tiles, (unsigned)nblk),
+  RPT_HIP(launch_dyn(brute_csr_kernel<TD, QT>, dim3((unsigned)tiles, (unsigned)nblk),
                      dim3(kBcThreads), smem, ctx->stream, data->rowptr, data->col,
                      (const TD*)data->val, data->nnz, data->n, data->d, q->rowptr, q->col,
                      (const TD*)q->val, q->n, k, brute_csr_cap(k), rows_per_block, refm, ids, dist,
-                     cnt);
-  RPT_HIP(hipGetLastError());
+                     cnt));
   return RPT_OK;
 }
 
