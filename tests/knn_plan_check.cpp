@@ -306,6 +306,124 @@ int main() {
     fused_after_batch(st, 3, 64, 0, 64);
     CHECK(st.kp8_boost == 4.0);
   }
+  {  // 29-33: the shapes of tests/test_gpu_knn_tier_bounds.py reach the kernel and the tier they are meant for
+    row = "29-33";
+    // sweeps: n = 6397, L = 6, minLeaf 100 -> leaves of 100; the shadows are those the call's own walk builds
+    auto sweep = [](int T, int d, int k) {
+      FusedIn in;
+      in.d = d;
+      in.k = k;
+      in.T = T;
+      in.L = 6;
+      in.min_leaf = 100;
+      in.n = 6397;
+      return in;
+    };
+    auto walked = [](FusedIn in) {  // rows that are not a multiple of 16 elements get no int8 shadow
+      unsigned st[8];
+      walk_shadows(in, in.d % 16 ? kShadow8 : 0u, st);
+      for (unsigned i = 0; i < 8; ++i) {
+        const unsigned got = st[i] & ~(in.d % 16 ? kShadow8 : 0u);
+        if (got & kShadow8) in.shadow8 = true;
+        if (got & kShadow32) in.shadow32 = true;
+        if (got & kShadow16) in.shadow16 = true;
+        if (got & kShadowCsr32) in.shadow32 = in.shadow_col16 = true;
+        if (got & kShadowEll) in.shadow_ell = true;
+      }
+      return in;
+    };
+    auto block = [](int d, size_t acc) { return (size_t)(2048 * 16 + 512 * 12 + 8192 + 232 * 16 + 64) + (size_t)d * (acc + 4); };
+    CHECK(fused_plan(sweep(12, 16, 10)).est_cand == 1200);
+    // 29: the workgroup kernel (12 x 100 candidates would be the shard kernels': knn_wave = 0)
+    FusedIn in = sweep(12, 16, 10);
+    in.knn_wave = 0;
+    in.knn_no_pre16 = true;
+    expect("29a", walked(in), Family::Workgroup, 1, 17, block(16, 8));
+    in = sweep(12, 208, 24);
+    in.knn_wave = 0;
+    in.knn_no_pre8 = true;
+    expect("29b", walked(in), Family::Workgroup, 2, 37, block(208, 8));
+    in.knn_no_pre8 = false;  // int8: margin 48 sqrt(208 / 128) = 61
+    expect("29c", walked(in), Family::Workgroup, 3, 86, block(208, 8));
+    in = sweep(12, 208, 1);
+    in.knn_wave = 0;
+    in.elem = in.proj = Elem::F32;
+    in.knn_no_pre8 = true;
+    expect("29d", walked(in), Family::Workgroup, 2, 10, block(208, 4));
+    // 30: the one-wave kernel: 6 x 100, knn_wave = 1 and knn_shard_old = 1
+    in = sweep(6, 37, 10);
+    in.knn_wave = 1;
+    in.knn_shard_old = true;
+    in.knn_no_pre8 = true;  // (d = 37: no int8 shadow either way)
+    expect("30a", walked(in), Family::Wave, 2, 19, 4 * 10816);  // 512 * 12 + 128 * 24 + 72 * 16 + 37 * 12 = 10812
+    in.knn_no_pre8 = false;
+    in.knn_no_pre16 = true;
+    expect("30b", walked(in), Family::Wave, 1, 17, 4 * 10816);
+    in = sweep(6, 128, 24);
+    in.knn_wave = 1;
+    in.knn_shard_old = true;
+    expect("30c", walked(in), Family::Wave, 3, 48, kWave128);
+    // 31: the shard kernels: 4 x 100 is one batch, 8 x 100 several
+    in = sweep(4, 128, 1);
+    in.knn_no_pre16 = true;
+    expect("31a", walked(in), Family::Shard, 1, 8, kShardOne128);
+    CHECK(fused_plan(walked(in)).one_batch);
+    in = sweep(8, 16, 24);
+    in.knn_no_pre8 = true;
+    expect("31b", walked(in), Family::Shard, 2, 37, 4 * (640 * 8 + 128 * 8 + 132 * 4 + 256 * 20 + 16 + 16 * 8 + 16 * 4));
+    CHECK(!fused_plan(walked(in)).one_batch);
+    in = sweep(8, 208, 10);
+    in.elem = in.proj = Elem::F32;
+    in.knn_no_pre8 = true;
+    expect("31c", walked(in), Family::Shard, 2, 19, 4 * (640 * 8 + 128 * 8 + 132 * 4 + 256 * 20 + 16 + 208 * 4 + 208 * 4));
+    in = sweep(4, 37, 10);
+    in.knn_no_pre8 = true;
+    // (the query's 37 * 8 = 296 bytes are padded to 304: 4096 + 1024 + 528 + 2560 + 16 + 304 + 148 = 8676 -> 8688)
+    expect("31d", walked(in), Family::Shard, 2, 19, 4 * 8688);
+    // 32: the aligned cases: ONE tree of depth 0, every row a candidate (301 rows; 1301: several batches)
+    auto leaf = [](int n, int d, int k) {
+      FusedIn in;
+      in.d = d;
+      in.k = k;
+      in.T = 1;
+      in.L = 0;
+      in.min_leaf = 0;
+      in.n = n;
+      return in;
+    };
+    in = leaf(301, 16, 10);
+    in.knn_no_pre16 = true;
+    CHECK(fused_plan(in).est_cand == 301);
+    expect("32a", walked(in), Family::Shard, 1, 17, 4 * (512 * 8 + 128 * 8 + 132 * 4 + 128 * 20 + 16 + 16 * 8 + 16 * 4));
+    CHECK(fused_plan(walked(in)).one_batch);
+    in.knn_wave = 0;
+    expect("32b", walked(in), Family::Workgroup, 1, 17, block(16, 8));
+    in.knn_wave = 1;
+    in.knn_shard_old = true;
+    expect("32c", walked(in), Family::Wave, 1, 17, 4 * (512 * 12 + 128 * 24 + 72 * 16 + 16 * 12));
+    in = leaf(1301, 128, 24);
+    in.knn_no_pre8 = true;
+    expect("32d", walked(in), Family::Shard, 2, 37, kShardTwo128);
+    CHECK(!fused_plan(walked(in)).one_batch);
+    in = leaf(301, 37, 1);
+    in.elem = in.proj = Elem::F32;
+    in.knn_wave = 0;
+    expect("32e", walked(in), Family::Workgroup, 2, 10, block(37, 4));
+    // 33: SVector rows: the workgroup kernel whatever the shape; the half table by default, the (u16, f32)
+    // shadow under knn_csr_pre32 + knn_no_pre16
+    in = leaf(301, 64, 10);
+    in.csr = true;
+    expect("33a", walked(in), Family::Workgroup, 2, 19, block(64, 8));
+    CHECK(fused_plan(walked(in)).csr_rank == CsrRank::Ell);
+    in.knn_csr_pre32 = in.knn_no_pre16 = true;
+    expect("33b", walked(in), Family::Workgroup, 1, 17, block(64, 8));
+    CHECK(fused_plan(walked(in)).csr_rank == CsrRank::Shadow32);
+    in = sweep(12, 64, 24);
+    in.csr = true;
+    expect("33c", walked(in), Family::Workgroup, 2, 37, block(64, 8));
+    in.knn_csr_pre32 = in.knn_no_pre16 = true;
+    expect("33d", walked(in), Family::Workgroup, 1, 37, block(64, 8));
+  }
   if (failures) {
     std::printf("%d checks failed\n", failures);
     return 1;
