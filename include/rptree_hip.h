@@ -338,7 +338,17 @@ int32_t rpt_knnh_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
  * per-query error bound certifies the cut (a query that fails it is tried once more with three
  * times the kept entries, then takes the all-f64 path).
  * Results are identical either way.  A dataset borrowed with rpt_dataset_dense_dev must not be
- * modified while the library holds it. */
+ * modified while the library holds it.
+ * Dense f32 / bf16 rows under L2: the elements are widened to f32 exactly and every difference,
+ * square and sum is rounded to f32 (no FMA); the answer is the k best of ALL candidates by (that f32
+ * squared distance, candidate position) under the duplicate rule, and the distance returned is
+ * sqrt((double)it).  Every returned distance lies within (d + 2) 2^-24 relative, plus sqrt(d) 4e-23
+ * for products in the f32 subnormal range, of the true Euclidean distance of the widened rows (the
+ * bound the ranking tiers' certificates on f32 data rely on), and the answer is the definition's bit
+ * for bit wherever f32 arithmetic is exact.  A row is summed in one fixed order on every query path,
+ * rpt_brute_knn_* and the truth of rpt_recall_hits_host included, so neither the bits nor the order
+ * of near-tied candidates depend on the path.  tests/test_gpu_knn_f32_l2.py holds every path to both
+ * statements against an f64 reference (tests/knn_f32_ref.py), every query. */
 int32_t rpt_knn_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
                      const rpt_dataset* queries, int32_t k, int32_t flags, int32_t* ids_host,
                      double* dist_host, int32_t* count_host);
@@ -382,7 +392,8 @@ int32_t rpt_build_last_handed_back(rpt_ctx* ctx, int64_t* nodes, int64_t* incons
  *              fold, every difference, square and sum rounded on its own, no FMA; f32 and bf16
  *              elements are widened exactly first.  The values are doubles and bit-exact against
  *              this definition for all three dtypes (as the cosine / inner-product metrics are, and
- *              unlike rpt_knn_*, whose L2 on f32 / bf16 rows is f32 arithmetic).  The fold is
+ *              unlike rpt_knn_*, whose L2 on f32 / bf16 rows is f32 arithmetic within a stated
+ *              bound of the true distance, see rpt_knn_host).  The fold is
  *              symmetric bit for bit, dist(i, j) == dist(j, i): a pair is evaluated once.
  *   answer     the first k of mates(i) ordered by (distance, id); NaN ranks behind every number,
  *              NaNs among themselves by id.  count[i] = min(k, |mates(i)|); unused slots hold

@@ -738,6 +738,28 @@ __global__ __launch_bounds__(256) void topk_dense_kernel(
           idv[u] = identity ? c : perm[rg.poff + c];
           s[u] = (TA)0;
         }
+        // f32 / bf16 rows: the value IS the answer's distance and what the candidates are ranked on,
+        // so a row is summed in the order of batch_distances (the fused kernels): rows of whole
+        // 16-byte pieces give every lane the pieces lane, lane + 64, ... and each piece a left fold,
+        // other rows the elements lane, lane + 64, ...; then the same butterfly.  (The lanes beyond a
+        // short row add +0.0, which changes nothing.)  A query then gets the same bits and the same
+        // order of near-ties on this path, the brute force included, as on the fused ones.
+        constexpr int V = 16 / (int)sizeof(TD);
+        if (!F64 && (d % V) == 0) {
+          struct alignas(16) Raw { TD v[V]; };
+          for (int j = lane * V; j < d; j += 64 * V) {
+            Raw x[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) x[u] = *reinterpret_cast<const Raw*>(X + (int64_t)idv[u] * d + j);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+              for (int v = 0; v < V; ++v) {
+                const TA df = ld<TD>(&x[u].v[v]) - qs[j + v];
+                s[u] += df * df;
+              }
+          }
+        } else
         for (int j = lane; j < d; j += 64) {
           const TA qj = qs[j];
           TA x[4];
@@ -1199,6 +1221,8 @@ struct Sh8 {
 //   int8 shadow: A = eq + emax (triangle inequality, Sh8), Bt = 0;  Dh = (s / 256) sqrt(I) and the
 //                value kept is I rounded to f32 (rnd = 1.2e-7 covers it)
 //   f32 DATA   : "exact" is the f32 distance the all-f32 kernel ranks on, within Bf = (d + 2) u of D
+//                (every kernel that returns it is held to that bound, every query, by
+//                tests/test_gpu_knn_f32_l2.py; tests/test_knn_f32_host.py: honest f32 sums reach 0.22 of it)
 // The stored ranking value v is a non-negative float (a squared distance, or I); Dh = g sqrt(v).
 struct TierBounds {
   double A, Bt, Bf, g, rnd;

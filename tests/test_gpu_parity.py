@@ -2,8 +2,14 @@
 seeded inputs.  Integer / index results must be IDENTICAL; exact-order projections must be
 bit-identical; MFMA projections within 1e-5 * |x||r| (north_star tolerance, norm-relative
 because a projection can cancel to ~0)."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import knn_f32_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -1015,6 +1021,14 @@ def test_knn_f32_data(rp, ctx, oracle):
     ref = np.sqrt(((X[ids[:, 1]].astype(np.float64) - X[:50].astype(np.float64)) ** 2).sum(1))
     assert np.allclose(dist[:, 1], ref, rtol=1e-5)
     assert (bi[:, 0] == np.arange(50)).all()
+    # bruteKnn, all k columns: the k best of all rows by (distance, id) within the f32 kernel's stated
+    # error bound of the f64 reference (tests/knn_f32_ref.py: check_interval over every row in id order)
+    allrows = np.arange(n, dtype=np.int32)
+    X64 = X.astype(np.float64)
+    for i in range(50):
+        knn_f32_ref.check_interval(allrows, knn_f32_ref.exact_dist(X64, X64[i]), bi[i], bd[i], 5, 5,
+                                   knn_f32_ref.KEEP, d)
+        assert bd[i, 0] == 0.0
 
 
 @pytest.mark.parametrize("shape", [(20000, 16, 12, 100), (20000, 16, 6, 100), (12000, 200, 8, 200),
