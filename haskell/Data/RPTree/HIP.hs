@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, recallWithHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -59,6 +59,8 @@ foreign import ccall safe "rpt_graph_search_host" c_graph_search_host :: Ptr Ctx
 foreign import ccall safe "rpt_graph_search_csr_host" c_graph_search_csr_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_host" c_graph_prepare_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_csr_host" c_graph_prepare_csr_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_csr_metric_host" c_knn_csr_metric_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_recall_hits_csr_metric_host" c_recall_hits_csr_metric :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
 -- multi-GPU (csrc/comm.hip on librccl): one process drives n devices; per-device arguments are
 -- arrays with one entry per device (Foreign.Marshal.Array.withArray)
@@ -418,6 +420,41 @@ recallWithHIP refMetric ctx f ds ntrees dim k qs =
         flags = if refMetric then 16777216 else 0     -- RPT_KNN_METRIC_REFERENCE (1 << 24)
     hits <- VSM.new (max 1 (nq * ntrees)); truth <- VSM.new (max 1 (nq * k))
     VSM.unsafeWith hits (\a -> VSM.unsafeWith truth (c_recall_hits ctx f ds qd (fromIntegral k) flags a)) >>= check
+    hs <- VS.freeze hits
+    let rec i = sum [ fromIntegral (hs VS.! (i * ntrees + t)) / fromIntegral k | t <- [0 .. ntrees - 1] ]
+                / fromIntegral ntrees
+    pure (V.generate nq rec)
+
+-- | 'knn distf k' (RPTree.hs:168-176) over an SVector forest under 'MetricCosine' / 'MetricInner', for
+-- a batch of SVector queries (rpt_knn_csr_metric_host).  The dot is a LEFT fold from +0.0 over the
+-- indices stored in both vectors, in ascending order, every product and sum rounded on its own: the
+-- products innerSS (Internal.hs:323) adds from the right, added from the left, so that the answer is
+-- the one 'knnMetricHIP' gives on the dense-ified rows whenever the stored values are finite; a stored
+-- Infinity / NaN counts only where both vectors store the index.  NaN (an empty or all-zero vector
+-- under 'MetricCosine') ranks last.  'MetricL2' is refused here (RPT_E_ARG): that is 'knnHIP' on the
+-- SVector forest.  @ds@ is the forest's point set ('withDeviceDataSV').
+knnMetricSVHIP :: Metric -> Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int -> Int
+               -> V.Vector (SVector Double) -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnMetricSVHIP m ctx f ds dim k qs =
+  withDeviceDataSV ctx dim qs $ \qd -> do
+    let nq = V.length qs
+    ids <- VSM.new (max 1 (nq * k)); dist <- VSM.new (max 1 (nq * k)); cnt <- VSM.new (max 1 nq)
+    VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt
+      (c_knn_csr_metric_host ctx f ds qd (fromIntegral k) (metricFlag m) a b))) >>= check
+    (,,) <$> (VS.take (nq * k) <$> VS.freeze ids) <*> (VS.take (nq * k) <$> VS.freeze dist)
+         <*> (VS.take nq <$> VS.freeze cnt)
+
+-- | 'recallWith distf forest k' (RPTree.hs:259-282) for a batch of SVector queries over an SVector
+-- forest under 'MetricCosine' / 'MetricInner' (rpt_recall_hits_csr_metric_host): the truth is the
+-- exhaustive search under 'knnMetricSVHIP''s distance, by (distance, id).
+recallWithMetricSVHIP :: Metric -> Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int -> Int -> Int
+                      -> V.Vector (SVector Double) -> IO (V.Vector Double)
+recallWithMetricSVHIP m ctx f ds ntrees dim k qs =
+  withDeviceDataSV ctx dim qs $ \qd -> do
+    let nq = V.length qs
+    hits <- VSM.new (max 1 (nq * ntrees)); truth <- VSM.new (max 1 (nq * k))
+    VSM.unsafeWith hits (\a -> VSM.unsafeWith truth
+      (c_recall_hits_csr_metric ctx f ds qd (fromIntegral k) (metricFlag m) a)) >>= check
     hs <- VS.freeze hits
     let rec i = sum [ fromIntegral (hs VS.! (i * ntrees + t)) / fromIntegral k | t <- [0 .. ntrees - 1] ]
                 / fromIntegral ntrees

@@ -889,6 +889,8 @@ int32_t rpt_brute_knn_metric_host(rpt_ctx* ctx, const rpt_dataset* data,
  *                             `recallWith metricL2` of the reference computes on SVector rows.
  *                             Dense data: RPT_E_ARG, as before.
  * RPT_KNN_METRIC_COSINE / _INNER on CSR data: RPT_E_UNSUPPORTED.
+ * (Those two distances on CSR data have entry points of their own: rpt_knn_csr_metric_*,
+ * rpt_brute_knn_csr_metric_* and rpt_recall_hits_csr_metric_host, below.)
  * One workgroup answers a tile of queries (dense-ified in LDS) against a block of rows streamed
  * once; the option brute_csr_tile sets the tile, the answer does not depend on it. */
 /* ... and into device arrays ids_dev / dist_dev [nq][k], for dense data (flags 0,
@@ -910,6 +912,62 @@ int32_t rpt_recall_hits_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* dat
                              const rpt_dataset* queries, int32_t k, int32_t flags,
                              int32_t* hits_host /*[nq][T]*/,
                              int32_t* truth_ids_host /*[nq][k], may be NULL*/);
+
+/* ---- cosine and inner-product kNN on SVector (CSR) rows ----
+ * rpt_knn_*, rpt_brute_knn_* and rpt_recall_hits_host for CSR data with CSR queries (same d, same
+ * dtype, f64 or f32 values widened exactly) under RPT_KNN_METRIC_COSINE / _INNER.  The definition:
+ * for two CSR rows with strictly ascending columns, dotS(x, q) starts at +0.0, takes the columns
+ * stored in BOTH rows in ascending column order, and for each acc = acc + x_j * q_j: a left fold,
+ * every product and sum rounded on its own, no FMA.
+ *   RPT_KNN_METRIC_INNER : dist = -dotS(x, q)
+ *   RPT_KNN_METRIC_COSINE: dist = 1 - dotS(x, q) / (sqrt(dotS(x, x)) * sqrt(dotS(q, q))), NaN for an
+ *                          empty or all-zero row or query; NaN ranks last.
+ * Equal to the dense definition for finite values: when every stored value of both rows is finite
+ * this is RPT_KNN_METRIC_INNER / _COSINE of the dense-ified rows bit for bit (a column one side
+ * lacks would add x * (+0.0) = +-0.0 to an acc that is never -0.0), so rpt_knn_* and
+ * rpt_brute_knn_metric_* on the dense-ified data give the same ids and distance bits.
+ * Different with a stored inf or NaN: the dense-ified fold meets inf * 0 = NaN, this one does not —
+ * a column counts only where both rows store it, which is what the reference's innerSS
+ * (Internal.hs:323) visits.  Not the reference's fold order: innerSS adds the same products from the
+ * right, x0 q0 + (x1 q1 + (... + 0)), which differs in the last bits and is not built; the left fold
+ * is chosen so that CSR and dense-ified data give one answer.
+ * Selection: rpt_brute_knn_csr_metric_*: the k best of rows 0 .. n-1 by (distance, id).
+ * rpt_knn_csr_metric_*: the k best of all candidates by (distance, candidate position) under the
+ * duplicate rule of `flags`.  Both: NaN behind every number, unused slots id -1 and distance +inf,
+ * -0.0 ties with +0.0 and the stored bits are the computed ones.
+ * `flags`: the duplicate rule (rpt_knn_csr_metric_* only) or-ed with exactly one of
+ * RPT_KNN_METRIC_COSINE / _INNER.  Neither bit or both: RPT_E_ARG (the L2 distance on CSR rows is
+ * rpt_knn_* / rpt_brute_knn_*).  Dense data or a dense / CSR pair: RPT_E_ARG (dense rows under the
+ * metrics are rpt_knn_* / rpt_brute_knn_metric_*).  RPT_KNN_METRIC_REFERENCE: RPT_E_ARG.
+ * RPT_KNN_VOTE: RPT_E_UNSUPPORTED.  A dtype mismatch, or queries whose projection type is not the
+ * forest's: RPT_E_ARG.
+ * Candidates are ranked on a lane-parallel f64 dot; the entries of the best k + 8 different rows are
+ * evaluated again as the fold and the cut is certified with RPT_KNN_METRIC_*'s rounding bound (a row
+ * pair has at most d products); a query whose cut cannot be certified (ties, NaN or inf at the cut,
+ * the cosine range rule) is answered again by an exact kernel.  rpt_knn_last_candidates and
+ * rpt_knn_last_uncertified are served, rpt_knn_last_tier and rpt_knn_last_retries read 0; the option
+ * knn_metric_exact sends every query to the exact kernel.  The exhaustive search streams the rows
+ * as rpt_brute_knn_* does on CSR data: a tile of queries (option brute_csr_tile; the answer does
+ * not depend on it) against a block of rows read once, every (query, row block) certifying its own
+ * cut; a query with an uncertified block is answered again, whole, by the exact kernel.  The
+ * first call caches the rows' dotS(x, x) on the dataset, 8 bytes per row.  The _dev variants
+ * enqueue on the ctx stream as rpt_knn_dev / rpt_brute_knn_dev do. */
+int32_t rpt_knn_csr_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                                const rpt_dataset* queries, int32_t k, int32_t flags,
+                                int32_t* ids_host, double* dist_host, int32_t* count_host);
+int32_t rpt_knn_csr_metric_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                               const rpt_dataset* queries, int32_t k, int32_t flags, int32_t* ids_dev,
+                               double* dist_dev, int32_t* count_dev);
+int32_t rpt_brute_knn_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data,
+                                      const rpt_dataset* queries, int32_t k, int32_t flags,
+                                      int32_t* ids_host, double* dist_host);
+int32_t rpt_brute_knn_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data,
+                                     const rpt_dataset* queries, int32_t k, int32_t flags,
+                                     int32_t* ids_dev, double* dist_dev);
+int32_t rpt_recall_hits_csr_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                                        const rpt_dataset* queries, int32_t k, int32_t flags,
+                                        int32_t* hits_host /*[nq][T]*/,
+                                        int32_t* truth_ids_host /*[nq][k], may be NULL*/);
 
 #ifdef __cplusplus
 }

@@ -1821,3 +1821,125 @@ int32_t rpt_recall_hits_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* dat
 }
 
 }  // extern "C"
+
+// ---- cosine / inner product on CSR rows -----------------------------------------------------
+namespace {
+// the rpt_*_csr_metric_* entry points: CSR data with CSR queries, exactly one metric bit in `flags`
+// next to `allowed` (the duplicate rule of the forest query; 0 for the brute force)
+int32_t check_csr_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t k,
+                         int32_t flags, int32_t allowed, const char* l2_entry, const char* dense_entry) {
+  RPT_ARG(ctx && data && queries, "NULL argument");
+  RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
+  const int32_t metric = flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER);
+  if (!data->csr || !queries->csr) return fail(RPT_E_ARG, dense_entry);
+  RPT_ARG(!(flags & RPT_KNN_METRIC_REFERENCE),
+          "RPT_KNN_METRIC_REFERENCE is an L2 metric: not with RPT_KNN_METRIC_COSINE / _INNER");
+  if (metric != RPT_KNN_METRIC_COSINE && metric != RPT_KNN_METRIC_INNER) return fail(RPT_E_ARG, l2_entry);
+  if (allowed && ((flags >> 8) & 0xffff) != 0)
+    return fail(RPT_E_UNSUPPORTED, "RPT_KNN_METRIC_COSINE / _INNER: no voting (RPT_KNN_VOTE)");
+  RPT_ARG(flags >= 0 && (flags & ~(metric | allowed)) == 0 && (flags & 3) != 3, "unknown knn flags");
+  RPT_ARG(data->d == queries->d && data->dtype == queries->dtype, "data and query shape / dtype must match");
+  RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
+  RPT_HIP(hipSetDevice(ctx->device));
+  return RPT_OK;
+}
+const char kCsrMetricKnnL2[] =
+    "rpt_knn_csr_metric_*: exactly one of RPT_KNN_METRIC_COSINE / _INNER (L2 on CSR rows: rpt_knn_*)";
+const char kCsrMetricKnnDense[] =
+    "rpt_knn_csr_metric_*: CSR data and CSR queries (dense rows under the metrics: rpt_knn_*)";
+const char kCsrMetricBruteL2[] =
+    "rpt_brute_knn_csr_metric_*: exactly one of RPT_KNN_METRIC_COSINE / _INNER (L2 on CSR rows: rpt_brute_knn_*)";
+const char kCsrMetricBruteDense[] =
+    "rpt_brute_knn_csr_metric_*: CSR data and CSR queries (dense rows under the metrics: "
+    "rpt_brute_knn_metric_*)";
+}  // namespace
+
+extern "C" {
+
+int32_t rpt_knn_csr_metric_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                               const rpt_dataset* queries, int32_t k, int32_t flags, int32_t* ids_dev,
+                               double* dist_dev, int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_query(ctx, f, queries));
+    RPT_TRY(check_csr_metric(ctx, data, queries, k, flags, 3, kCsrMetricKnnL2, kCsrMetricKnnDense));
+    RPT_ARG(data->n == f->n && data->d == f->d, "data shape differs from the forest's");
+    RPT_ARG(proj_dtype(queries->dtype) == f->pdtype,
+            "query dtype must have the forest's projection type (f64 vs f32/bf16)");
+    RPT_ARG(ids_dev && dist_dev && count_dev, "NULL output");
+    return knn_csr_metric_dev(ctx, f, data, queries, k, flags, ids_dev, dist_dev, count_dev);
+  });
+}
+
+int32_t rpt_knn_csr_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                                const rpt_dataset* queries, int32_t k, int32_t flags, int32_t* ids_host,
+                                double* dist_host, int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_query(ctx, f, queries));
+    RPT_TRY(check_csr_metric(ctx, data, queries, k, flags, 3, kCsrMetricKnnL2, kCsrMetricKnnDense));
+    RPT_ARG(ids_host && dist_host && count_host, "NULL output");
+    const int64_t nq = queries->n;
+    DevBuf<int32_t> ids, cnt;
+    DevBuf<double> dist;
+    RPT_TRY(ids.alloc((size_t)nq * k));
+    RPT_TRY(dist.alloc((size_t)nq * k));
+    RPT_TRY(cnt.alloc((size_t)nq));
+    RPT_TRY(rpt_knn_csr_metric_dev(ctx, f, data, queries, k, flags, ids.p, dist.p, cnt.p));
+    RPT_HIP(stream_sync(ctx->stream));
+    if (nq) {
+      RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+      RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+      RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    }
+    return RPT_OK;
+  });
+}
+
+int32_t rpt_brute_knn_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                     int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_csr_metric(ctx, data, queries, k, flags, 0, kCsrMetricBruteL2, kCsrMetricBruteDense));
+    RPT_ARG(ids_dev && dist_dev, "NULL output");
+    return brute_knn_csr_metric_dev(ctx, data, queries, k, flags, ids_dev, dist_dev);
+  });
+}
+
+int32_t rpt_brute_knn_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                      int32_t k, int32_t flags, int32_t* ids_host, double* dist_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_csr_metric(ctx, data, queries, k, flags, 0, kCsrMetricBruteL2, kCsrMetricBruteDense));
+    RPT_ARG(ids_host && dist_host, "NULL output");
+    const int64_t nq = queries->n;
+    if (nq == 0) return RPT_OK;
+    DevBuf<int32_t> ids;
+    DevBuf<double> dist;
+    RPT_TRY(ids.alloc((size_t)nq * k));
+    RPT_TRY(dist.alloc((size_t)nq * k));
+    RPT_TRY(brute_knn_csr_metric_dev(ctx, data, queries, k, flags, ids.p, dist.p));
+    RPT_HIP(stream_sync(ctx->stream));
+    RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    return RPT_OK;
+  });
+}
+
+int32_t rpt_recall_hits_csr_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                                        const rpt_dataset* queries, int32_t k, int32_t flags,
+                                        int32_t* hits_host, int32_t* truth_ids_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_query(ctx, f, queries));
+    RPT_TRY(check_csr_metric(ctx, data, queries, k, flags, 0, kCsrMetricBruteL2, kCsrMetricBruteDense));
+    RPT_ARG(hits_host, "NULL output");
+    RPT_ARG(data->n == f->n && data->d == f->d, "data shape differs from the forest's");
+    RPT_ARG(proj_dtype(queries->dtype) == f->pdtype,
+            "query dtype must have the forest's projection type (f64 vs f32/bf16)");
+    RPT_ARG(queries->n * (int64_t)f->T <= 0x7fffffff, "too many (query, tree) pairs for one call");
+    return recall_hits(ctx, f, data, queries, k, flags, hits_host, truth_ids_host);
+  });
+}
+
+}  // extern "C"

@@ -412,8 +412,16 @@ int32_t brute_knn_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
 // (dense data) or RPT_KNN_METRIC_REFERENCE (CSR data)
 int32_t brute_knn_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
                       int32_t flags, int32_t* ids_dev, double* dist_dev);
+// flags as brute_knn_dev's; CSR data with RPT_KNN_METRIC_COSINE / _INNER: brute_knn_csr_metric_dev's truth
 int32_t recall_hits(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
                     int32_t k, int32_t flags, int32_t* hits_host, int32_t* truth_ids_host);
+// CSR data and CSR queries under exactly one of RPT_KNN_METRIC_COSINE / _INNER (flags of knn: or-ed
+// with the duplicate rule), the distances over the columns both rows store (rptree_hip.h); device
+// outputs; the brute force enqueues only
+int32_t knn_csr_metric_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                           int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+int32_t brute_knn_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
+                                 int32_t metric, int32_t* ids_dev, double* dist_dev);
 // the rows' dot(x, x) as the left fold into data->sqnorm ([n] doubles, then the certified cut's two
 // statistics), once per dataset, enqueued on the ctx stream (knn.hip)
 int32_t ensure_sqnorm(rpt_ctx* ctx, const rpt_dataset* data);

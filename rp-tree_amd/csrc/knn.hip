@@ -629,6 +629,12 @@ __device__ inline double leftfold_dot(const TD* __restrict__ x, const double* qs
 // already), the first k written.  tid / nthr / sync: the threads that share the arrays.
 // METRIC != L2: the rows are TX (f64 / f32 / bf16), the values metric_value of the left-fold dot,
 // rn the rows' dot(x, x) (cosine), qq the query's.
+template <class Sync>
+__device__ inline void finalize_select(int m, int k, int dedup, const double* lf, int* order, const int* bid,
+                                       const int* bpos, int tid, int nthr, Sync sync, int64_t q,
+                                       int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
+                                       int32_t* __restrict__ out_cnt, int* s_w, double* s_last);
+
 template <int METRIC = kMetricL2, class TX = double, class Sync>
 __device__ inline void finalize_leftfold(const TX* __restrict__ X, int d, const double* qs, int m,
                                          int k, int dedup, double* lf, int* order, const int* bid,
@@ -645,6 +651,15 @@ __device__ inline void finalize_leftfold(const TX* __restrict__ X, int d, const 
                                    METRIC == kMetricCosine ? rn[bid[i]] : 0.0, qq);
   }
   sync();
+  finalize_select(m, k, dedup, lf, order, bid, bpos, tid, nthr, sync, q, out_ids, out_dist, out_cnt, s_w, s_last);
+}
+
+// finalize_leftfold's selection, the values lf[0, m) given (knn_metric_csr_kernel computes its own)
+template <class Sync>
+__device__ inline void finalize_select(int m, int k, int dedup, const double* lf, int* order, const int* bid,
+                                       const int* bpos, int tid, int nthr, Sync sync, int64_t q,
+                                       int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
+                                       int32_t* __restrict__ out_cnt, int* s_w, double* s_last) {
   for (int i = tid; i < m; i += nthr) {
     const double di = lf[i];
     const int pi = bpos[i];
@@ -1470,7 +1485,8 @@ struct CsrPtrs {
 // the general path call this same function).  All loads of a step — U rows — are issued before
 // the first is used: the walk of a row is a chain of dependent loads (id -> rowptr -> col / val
 // -> qs[col]), and issuing them row by row left the kernels latency-bound (C3: 2.2 TB/s).
-template <class TD, int U>
+// DOT: the term is the product x_j q_j instead (the lane-parallel dot of knn_metric_csr_kernel).
+template <class TD, int U, bool DOT = false>
 __device__ __forceinline__ void csr_rows_dist2(const int32_t* __restrict__ col,
                                                const TD* __restrict__ val, int64_t nnz,
                                                const int64_t (&ra)[U], const int64_t (&rb)[U],
@@ -1513,9 +1529,14 @@ __device__ __forceinline__ void csr_rows_dist2(const int32_t* __restrict__ col,
       for (int e = 0; e < 4; ++e) {
         const bool ok = j + e < rb[u];
         const double qj = qs[ok ? c[u].v[e] : 0];
-        const double df = (double)v[u].v[e] - qj;
-        const double term = df * df - qj * qj;
-        s[u] += ok ? term : 0.0;
+        if constexpr (DOT) {
+          const double term = (double)v[u].v[e] * qj;
+          s[u] += ok ? term : 0.0;
+        } else {
+          const double df = (double)v[u].v[e] - qj;
+          const double term = df * df - qj * qj;
+          s[u] += ok ? term : 0.0;
+        }
       }
     }
     if (!__any(more)) break;
@@ -1527,7 +1548,7 @@ __device__ __forceinline__ void csr_rows_dist2(const int32_t* __restrict__ col,
 
 // distances of the CSR candidates [first, fill) of an LDS batch: sixteen rows of a wave in flight
 // (four row slots per 16-lane group)
-template <class TD>
+template <class TD, bool DOT = false /* cdist: the rows' lane-parallel dots with qs, qn2 unused */>
 __device__ __forceinline__ void batch_distances_csr(const int64_t* __restrict__ rowptr,
                                                     const int32_t* __restrict__ col,
                                                     const TD* __restrict__ val, int64_t nnz,
@@ -1547,12 +1568,14 @@ __device__ __forceinline__ void batch_distances_csr(const int64_t* __restrict__ 
       ra[u] = rowptr[id];
       rb[u] = ok ? rowptr[id + 1] : ra[u];
     }
-    csr_rows_dist2<TD, U>(col, val, nnz, ra, rb, qs, l16, s);
+    csr_rows_dist2<TD, U, DOT>(col, val, nnz, ra, rb, qs, l16, s);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const double t = s[u] + qn2;
       const int i = i0 + u * 4 + grp;
-      if (l16 == 0 && i < fill) cdist[i] = sqrt(t > 0 ? t : 0.0);
+      if constexpr (DOT) {
+        if (l16 == 0 && i < fill) cdist[i] = s[u];
+      } else if (l16 == 0 && i < fill) cdist[i] = sqrt(t > 0 ? t : 0.0);
     }
   }
 }
@@ -3484,6 +3507,220 @@ __global__ __launch_bounds__(256) void topk_csr_kernel(
   if (threadIdx.x == 0) out_cnt[q] = best;
 }
 
+// ---- cosine / inner product on CSR rows (rpt_knn_csr_metric_*, rpt_brute_knn_csr_metric_*) ----
+// dotS(x, q) of two CSR rows (strictly ascending columns, values widened exactly): from +0.0, over the
+// columns stored in BOTH rows in ascending order, acc = acc + x_j * q_j, every product and sum
+// rounded on its own.  inner = -dotS(x, q), cosine = 1 - dotS(x, q) / (sqrt(dotS(x, x)) sqrt(dotS(q,
+// q))).  With finite stored values these are the dense metrics' bits on the dense-ified rows: a
+// column one side lacks would add x * (+0.0) = +-0.0 to an acc that is never -0.0.  A stored inf or
+// NaN meets no 0 of the other side: the column counts only where both rows store it.
+// One thread walks the row x (nonzeros [a, b)) against the dense-ified query qs; pres holds one bit
+// per column the query stores.  Eight loads in flight; the sum is the fold whatever their grouping.
+template <class TD>
+__device__ inline double leftfold_dot_csr(const int32_t* __restrict__ col, const TD* __restrict__ val,
+                                          int64_t a, int64_t b, const double* qs, const unsigned int* pres) {
+  double acc = 0.0;
+  int64_t j = a;
+  for (; j + 8 <= b; j += 8) {
+    int c[8];
+    TD v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      c[u] = col[j + u];
+      v[u] = val[j + u];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if ((pres[c[u] >> 5] >> (c[u] & 31)) & 1u) acc = acc + (double)v[u] * qs[c[u]];
+  }
+  for (; j < b; ++j) {
+    const int c = col[j];
+    if ((pres[c >> 5] >> (c & 31)) & 1u) acc = acc + (double)val[j] * qs[c];
+  }
+  return acc;
+}
+
+// row_sqnorm_kernel for CSR rows: rn[i] = dotS(x_i, x_i), the fold of the row's stored squares, and
+// the same two statistics (a row is all zeros when every stored value equals 0)
+template <class TD>
+__global__ __launch_bounds__(256) void row_sqnorm_csr_kernel(const int64_t* __restrict__ rowptr,
+                                                             const TD* __restrict__ val, int64_t n,
+                                                             double* __restrict__ rn,
+                                                             unsigned long long* __restrict__ stats) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  unsigned long long bits = 0, bad = 0;
+  if (r < n) {
+    double v = 0.0;
+    bool nz = false;
+    for (int64_t j = rowptr[r]; j < rowptr[r + 1]; ++j) {
+      const double x = (double)val[j];
+      v = v + x * x;
+      nz = nz || x != 0.0;
+    }
+    rn[r] = v;
+    bits = (unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffULL;
+    if (!(v >= 0x1p-900 && v <= 0x1p900)) bad = nz;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long ob = __shfl_xor(bits, o), oo = __shfl_xor(bad, o);
+    bits = ob > bits ? ob : bits;
+    bad |= oo;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (bits) atomicMax(&stats[0], bits);
+    if (bad) atomicOr(&stats[1], bad);
+  }
+}
+
+// knn_metric_kernel for CSR rows and CSR queries: the same batches, merges, margin and certificate
+// (metric_cut_slack with d: a row pair has at most d products, fewer only tighten the bound), one
+// workgroup per query over the plan's leaf ranges or, identity, rows 0 .. N - 1 (the brute force).
+// The query is dense-ified into LDS (qs, and pres: a bit per stored column); qq = dotS(q, q) is
+// folded by one thread over the query's stored values.
+//   EXACT = false: the values are csr_rows_dist2's lane-parallel dot (sixteen lanes per row, four
+// rows per group in flight); it reads qs alone — with finite values the columns the query lacks add
+// exact zeros, and a stored inf / NaN makes stats or qq non-finite, which fails the certificate of
+// every query that left a candidate out.  The kept entries are evaluated again as the fold WITH the
+// presence test, so a query that left nothing out is the definition whatever the values are.
+//   EXACT = true: every value is leftfold_dot_csr, merge_best selects with no margin.
+// LDS: knn_metric_kernel's, then pres [(d + 31) / 32] words.
+template <class TD, int METRIC, bool EXACT>
+__global__ __launch_bounds__(256) void knn_metric_csr_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const TD* __restrict__ val, int64_t nnz,
+    int d, const int64_t* __restrict__ qrowptr, const int32_t* __restrict__ qcol, const TD* __restrict__ qval,
+    int64_t nq, const int32_t* __restrict__ perm, const Range* __restrict__ ranges,
+    const int64_t* __restrict__ rng_off, int T, int64_t N, int identity, int nbuf, int k, int dedup,
+    const double* __restrict__ rn, const unsigned long long* __restrict__ stats, int32_t* __restrict__ unc,
+    unsigned long long* __restrict__ unc_count, int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
+    int32_t* __restrict__ out_cnt) {
+  static_assert(METRIC == kMetricCosine || METRIC == kMetricInner, "cosine or inner product");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  Entry* buf = reinterpret_cast<Entry*>(smem);                         // [nbuf]
+  int* scratch = reinterpret_cast<int*>(smem + sizeof(Entry) * nbuf);  // [nbuf]
+  double* cd = reinterpret_cast<double*>(scratch + nbuf);              // [kMB]
+  int* cid = reinterpret_cast<int*>(cd + kMB);                         // [kMB]
+  int* cpos = cid + kMB;                                               // [kMB]
+  double* qs = reinterpret_cast<double*>(cpos + kMB);                  // [d]
+  unsigned int* pres = reinterpret_cast<unsigned int*>(qs + d);        // [(d + 31) / 32]
+  __shared__ Range s_rng[kMW];
+  __shared__ int s_fill, s_merge[2], s_w;
+  __shared__ double s_qq, s_blast, s_last;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int kk = EXACT ? k : (k + kLfMargin < nbuf / 2 ? k + kLfMargin : nbuf / 2);
+  const int sdedup = EXACT ? dedup : (dedup ? 1 : 0);  // the fast path's rule while streaming
+  const int64_t nw = EXACT && unc ? (int64_t)*unc_count : nq;  // the queries of this launch
+  for (int64_t iw = blockIdx.x; iw < nw; iw += gridDim.x) {
+    const int64_t q = EXACT && unc ? (int64_t)unc[iw] : iw;
+    __syncthreads();  // (the previous query's finalize still reads the arrays)
+    for (int j = threadIdx.x; j < d; j += blockDim.x) qs[j] = 0.0;
+    for (int j = threadIdx.x; j < (d + 31) / 32; j += blockDim.x) pres[j] = 0u;
+    if (threadIdx.x == 0) s_fill = 0;
+    __syncthreads();
+    const int64_t qa = qrowptr[q], qb = qrowptr[q + 1];
+    for (int64_t j = qa + threadIdx.x; j < qb; j += blockDim.x) {
+      const int c = qcol[j];
+      qs[c] = (double)qval[j];
+      atomicOr(&pres[c >> 5], 1u << (c & 31));
+    }
+    if (threadIdx.x == 0) {  // dotS(q, q)
+      double acc = 0.0;
+      for (int64_t j = qa; j < qb; ++j) {
+        const double v = (double)qval[j];
+        acc = acc + v * v;
+      }
+      s_qq = acc;
+    }
+    __syncthreads();
+    const double qq = METRIC == kMetricCosine ? s_qq : 0.0;
+
+    int best = 0;
+    bool cut = false;       // some candidate is not in buf (other than a same-id copy)
+    Entry thr{0.0, 0, -1};  // the last kept entry after a cut; id -1: none yet, every entry enters
+    const int64_t r0 = identity ? 0 : rng_off[q * T];
+    const int64_t r1 = identity ? 1 : rng_off[(q + 1) * T];
+    int64_t r = r0, w0 = r0, w1 = r0;  // next range; ranges [w0, w1) are in s_rng
+    int done = 0;                      // candidates of range r already taken
+    while (r < r1) {
+      int nb = 0;
+      while (nb < kMB && r < r1) {  // block-uniform
+        if (r == w1) {
+          __syncthreads();
+          w0 = r;
+          w1 = r + kMW < r1 ? r + kMW : r1;
+          for (int i = threadIdx.x; i < w1 - w0; i += blockDim.x)
+            s_rng[i] = identity ? Range{0, (int32_t)N, 0} : ranges[w0 + i];
+          __syncthreads();
+        }
+        const Range rg = s_rng[r - w0];
+        int take = rg.n - done;
+        if (take > kMB - nb) take = kMB - nb;
+        for (int i = threadIdx.x; i < take; i += blockDim.x) {
+          const int c = done + i;
+          cid[nb + i] = identity ? c : perm[rg.poff + c];
+          cpos[nb + i] = rg.pos + c;
+        }
+        nb += take;
+        done += take;
+        if (done == rg.n) {
+          ++r;
+          done = 0;
+        }
+      }
+      __syncthreads();
+      if constexpr (EXACT) {
+        for (int i = threadIdx.x; i < nb; i += blockDim.x)
+          cd[i] = leftfold_dot_csr<TD>(col, val, rowptr[cid[i]], rowptr[cid[i] + 1], qs, pres);
+      } else {
+        batch_distances_csr<TD, true>(rowptr, col, val, nnz, cid, cd, qs, 0.0, 0, nb, wave, lane);
+      }
+      __syncthreads();
+      // the order inside buf does not matter (the merges sort by value and position)
+      for (int i = threadIdx.x; i < nb; i += blockDim.x) {
+        const Entry e{metric_value<METRIC>(cd[i], METRIC == kMetricCosine ? rn[cid[i]] : 0.0, qq), cpos[i],
+                      cid[i]};
+        if (entry_less_total(e, thr)) buf[atomicAdd(&s_fill, 1)] = e;
+      }
+      __syncthreads();
+      const int filled = s_fill;
+      if (filled + kMB > nbuf || r >= r1) {
+        if constexpr (EXACT) {
+          best = merge_best<true>(buf, filled, kk, sdedup, scratch);
+          if (best == kk) thr = buf[kk - 1];
+        } else {
+          best = merge_distinct(buf, filled, kk, nbuf / 2, sdedup != 0, scratch, s_merge);
+          if (s_merge[1]) {
+            cut = true;
+            thr = buf[best - 1];
+          }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) s_fill = best;
+        __syncthreads();
+      }
+    }
+    if (threadIdx.x == 0) s_blast = best > 0 ? buf[best - 1].dist : 0.0;  // (buf's lower half stays)
+    double* lf = reinterpret_cast<double*>(scratch);     // nbuf / 2 doubles >= kk
+    int* ids2 = reinterpret_cast<int*>(buf + nbuf / 2);  // the upper half of buf is free now:
+    int* pos2 = ids2 + nbuf / 2;                         // 3 x nbuf / 2 ints fit its 8 x nbuf bytes
+    int* order = pos2 + nbuf / 2;
+    for (int i = threadIdx.x; i < best; i += blockDim.x) {
+      const int id = buf[i].id;
+      ids2[i] = id;
+      pos2[i] = buf[i].pos;
+      lf[i] = metric_value<METRIC>(leftfold_dot_csr<TD>(col, val, rowptr[id], rowptr[id + 1], qs, pres),
+                                   METRIC == kMetricCosine ? rn[id] : 0.0, qq);
+    }
+    __syncthreads();
+    finalize_select(best, k, dedup, lf, order, ids2, pos2, (int)threadIdx.x, (int)blockDim.x,
+                    [] { __syncthreads(); }, q, out_ids, out_dist, out_cnt, &s_w, &s_last);
+    if (!EXACT && threadIdx.x == 0) {  // (the thread that wrote the answer and s_w / s_last)
+      bool ok = !cut;
+      if (!ok && s_w == k) ok = s_last < s_blast - metric_cut_slack<METRIC>(d, s_qq, stats);
+      if (!ok) unc[atomicAdd(unc_count, 1ULL)] = (int32_t)q;
+    }
+  }
+}
+
 // knnH: distances of the points of the selected leaf ranges, written in result order
 // (sel[r].pos = position of the range's first point in the query's result).  One block per
 // query, one wave per point.
@@ -3992,7 +4229,13 @@ int32_t ensure_sqnorm(rpt_ctx* ctx, const rpt_dataset* data) {
   RPT_HIP(hipMemsetAsync(stats, 0, 16, ctx->stream));
   const unsigned blocks = (unsigned)((data->n + 255) / 256);
   if (blocks > 0) {
-    if (data->dtype == RPT_F64)
+    if (data->csr && data->dtype == RPT_F64)  // (CSR rows: dotS(x, x), f64 or f32 values)
+      hipLaunchKernelGGL(row_sqnorm_csr_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, data->rowptr,
+                         (const double*)data->val, data->n, rn.p, stats);
+    else if (data->csr)
+      hipLaunchKernelGGL(row_sqnorm_csr_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream, data->rowptr,
+                         (const float*)data->val, data->n, rn.p, stats);
+    else if (data->dtype == RPT_F64)
       hipLaunchKernelGGL(row_sqnorm_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream,
                          (const double*)data->X, data->n, data->d, rn.p, stats);
     else if (data->dtype == RPT_F32)
@@ -4143,6 +4386,68 @@ static int32_t knn_metric(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, 
                         count_dev));
   RPT_HIP(stream_sync(ctx->stream));  // the plan's buffers are released on return
   return RPT_OK;
+}
+
+// ---- cosine / inner product on CSR rows: knn_metric_csr_kernel's launchers (as launch_metric_*) ----
+template <class TD, int METRIC, bool EXACT>
+static int32_t launch_metric_csr_v(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
+                                   const int32_t* perm, const Range* ranges, const int64_t* rng_off, int T,
+                                   int identity, int k, int dedup, int32_t* unc, unsigned long long* unc_count,
+                                   int32_t* ids, double* dist, int32_t* cnt) {
+  const int nbuf = k + kLfMargin + kMB <= 1024 ? 1024 : kBuf;
+  const size_t smem = metric_smem(nbuf, data->d) + (size_t)((data->d + 31) / 32) * 4;
+  RPT_ARG(smem <= 150 * 1024, "d too large");
+  int64_t grid = q->n;
+  if (EXACT && grid > (int64_t)ctx->n_cu * 4) grid = (int64_t)ctx->n_cu * 4;
+  ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
+  RPT_HIP(launch_dyn(knn_metric_csr_kernel<TD, METRIC, EXACT>, dim3((unsigned)grid), dim3(256), smem, ctx->stream,
+                     data->rowptr, data->col, (const TD*)data->val, data->nnz, data->d, q->rowptr, q->col,
+                     (const TD*)q->val, q->n, perm, ranges, rng_off, T, data->n, identity, nbuf, k, dedup,
+                     (const double*)data->sqnorm,
+                     reinterpret_cast<const unsigned long long*>(data->sqnorm + data->n), unc, unc_count, ids,
+                     dist, cnt));
+  return RPT_OK;
+}
+
+template <class TD, int METRIC>
+static int32_t launch_metric_csr_t(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
+                                   const int32_t* perm, const Range* ranges, const int64_t* rng_off, int T,
+                                   int identity, int k, int dedup, int32_t* unc, int32_t* ids, double* dist,
+                                   int32_t* cnt) {
+  unsigned long long* uc = nullptr;
+  RPT_TRY(metric_unc_count(ctx, &uc));
+  if (ctx->opt.knn_metric_exact) {
+    unc = nullptr;  // every query
+    ctx->last_uncertified = q->n;
+    ctx->metric_unc_pending = false;
+  } else {
+    RPT_HIP(hipMemsetAsync(uc, 0, 8, ctx->stream));
+    RPT_TRY((launch_metric_csr_v<TD, METRIC, false>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup,
+                                                    unc, uc, ids, dist, cnt)));
+    ctx->metric_unc_pending = true;
+  }
+  return launch_metric_csr_v<TD, METRIC, true>(ctx, data, q, perm, ranges, rng_off, T, identity, k, dedup, unc, uc,
+                                               ids, dist, cnt);
+}
+
+// CSR rows and CSR queries under RPT_KNN_METRIC_COSINE / _INNER over the query plan or, identity, the
+// whole dataset (the brute force: ties by id).  unc: [q->n] ints of device scratch, as launch_metric's.
+static int32_t launch_metric_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
+                                 const int32_t* perm, const Range* ranges, const int64_t* rng_off, int T,
+                                 int identity, int k, int dedup, int metric, int32_t* unc, int32_t* ids,
+                                 double* dist, int32_t* cnt) {
+  RPT_ARG(data->n <= 0x7fffffff, "too many rows");
+  RPT_TRY(ensure_sqnorm(ctx, data));
+  const bool cosine = metric == RPT_KNN_METRIC_COSINE;
+  if (data->dtype == RPT_F64)
+    return cosine ? launch_metric_csr_t<double, kMetricCosine>(ctx, data, q, perm, ranges, rng_off, T, identity, k,
+                                                               dedup, unc, ids, dist, cnt)
+                  : launch_metric_csr_t<double, kMetricInner>(ctx, data, q, perm, ranges, rng_off, T, identity, k,
+                                                              dedup, unc, ids, dist, cnt);
+  return cosine ? launch_metric_csr_t<float, kMetricCosine>(ctx, data, q, perm, ranges, rng_off, T, identity, k,
+                                                            dedup, unc, ids, dist, cnt)
+                : launch_metric_csr_t<float, kMetricInner>(ctx, data, q, perm, ranges, rng_off, T, identity, k,
+                                                           dedup, unc, ids, dist, cnt);
 }
 
 // (u16 column, f32 value) shadow of a CSR f64 dataset, its largest squared row norm and longest row
@@ -5081,6 +5386,314 @@ static int32_t brute_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
   return knn_merge_dev(ctx, pi.p, pd.p, pc.p, 0, (int32_t)nblk, nq, k, 0, ids_dev, dist_dev, cnt_dev);
 }
 
+// ---- brute force over CSR rows under the cosine / inner-product metrics, query-tiled ------------
+// brute_csr_kernel's stream with the per-nonzero term x * q_j: a tile of QT queries (dense-ified
+// interleaved, plus one byte per column whose bit i says query i stores it) against a block of rows
+// read once.  Each (query, row block) keeps the best kk = k + kLfMargin rows by the lane-parallel
+// value (rows arrive in ascending id order and are distinct: merge_best is merge_distinct here),
+// evaluates those again as the fold dotS (leftfold_dot_csr's walk, one thread per kept row, the
+// presence test on), writes its k best by (fold value, id) — finalize_leftfold's order — and
+// certifies its own cut as knn_metric_csr_kernel does; a query with an uncertified block is flagged
+// 2 and answered again, whole, by knn_metric_csr_kernel<.., EXACT = true> in identity mode.
+// LDS: qs [d][QT] doubles, bufs [QT][cap] entries (cap >= kk + kBcRows), the finalize arrays
+// (kk x 20 bytes, one query at a time), pres [d] bytes.
+static inline size_t brute_csr_metric_smem(int d, int qt, int kk) {
+  return (size_t)d * qt * sizeof(double) + (size_t)qt * brute_csr_cap(kk) * sizeof(Entry) +
+         (((size_t)kk * 20 + 15) & ~(size_t)15) + (((size_t)d + 15) & ~(size_t)15);
+}
+
+template <class TD, int QT, int METRIC>
+__global__ __launch_bounds__(kBcThreads) void brute_csr_metric_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const TD* __restrict__ val, int64_t nnz,
+    int64_t n, int d, const int64_t* __restrict__ qrowptr, const int32_t* __restrict__ qcol,
+    const TD* __restrict__ qval, int64_t nq, int k, int kk, int cap, int64_t rows_per_block,
+    const double* __restrict__ rn, const unsigned long long* __restrict__ stats, unsigned int* __restrict__ flags,
+    int32_t* __restrict__ out_ids, double* __restrict__ out_dist, int32_t* __restrict__ out_cnt) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* qs = reinterpret_cast<double*>(smem);                                   // [d][QT]
+  Entry* bufs = reinterpret_cast<Entry*>(smem + (size_t)d * QT * sizeof(double));  // [QT][cap]
+  double* lf = reinterpret_cast<double*>(bufs + (size_t)QT * cap);                // [kk]
+  int* order = reinterpret_cast<int*>(lf + kk);                                   // [kk]
+  int* ids2 = order + kk;                                                         // [kk]
+  int* pos2 = ids2 + kk;                                                          // [kk]
+  unsigned char* pres = smem + (size_t)d * QT * sizeof(double) + (size_t)QT * cap * sizeof(Entry) +
+                        (((size_t)kk * 20 + 15) & ~(size_t)15);                   // [d]
+  __shared__ double s_qq[QT], s_last;
+  __shared__ Entry s_thr[QT];
+  __shared__ int s_fill[QT], s_have[QT], s_cut[QT], s_w;
+  const int tid = threadIdx.x;
+  const int64_t q0 = (int64_t)blockIdx.x * QT;
+  const int nqt = nq - q0 < QT ? (int)(nq - q0) : QT;
+  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+  for (int j = tid; j < d * QT; j += kBcThreads) qs[j] = 0.0;
+  for (int j = tid; j < d; j += kBcThreads) pres[j] = 0;
+  if (tid < QT) {
+    s_fill[tid] = 0;
+    s_have[tid] = 0;
+    s_cut[tid] = 0;
+    s_qq[tid] = 0.0;
+  }
+  __syncthreads();
+  // (a column's byte is shared by the tile's queries: one query at a time, a barrier between them)
+  for (int i = 0; i < nqt; ++i) {
+    for (int64_t j = qrowptr[q0 + i] + tid; j < qrowptr[q0 + i + 1]; j += kBcThreads) {
+      qs[(int64_t)qcol[j] * QT + i] = (double)qval[j];
+      pres[qcol[j]] |= (unsigned char)(1u << i);
+    }
+    __syncthreads();
+  }
+  if (tid < nqt) {  // dotS(q, q)
+    double acc = 0.0;
+    for (int64_t j = qrowptr[q0 + tid]; j < qrowptr[q0 + tid + 1]; ++j) {
+      const double v = (double)qval[j];
+      acc = acc + v * v;
+    }
+    s_qq[tid] = acc;
+  }
+  __syncthreads();
+  // rows arrive in ascending id order: an entry enters only if it beats the kk-th best so far in
+  // the total order (an equal value, or a NaN behind a NaN, loses to the smaller id)
+  auto push = [&](int i, double dist, int row) {
+    const Entry e{dist, row, row};
+    if (!s_have[i] || entry_less_total(e, s_thr[i])) bufs[i * cap + atomicAdd(&s_fill[i], 1)] = e;
+    else s_cut[i] = 1;
+  };
+  // sorts query i's buffer, keeps the best kk in front; every thread calls
+  auto settle = [&](int i) {
+    Entry* buf = bufs + i * cap;
+    const int filled = s_fill[i];
+    const int best = merge_best<true>(buf, filled, kk, 0, nullptr);
+    __syncthreads();
+    if (tid == 0) {
+      s_fill[i] = best;
+      if (filled > best) s_cut[i] = 1;
+      if (best == kk) {
+        s_have[i] = 1;
+        s_thr[i] = buf[kk - 1];
+      }
+    }
+    __syncthreads();
+    return best;
+  };
+  for (int64_t b0 = r0; b0 < r1; b0 += kBcRows) {
+    struct __attribute__((packed, aligned(4))) C4 { int v[4]; };
+    struct __attribute__((packed, aligned(4))) V4 { TD v[4]; };
+    const int grp = tid >> 4, l16 = tid & 15;
+    int64_t ra[kBcU], rb[kBcU];
+    double s[kBcU][QT];
+#pragma unroll
+    for (int u = 0; u < kBcU; ++u) {
+      const int64_t row = b0 + u * kBcGroups + grp;
+      const bool ok = row < r1;
+      ra[u] = rowptr[ok ? row : r0];
+      rb[u] = ok ? rowptr[row + 1] : ra[u];
+#pragma unroll
+      for (int i = 0; i < QT; ++i) s[u][i] = 0.0;
+    }
+    for (int64_t t = 4 * l16;; t += 64) {
+      C4 c[kBcU];
+      V4 v[kBcU];
+      bool more = false;
+#pragma unroll
+      for (int u = 0; u < kBcU; ++u) {
+        const int64_t j = ra[u] + t;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          c[u].v[e] = 0;
+          v[u].v[e] = (TD)0;
+        }
+        if (j < rb[u]) {
+          if (j + 4 <= nnz) {  // may run past the row's end (masked below), never past the arrays'
+            c[u] = *reinterpret_cast<const C4*>(col + j);
+            v[u] = *reinterpret_cast<const V4*>(val + j);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (j + e < rb[u]) {
+                c[u].v[e] = col[j + e];
+                v[u].v[e] = val[j + e];
+              }
+          }
+        }
+        more = more || j + 64 < rb[u];
+      }
+#pragma unroll
+      for (int u = 0; u < kBcU; ++u) {
+        const int64_t j = ra[u] + t;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool ok = j + e < rb[u];
+          const double* qp = qs + (int64_t)(ok ? c[u].v[e] : 0) * QT;
+          const double x = (double)v[u].v[e];
+#pragma unroll
+          for (int i = 0; i < QT; ++i) {
+            const double term = x * qp[i];
+            s[u][i] += ok ? term : 0.0;
+          }
+        }
+      }
+      if (!__any(more)) break;
+    }
+#pragma unroll
+    for (int u = 0; u < kBcU; ++u) {
+      const int64_t row = b0 + u * kBcGroups + grp;
+#pragma unroll
+      for (int i = 0; i < QT; ++i) {
+        double a = s[u][i];
+        for (int o = 8; o > 0; o >>= 1) a += __shfl_xor(a, o);  // csr_rows_dist2's butterfly
+        if (l16 == 0 && row < r1 && i < nqt)
+          push(i, metric_value<METRIC>(a, METRIC == kMetricCosine ? rn[row] : 0.0, s_qq[i]), (int)row);
+      }
+    }
+    __syncthreads();
+    // a batch appends at most kBcRows entries to a buffer: sort the ones the next might overflow
+    unsigned need = 0;
+    for (int i = 0; i < nqt; ++i) need |= (s_fill[i] > cap - kBcRows ? 1u : 0u) << i;
+    __syncthreads();
+    for (int i = 0; i < nqt; ++i)
+      if (need >> i & 1) settle(i);
+  }
+  for (int i = 0; i < nqt; ++i) {
+    const int best = settle(i);
+    const Entry* buf = bufs + i * cap;
+    const int64_t o = (int64_t)blockIdx.y * nq + q0 + i;
+    const double qq = METRIC == kMetricCosine ? s_qq[i] : 0.0;
+    for (int r = tid; r < best; r += kBcThreads) {  // the kept rows again as the fold
+      const int id = buf[r].id;
+      ids2[r] = id;
+      pos2[r] = id;
+      double acc = 0.0;
+      for (int64_t j = rowptr[id]; j < rowptr[id + 1]; ++j) {
+        const int c = col[j];
+        if ((pres[c] >> i) & 1) acc = acc + (double)val[j] * qs[(int64_t)c * QT + i];
+      }
+      lf[r] = metric_value<METRIC>(acc, METRIC == kMetricCosine ? rn[id] : 0.0, qq);
+    }
+    __syncthreads();
+    finalize_select(best, k, 0, lf, order, ids2, pos2, tid, kBcThreads, [] { __syncthreads(); }, o, out_ids,
+                    out_dist, out_cnt, &s_w, &s_last);
+    if (tid == 0) {  // (the thread that wrote the answer and s_w / s_last)
+      bool ok = !s_cut[i];
+      if (!ok && s_w == k && best > 0)
+        ok = s_last < buf[best - 1].dist - metric_cut_slack<METRIC>(d, s_qq[i], stats);
+      if (!ok) flags[q0 + i] = 2u;
+    }
+    __syncthreads();
+  }
+}
+
+template <class TD, int QT, int METRIC>
+static int32_t launch_brute_csr_metric_t(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k,
+                                         int64_t rows_per_block, int nblk, unsigned int* flags, int32_t* ids,
+                                         double* dist, int32_t* cnt) {
+  const int kk = k + kLfMargin;
+  const int64_t tiles = (q->n + QT - 1) / QT;
+  RPT_HIP(launch_dyn(brute_csr_metric_kernel<TD, QT, METRIC>, dim3((unsigned)tiles, (unsigned)nblk),
+                     dim3(kBcThreads), brute_csr_metric_smem(data->d, QT, kk), ctx->stream, data->rowptr, data->col,
+                     (const TD*)data->val, data->nnz, data->n, data->d, q->rowptr, q->col, (const TD*)q->val, q->n,
+                     k, kk, brute_csr_cap(kk), rows_per_block, (const double*)data->sqnorm,
+                     reinterpret_cast<const unsigned long long*>(data->sqnorm + data->n), flags, ids, dist, cnt));
+  return RPT_OK;
+}
+
+template <class TD, int METRIC>
+static int32_t launch_brute_csr_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k, int qt,
+                                       int64_t rows, int nblk, unsigned int* flags, int32_t* ids, double* dist,
+                                       int32_t* cnt) {
+  switch (qt) {
+    case 8: return launch_brute_csr_metric_t<TD, 8, METRIC>(ctx, data, q, k, rows, nblk, flags, ids, dist, cnt);
+    case 4: return launch_brute_csr_metric_t<TD, 4, METRIC>(ctx, data, q, k, rows, nblk, flags, ids, dist, cnt);
+    case 2: return launch_brute_csr_metric_t<TD, 2, METRIC>(ctx, data, q, k, rows, nblk, flags, ids, dist, cnt);
+    default: return launch_brute_csr_metric_t<TD, 1, METRIC>(ctx, data, q, k, rows, nblk, flags, ids, dist, cnt);
+  }
+}
+
+// exhaustive kNN of CSR queries over CSR rows under RPT_KNN_METRIC_COSINE / _INNER into device arrays
+// [nq][k]: the tiled stream (brute_csr's tile and row blocks, merged by knn_merge_dev), then the
+// exact kernel over the flagged queries — or alone over all of them with knn_metric_exact.
+// cnt: [nq] ints of device scratch.  Enqueues only; ctx->last_uncertified follows lazily.
+static int32_t brute_csr_metric(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k, int metric,
+                                int32_t* ids_dev, double* dist_dev, int32_t* cnt_dev) {
+  RPT_ARG(data->n <= 0x7fffffff, "too many rows");
+  RPT_TRY(ensure_sqnorm(ctx, data));
+  const int64_t nq = q->n, n = data->n;
+  const bool cosine = metric == RPT_KNN_METRIC_COSINE;
+  unsigned long long* uc = nullptr;
+  RPT_TRY(metric_unc_count(ctx, &uc));
+  DevBuf<int32_t> unc;
+  RPT_TRY(unc.alloc((size_t)nq));
+  auto exact = [&](int32_t* list) -> int32_t {
+    if (data->dtype == RPT_F64)
+      return cosine ? launch_metric_csr_v<double, kMetricCosine, true>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1,
+                                                                       k, 0, list, uc, ids_dev, dist_dev, cnt_dev)
+                    : launch_metric_csr_v<double, kMetricInner, true>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1,
+                                                                      k, 0, list, uc, ids_dev, dist_dev, cnt_dev);
+    return cosine ? launch_metric_csr_v<float, kMetricCosine, true>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k,
+                                                                    0, list, uc, ids_dev, dist_dev, cnt_dev)
+                  : launch_metric_csr_v<float, kMetricInner, true>(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k,
+                                                                   0, list, uc, ids_dev, dist_dev, cnt_dev);
+  };
+  if (ctx->opt.knn_metric_exact) {
+    ctx->last_uncertified = nq;
+    ctx->metric_unc_pending = false;
+    return exact(nullptr);
+  }
+  const int kk = k + kLfMargin;
+  int qt = brute_csr_tile(ctx, data->d, kk, nq);
+  while (qt > 1 && brute_csr_metric_smem(data->d, qt, kk) > kBcLds) qt >>= 1;
+  // (a d near the `d too large` limit with k near 1024: one query does not fit next to the finalize
+  // arrays — the forest kernel pair in identity mode, one workgroup per query, has the same answer)
+  if (brute_csr_metric_smem(data->d, qt, kk) > kBcLds)
+    return launch_metric_csr(ctx, data, q, nullptr, nullptr, nullptr, 1, 1, k, 0, metric, unc.p, ids_dev, dist_dev,
+                             cnt_dev);
+  // the row blocks of brute_csr
+  const int64_t tiles = (nq + qt - 1) / qt;
+  int64_t nblk = (2 * (int64_t)ctx->n_cu + tiles - 1) / tiles;
+  nblk = std::min(nblk, std::min<int64_t>(kMergeMax / k, n / 4096));
+  nblk = std::max<int64_t>(nblk, 1);
+  int64_t rows = (n + nblk - 1) / nblk;
+  rows = std::max<int64_t>((rows + kBcRows - 1) / kBcRows * kBcRows, kBcRows);
+  nblk = std::max<int64_t>((n + rows - 1) / rows, 1);
+  DevBuf<unsigned int> flags;
+  RPT_TRY(flags.alloc((size_t)nq));
+  RPT_HIP(hipMemsetAsync(flags.p, 0, (size_t)nq * 4, ctx->stream));
+  RPT_HIP(hipMemsetAsync(uc, 0, 8, ctx->stream));
+  DevBuf<int32_t> pi, pc;
+  DevBuf<double> pd;
+  int32_t* oi = ids_dev;
+  double* od = dist_dev;
+  int32_t* oc = cnt_dev;
+  if (nblk > 1) {
+    RPT_TRY(pi.alloc((size_t)nblk * nq * k));
+    RPT_TRY(pd.alloc((size_t)nblk * nq * k));
+    RPT_TRY(pc.alloc((size_t)nblk * nq));
+    oi = pi.p;
+    od = pd.p;
+    oc = pc.p;
+  }
+  {
+    ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
+    if (data->dtype == RPT_F64)
+      RPT_TRY(cosine ? (launch_brute_csr_metric<double, kMetricCosine>(ctx, data, q, k, qt, rows, (int)nblk, flags.p,
+                                                                       oi, od, oc))
+                     : (launch_brute_csr_metric<double, kMetricInner>(ctx, data, q, k, qt, rows, (int)nblk, flags.p,
+                                                                      oi, od, oc)));
+    else
+      RPT_TRY(cosine ? (launch_brute_csr_metric<float, kMetricCosine>(ctx, data, q, k, qt, rows, (int)nblk, flags.p,
+                                                                      oi, od, oc))
+                     : (launch_brute_csr_metric<float, kMetricInner>(ctx, data, q, k, qt, rows, (int)nblk, flags.p, oi,
+                                                                     od, oc)));
+  }
+  if (nblk > 1)
+    RPT_TRY(knn_merge_dev(ctx, pi.p, pd.p, pc.p, 0, (int32_t)nblk, nq, k, 0, ids_dev, dist_dev, cnt_dev));
+  hipLaunchKernelGGL(collect_flagged_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, flags.p,
+                     nq, unc.p, uc);
+  RPT_HIP(hipGetLastError());
+  ctx->metric_unc_pending = true;
+  return exact(unc.p);
+}
+
 // ---- recallWith on the device: |candidates(tree t, query i) ∩ truth_i| --------------------------
 // One workgroup per (query, tree): the k truth ids are sorted in LDS, every candidate id of the
 // tree's leaf ranges is looked up by bisection and MARKS the truth slot it equals; the marked slots
@@ -5201,6 +5814,44 @@ int32_t brute_knn(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, i
 
 // recallWith (RPTree.hs:276-282) for a query batch, the division left to the caller:
 // hits[i][t] = |candidates(tree t, query i) ∩ truth_i|, truth_i = the brute force under `flags`
+// ---- cosine / inner product on CSR rows (rpt_knn_csr_metric_*, rpt_brute_knn_csr_metric_*) ----
+// arguments checked by the caller: CSR data and queries of one dtype, exactly one metric bit
+int32_t knn_csr_metric_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                           int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  RPT_ARG(k <= kBuf / 2, "k too large for the LDS merge buffer");
+  RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
+  ctx->last_uncertified = 0;
+  ctx->metric_unc_pending = false;
+  ctx->last_retries = 0;
+  ctx->last_tier = 0;
+  QueryPlan pl;
+  RPT_TRY(make_plan(ctx, f, q, pl));
+  ctx->last_candidates = pl.total_cand;
+  if (q->n == 0) return RPT_OK;
+  DevBuf<int32_t> unc;
+  RPT_TRY(unc.alloc((size_t)q->n));
+  RPT_TRY(launch_metric_csr(ctx, data, q, f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, 0, k, flags & 3,
+                            flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER), unc.p, ids_dev, dist_dev,
+                            count_dev));
+  RPT_HIP(stream_sync(ctx->stream));  // the plan's buffers are released on return
+  return RPT_OK;
+}
+
+// exhaustive: brute_csr_metric_kernel's tiled stream, the exact kernel over the flagged queries.
+// Enqueues only.
+int32_t brute_knn_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
+                                 int32_t metric, int32_t* ids_dev, double* dist_dev) {
+  RPT_ARG(k <= kBuf / 2, "k too large");
+  RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
+  ctx->last_uncertified = 0;
+  ctx->metric_unc_pending = false;
+  const int64_t nq = q->n;
+  if (nq == 0) return RPT_OK;
+  DevBuf<int32_t> cnt;
+  RPT_TRY(cnt.alloc((size_t)nq));
+  return brute_csr_metric(ctx, data, q, k, metric, ids_dev, dist_dev, cnt.p);
+}
+
 int32_t recall_hits(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
                     int32_t k, int32_t flags, int32_t* hits_host, int32_t* truth_ids_host) {
   const int64_t nq = q->n;
@@ -5210,7 +5861,10 @@ int32_t recall_hits(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const 
   RPT_TRY(ids.alloc((size_t)nq * k));
   RPT_TRY(dist.alloc((size_t)nq * k));
   RPT_TRY(hits.alloc((size_t)nq * f->T));
-  RPT_TRY(brute_knn_dev(ctx, data, q, k, flags, ids.p, dist.p));
+  if (data->csr && (flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)))  // (rpt_recall_hits_csr_metric_host)
+    RPT_TRY(brute_knn_csr_metric_dev(ctx, data, q, k, flags, ids.p, dist.p));
+  else
+    RPT_TRY(brute_knn_dev(ctx, data, q, k, flags, ids.p, dist.p));
   QueryPlan pl;
   RPT_TRY(make_plan(ctx, f, q, pl));
   hipLaunchKernelGGL(recall_hits_kernel, dim3((unsigned)(nq * f->T)), dim3(256), 0, ctx->stream,

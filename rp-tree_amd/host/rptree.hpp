@@ -127,6 +127,7 @@ class Dataset {
  public:
   int64_t n = 0;
   int d = 0;
+  bool csr = false;  // SVector rows
   Dataset(Context& ctx, const std::vector<DVector>& xs) {
     n = (int64_t)xs.size();
     d = n ? (int)xs[0].dvVec.size() : 1;
@@ -139,6 +140,7 @@ class Dataset {
   Dataset(Context& ctx, const std::vector<SVector>& xs, int dim) {
     n = (int64_t)xs.size();
     d = dim;
+    csr = true;
     std::vector<int64_t> rowptr{0};
     std::vector<int32_t> col;
     std::vector<double> val;
@@ -243,7 +245,10 @@ inline RPForest forest(Context& ctx, uint64_t seed, int maxd, int minl, int ntre
 
 // The distance `knn` ranks by (the reference's distf argument): metricL2, or the cosine / negated
 // inner-product distances of RPT_KNN_METRIC_COSINE / RPT_KNN_METRIC_INNER (include/rptree_hip.h:
-// every value in double, the dots a left fold; dense data only)
+// every value in double, the dots a left fold).  On SVector data Cosine / Inner go to the
+// rpt_*_csr_metric_* entry points: the fold runs over the indices both vectors store, in ascending
+// order — the dense value of the dense-ified vectors when the stored values are finite, and a
+// stored inf / NaN counts only where both store the index.
 enum class Metric { L2, Cosine, Inner };
 
 inline int32_t metric_flags(Metric m) {
@@ -278,6 +283,30 @@ inline std::vector<std::pair<double, int32_t>> knnPQ(const RPForest& tts, int k,
   std::vector<std::pair<double, int32_t>> out;
   for (int i = 0; i < cnt; ++i) out.push_back({dist[(size_t)i], ids[(size_t)i]});
   return out;
+}
+
+// ... and for an SVector forest; Metric::Cosine / Inner: rpt_knn_csr_metric_host
+inline std::vector<std::pair<double, int32_t>> knnSV(const RPForest& tts, int k, const SVector& q, Metric metric,
+                                                     int32_t dedup) {
+  std::vector<SVector> qv{q};
+  Dataset qs(*tts.ctx, qv, tts.data->d);
+  std::vector<int32_t> ids((size_t)k);
+  std::vector<double> dist((size_t)k);
+  int32_t cnt = 0;
+  check((metric == Metric::L2 ? rpt_knn_host : rpt_knn_csr_metric_host)(
+      tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), k, dedup | metric_flags(metric), ids.data(), dist.data(),
+      &cnt));
+  std::vector<std::pair<double, int32_t>> out;
+  for (int i = 0; i < cnt; ++i) out.push_back({dist[(size_t)i], ids[(size_t)i]});
+  return out;
+}
+inline std::vector<std::pair<double, int32_t>> knn(const RPForest& tts, int k, const SVector& q,
+                                                   Metric metric = Metric::L2) {
+  return knnSV(tts, k, q, metric, RPT_KNN_KEEP_DUPLICATES);
+}
+inline std::vector<std::pair<double, int32_t>> knnPQ(const RPForest& tts, int k, const SVector& q,
+                                                     Metric metric = Metric::L2) {
+  return knnSV(tts, k, q, metric, RPT_KNN_DEDUP_DISTANCE);
 }
 
 // knnH metricL2 k forest q  (RPTree.hs:199-217): whole buckets of the leaves with the smallest
@@ -646,6 +675,17 @@ inline BruteResult bruteKnn(Context& ctx, const Dataset& data, const Dataset& qs
   r.dist.resize((size_t)qs.n * k);
   return r;
 }
+// ... under a Metric, dense or SVector data (SVector rows under Cosine / Inner:
+// rpt_brute_knn_csr_metric_host, the distance over the indices both vectors store)
+inline BruteResult bruteKnn(Context& ctx, const Dataset& data, const Dataset& qs, int k, Metric metric) {
+  if (!data.csr || metric == Metric::L2) return bruteKnn(ctx, data, qs, k, metric_flags(metric));
+  BruteResult r{std::vector<int32_t>((size_t)qs.n * k + 1), std::vector<double>((size_t)qs.n * k + 1)};
+  check(rpt_brute_knn_csr_metric_host(ctx.get(), data.get(), qs.get(), k, metric_flags(metric), r.ids.data(),
+                                      r.dist.data()));
+  r.ids.resize((size_t)qs.n * k);
+  r.dist.resize((size_t)qs.n * k);
+  return r;
+}
 // hits[i][t] = |candidates(tree t, query i) n true kNN of query i|, truth (optional) [nq][k]
 inline std::vector<int32_t> recallHits(const RPForest& tts, int k, const Dataset& qs, int32_t flags = 0,
                                        std::vector<int32_t>* truth = nullptr) {
@@ -667,6 +707,34 @@ inline std::vector<double> recallWithBatch(const RPForest& tts, int k, const Dat
     out[(size_t)i] = acc / (double)tts.T;
   }
   return out;
+}
+// ... under a Metric, dense or SVector forests (SVector rows under Cosine / Inner:
+// rpt_recall_hits_csr_metric_host)
+inline std::vector<int32_t> recallHits(const RPForest& tts, int k, const Dataset& qs, Metric metric,
+                                       std::vector<int32_t>* truth = nullptr) {
+  if (!tts.data->csr || metric == Metric::L2) return recallHits(tts, k, qs, metric_flags(metric), truth);
+  std::vector<int32_t> hits((size_t)qs.n * tts.T + 1);
+  if (truth) truth->assign((size_t)qs.n * k + 1, -1);
+  check(rpt_recall_hits_csr_metric_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), k,
+                                        metric_flags(metric), hits.data(), truth ? truth->data() : nullptr));
+  hits.resize((size_t)qs.n * tts.T);
+  if (truth) truth->resize((size_t)qs.n * k);
+  return hits;
+}
+inline std::vector<double> recallWithBatch(const RPForest& tts, int k, const Dataset& qs, Metric metric) {
+  const std::vector<int32_t> hits = recallHits(tts, k, qs, metric);
+  std::vector<double> out((size_t)qs.n);
+  for (int64_t i = 0; i < qs.n; ++i) {
+    double acc = 0.0;
+    for (int t = 0; t < tts.T; ++t) acc += (double)hits[(size_t)i * tts.T + t] / (double)k;
+    out[(size_t)i] = acc / (double)tts.T;
+  }
+  return out;
+}
+inline double recallWith(const RPForest& tts, int k, const SVector& q, Metric metric) {
+  std::vector<SVector> qv{q};
+  Dataset qs(*tts.ctx, qv, tts.data->d);
+  return recallWithBatch(tts, k, qs, metric)[0];
 }
 inline double recallWith(const RPForest& tts, int k, const DVector& q, Metric metric = Metric::L2) {
   std::vector<DVector> qv{q};

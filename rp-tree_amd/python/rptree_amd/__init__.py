@@ -707,19 +707,54 @@ def _dot_fold(a, b):
     return acc
 
 
+def _dot_sv(u, v):
+    """dotS of two SVectors (strictly ascending indices): from +0.0, over the indices stored in BOTH,
+    in ascending order, acc = acc + u_j * v_j, each product and sum rounded.  The products inner()
+    adds from the right (the reference's innerSS order), added from the left: the order that makes
+    SVector and dense-ified rows agree bit for bit when the stored values are finite."""
+    acc, a, b = 0.0, 0, 0
+    ui, vi = np.asarray(u.svIdx).tolist(), np.asarray(v.svIdx).tolist()
+    ux = np.asarray(u.svVal).astype(np.float64).tolist()
+    vx = np.asarray(v.svVal).astype(np.float64).tolist()
+    while a < len(ui) and b < len(vi):
+        if ui[a] == vi[b]:
+            acc = acc + ux[a] * vx[b]
+            a += 1
+            b += 1
+        elif ui[a] < vi[b]:
+            a += 1
+        else:
+            b += 1
+    return acc
+
+
+def _metric_dots(u, v):
+    # (u.v, u.u, v.v): dotS for two SVectors, the dense left fold otherwise
+    if isinstance(u, SVector) or isinstance(v, SVector):
+        if not (isinstance(u, SVector) and isinstance(v, SVector)):
+            raise TypeError("metricInner / metricCosine: two SVectors or two dense vectors")
+        return _dot_sv(u, v), _dot_sv(u, u), _dot_sv(v, v)
+    a, b = _dense_f64(u), _dense_f64(v)
+    return _dot_fold(a, b), _dot_fold(a, a), _dot_fold(b, b)
+
+
 def metricInner(u, v):
     """-(inner u v): the inner-product distance of the device's RPT_KNN_METRIC_INNER (maximum
-    inner-product search; smaller is nearer), the dot a left fold in Double from +0.0."""
-    return -_dot_fold(_dense_f64(u), _dense_f64(v))
+    inner-product search; smaller is nearer), the dot a left fold in Double from +0.0.
+    Two SVectors: the fold runs over the indices stored in both, in ascending order (what
+    rpt_knn_csr_metric_* evaluates): the dense value of the dense-ified vectors when the stored
+    values are finite; a stored inf / NaN counts only where both vectors store the index."""
+    return -_metric_dots(u, v)[0]
 
 
 def metricCosine(u, v):
     """1 - inner u v / (sqrt (inner u u) * sqrt (inner v v)): the cosine distance of the device's
-    RPT_KNN_METRIC_COSINE, every dot a left fold in Double; NaN when u or v is zero."""
-    a, b = _dense_f64(u), _dense_f64(v)
-    den = np.float64(math.sqrt(_dot_fold(a, a))) * np.float64(math.sqrt(_dot_fold(b, b)))
+    RPT_KNN_METRIC_COSINE, every dot a left fold in Double; NaN when u or v is zero.
+    Two SVectors: every dot as metricInner's (NaN for an empty or all-zero vector)."""
+    uv, uu, vv = _metric_dots(u, v)
+    den = np.float64(math.sqrt(uu)) * np.float64(math.sqrt(vv))
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        return float(1.0 - np.float64(_dot_fold(a, b)) / den)
+        return float(1.0 - np.float64(uv) / den)
 
 
 _METRIC_FLAGS = {metricL2: 0, metricCosine: RPT_KNN_METRIC_COSINE, metricInner: RPT_KNN_METRIC_INNER}
@@ -769,8 +804,10 @@ def knnBatch(k, forest, qs, dedup=False, vote=0, reference_metric=False, metric=
     reference_metric: SVector data are ranked by the reference's own metricSSL2 (Internal.hs:
     389-393: the merge of the index lists stops at the shorter vector's end) instead of the true
     Euclidean distance.
-    metric: None / metricL2, metricCosine or metricInner (dense data; RPT_KNN_METRIC_COSINE /
-    _INNER: every value in f64, bit-exact to those host functions)."""
+    metric: None / metricL2, metricCosine or metricInner (RPT_KNN_METRIC_COSINE / _INNER: every
+    value in f64, bit-exact to those host functions).  On SVector data the two are evaluated over
+    the indices both vectors store (rpt_knn_csr_metric_host; see metricInner): the answer of the
+    dense-ified data when the stored values are finite; not with reference_metric (ValueError)."""
     ctx = forest.ctx
     qd, nq = _query_dataset(ctx, forest.data, qs)
     ids = np.empty((nq, k), dtype=np.int32)
@@ -781,9 +818,14 @@ def knnBatch(k, forest, qs, dedup=False, vote=0, reference_metric=False, metric=
     flags |= int(vote) << 8                       # RPT_KNN_VOTE(v)
     if reference_metric:                          # SVector data: the truncating metricSSL2
         flags |= RPT_KNN_METRIC_REFERENCE
-    flags |= _metric_flag(metric)
-    check(lib().rpt_knn_host(ctx._h, forest._h, forest.data._h, qd._h, int(k), flags, _vp(ids),
-                             _vp(dist), _vp(cnt)))
+    mflag = _metric_flag(metric)
+    if mflag and reference_metric and forest.data.is_csr:
+        raise ValueError("reference_metric is an L2 metric: not with metricCosine / metricInner")
+    flags |= mflag
+    # SVector data under metricCosine / metricInner: the entry point of their own (the distance over
+    # the indices both vectors store, see metricInner); vote stays an error there
+    entry = lib().rpt_knn_csr_metric_host if mflag and forest.data.is_csr else lib().rpt_knn_host
+    check(entry(ctx._h, forest._h, forest.data._h, qd._h, int(k), flags, _vp(ids), _vp(dist), _vp(cnt)))
     return ids, dist, cnt
 
 
@@ -1261,16 +1303,20 @@ def _brute_flags(data, metric, reference_metric):
 
 def bruteKnn(forest_or_data, qs, k, ctx=None, metric=None, reference_metric=False):
     """exhaustive kNN on the device, the k best by (distance, id); metric: None / metricL2,
-    metricCosine or metricInner (the last two: dense data).  SVector (CSR) data: the true Euclidean
-    distance, or with reference_metric the reference's truncating metricSSL2 (Internal.hs:389-393),
-    bit-exact."""
+    metricCosine or metricInner.  SVector (CSR) data: the true Euclidean distance, or with
+    reference_metric the reference's truncating metricSSL2 (Internal.hs:389-393), bit-exact; under
+    metricCosine / metricInner the distance over the indices both vectors store
+    (rpt_brute_knn_csr_metric_host; see metricInner), NaN behind every number."""
     data = forest_or_data.data if isinstance(forest_or_data, RPForest) else forest_or_data
     ctx = ctx or data.ctx
     qd, nq = _query_dataset(ctx, data, qs)
     ids = np.empty((nq, k), dtype=np.int32)
     dist = np.empty((nq, k), dtype=np.float64)
     flags = _brute_flags(data, metric, reference_metric)
-    if flags:
+    if data.is_csr and flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER):
+        check(lib().rpt_brute_knn_csr_metric_host(ctx._h, data._h, qd._h, int(k), flags, _vp(ids),
+                                                  _vp(dist)))
+    elif flags:
         check(lib().rpt_brute_knn_metric_host(ctx._h, data._h, qd._h, int(k), flags, _vp(ids),
                                               _vp(dist)))
     else:
@@ -1280,14 +1326,17 @@ def bruteKnn(forest_or_data, qs, k, ctx=None, metric=None, reference_metric=Fals
 
 def recallHits(distf, forest, k, qs, reference_metric=False):
     """-> (hits[nq][T], truth[nq][k]): hits[i][t] = |candidates(tree t, query i) ∩ true kNN of
-    query i|, the truth by brute force under distf, both on the device (rpt_recall_hits_host)."""
+    query i|, the truth by brute force under distf, both on the device (rpt_recall_hits_host;
+    SVector data under metricCosine / metricInner: rpt_recall_hits_csr_metric_host, the truth
+    bruteKnn's under that distf)."""
     ctx = forest.ctx
     qd, nq = _query_dataset(ctx, forest.data, qs)
     hits = np.empty((nq, forest.T), dtype=np.int32)
     truth = np.empty((nq, k), dtype=np.int32)
     flags = _brute_flags(forest.data, distf, reference_metric)
-    check(lib().rpt_recall_hits_host(ctx._h, forest._h, forest.data._h, qd._h, int(k), flags,
-                                     _vp(hits), _vp(truth)))
+    csr_metric = forest.data.is_csr and flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER)
+    entry = lib().rpt_recall_hits_csr_metric_host if csr_metric else lib().rpt_recall_hits_host
+    check(entry(ctx._h, forest._h, forest.data._h, qd._h, int(k), flags, _vp(hits), _vp(truth)))
     return hits, truth
 
 

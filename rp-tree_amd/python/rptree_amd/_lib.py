@@ -117,6 +117,11 @@ SYMBOLS = {
     "rpt_brute_knn_metric_host": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "rpt_brute_knn_dev": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "rpt_recall_hits_host": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
+    "rpt_knn_csr_metric_host": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "rpt_knn_csr_metric_dev": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "rpt_brute_knn_csr_metric_host": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+    "rpt_brute_knn_csr_metric_dev": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+    "rpt_recall_hits_csr_metric_host": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
 }
 
 
