@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -55,6 +55,8 @@ foreign import ccall safe "rpt_knn_graph_metric_host" c_knn_graph_metric_host ::
 foreign import ccall safe "rpt_knn_graph_refine_metric_host" c_knn_graph_refine_metric_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_csr_host" c_knn_graph_csr_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_refine_csr_host" c_knn_graph_refine_csr_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_graph_csr_metric_host" c_knn_graph_csr_metric_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_graph_refine_csr_metric_host" c_knn_graph_refine_csr_metric_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_host" c_graph_search_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_csr_host" c_graph_search_csr_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_host" c_graph_prepare_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
@@ -323,6 +325,34 @@ knnGraphRefineMetricHIP ctx ds m _n k reverse iters (i0, d0, c0) = do
   dist <- VS.thaw d0
   cnt <- VS.thaw c0
   VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_refine_metric_host ctx ds (fromIntegral k) (fromIntegral reverse) (fromIntegral iters) (metricFlag m) 0 a b))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | 'knnGraphSVHIP' under another distance (rpt_knn_graph_csr_metric_host): 'MetricCosine' /
+-- 'MetricInner' over the indices both rows store, the distances of 'knnMetricSVHIP' (the left fold
+-- of the shared indices' products from +0.0, in Double).  While every stored value is finite that
+-- is 'knnGraphMetricHIP' on the dense-ified rows bit for bit; with a stored infinity or NaN it is
+-- not (the dense fold meets inf * 0), and the answer is this definition.  'MetricL2' gives
+-- 'knnGraphSVHIP''s bits.  @Just earlier@ must be an answer under the same metric.
+knnGraphMetricSVHIP :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Metric -> Int -> Int
+                    -> Maybe (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+                    -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnGraphMetricSVHIP ctx f ds m n k earlier = do
+  (ids, dist, cnt, flags) <- case earlier of
+    Nothing -> (,,,) <$> VSM.new (n * k) <*> VSM.new (n * k) <*> VSM.new n <*> pure 0
+    Just (i0, d0, c0) -> (,,,) <$> VS.thaw i0 <*> VS.thaw d0 <*> VS.thaw c0 <*> pure 1
+  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_csr_metric_host ctx f ds (fromIntegral k) (metricFlag m) flags a b))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | 'knnGraphRefineSVHIP' under another distance (rpt_knn_graph_refine_csr_metric_host); the graph's
+-- stored distances must be that metric's ('knnGraphMetricSVHIP' under the same 'Metric').
+knnGraphRefineMetricSVHIP :: Ptr Ctx -> Ptr Dataset -> Metric -> Int -> Int -> Int -> Int
+                          -> (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+                          -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnGraphRefineMetricSVHIP ctx ds m _n k reverse iters (i0, d0, c0) = do
+  ids <- VS.thaw i0
+  dist <- VS.thaw d0
+  cnt <- VS.thaw c0
+  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (c_knn_graph_refine_csr_metric_host ctx ds (fromIntegral k) (fromIntegral reverse) (fromIntegral iters) (metricFlag m) 0 a b))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | Query a kNN graph: best-first beam search (rpt_graph_search_host).  @(gids, gcount)@ is a graph

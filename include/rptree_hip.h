@@ -151,6 +151,9 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *   graph_general (0 / 1)          kNN graph: every leaf on the tiled kernel (rpt_knn_graph_*)
  *   graph_refine_general (0 / 1)   kNN graph refinement: one point per workgroup for every k and
  *                                  reverse (rpt_knn_graph_refine_*)
+ *   graph_csr_masked (0 / 1)       kNN graph on CSR rows under cosine / inner product: the
+ *                                  presence-masked fold for every call, not only for data that stores
+ *                                  an inf or NaN (rpt_knn_graph_csr_metric_*)
  *   graph_search_nofilter (0 / 1)  graph search: no visited filter, only the beam itself is checked
  *                                  before a distance is computed (rpt_graph_search_*)
  *   graph_search_csr_stream (0 / 1)  graph search on CSR rows: every query passes through LDS in
@@ -574,6 +577,58 @@ int32_t rpt_knn_graph_refine_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, int3
 int32_t rpt_knn_graph_refine_csr_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
                                       int32_t reverse, int32_t iters, int32_t flags,
                                       int32_t* ids_host, double* dist_host, int32_t* count_host);
+
+/* ---- the kNN graph and its NN-descent rounds on SVector (CSR) rows, under cosine / inner product ----
+ * rpt_knn_graph_csr_metric_* and rpt_knn_graph_refine_csr_metric_* are rpt_knn_graph_csr_* and
+ * rpt_knn_graph_refine_csr_* with one more argument, `metric` (before `flags`): 0,
+ * RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER.  Everything stated for those entry points carries
+ * over word for word (mates, the order (distance, id), the layout, unused slots, k <= 64,
+ * RPT_GRAPH_ACCUMULATE, batch forests only, the refinement round and rpt_knn_graph_refine_last,
+ * rpt_knn_graph_last_pairs, the options graph_general / graph_refine_general); the one thing that
+ * changes is dist(i, j), and it is the definition rpt_knn_csr_metric_* uses, word for word:
+ * dotS(x, y) starts at +0.0, takes the columns stored in BOTH rows in ascending column order and
+ * folds acc = acc + x_c * y_c, every product and sum rounded on its own, f32 values widened
+ * exactly, no FMA.
+ *   metric == 0            the bits of rpt_knn_graph_csr_* / rpt_knn_graph_refine_csr_*
+ *   RPT_KNN_METRIC_INNER   dist(i, j) = -dotS(x_i, x_j)
+ *   RPT_KNN_METRIC_COSINE  dist(i, j) = 1 - dotS(x_i, x_j) / (sqrt(dotS(x_i, x_i)) * sqrt(dotS(x_j, x_j)))
+ *                          with the norms cached on the data set; an empty or all-zero row is at NaN
+ *                          from everything and ranks last, by id
+ * NaN ranks behind every number, NaNs among themselves by id; -0.0 (the inner distance of two rows
+ * that share no column) ties with +0.0, the id decides and the stored bits are the computed ones.
+ * Both distances are symmetric bit for bit, so a pair of a leaf is still evaluated once.
+ *   Stored inf and NaN  While every stored value is finite, this is the dense definition
+ *                (rpt_knn_graph_metric_* on the dense-ified rows with the same perm) bit for bit: a
+ *                column only one row stores would add x * (+0.0) = +-0.0 to an accumulator that is
+ *                never -0.0.  With a stored inf or NaN it is not: the dense fold meets inf * 0 = NaN
+ *                where dotS takes no product (dotS of {0: inf} and {1: 1.0} is +0.0).  The answer
+ *                is dotS in both cases.  The leaf kernels stage zero-filled windows; they read the
+ *                data set's cached statistic (the largest dotS(x, x)) on the device, and when it is
+ *                not finite they keep a presence word per staged row and fold a product only where
+ *                both rows store the column.  The context option graph_csr_masked = 1 sends every
+ *                call down that path; the answer does not depend on it.
+ *   Ascending columns  as above: unspecified answer, in bounds, terminates.
+ * Errors: any other `metric` value, both metric bits together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG
+ * (a metric bit in `flags` too).  Dense data: RPT_E_ARG.  A streamed forest: RPT_E_UNSUPPORTED.
+ * Everything else as rpt_knn_graph_csr_* / rpt_knn_graph_refine_csr_*; an error leaves the context
+ * usable.  The graph under either metric (the inner product for the statistic alone) and the
+ * refinement under cosine cache the rows' dotS(x, x) and their statistics on the data set, 8 bytes
+ * per row, on their first call.  Not built: rpt_graph_search_csr_* and rpt_graph_prepare_csr_*
+ * under a metric (RPT_E_UNSUPPORTED), streamed forests, the reference's right-fold innerSS order. */
+int32_t rpt_knn_graph_csr_metric_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                                     int32_t metric, int32_t flags, int32_t* ids_dev,
+                                     double* dist_dev, int32_t* count_dev);
+int32_t rpt_knn_graph_csr_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                                      int32_t metric, int32_t flags, int32_t* ids_host,
+                                      double* dist_host, int32_t* count_host);
+int32_t rpt_knn_graph_refine_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                            int32_t reverse, int32_t iters, int32_t metric,
+                                            int32_t flags, int32_t* ids_dev, double* dist_dev,
+                                            int32_t* count_dev);
+int32_t rpt_knn_graph_refine_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                             int32_t reverse, int32_t iters, int32_t metric,
+                                             int32_t flags, int32_t* ids_host, double* dist_host,
+                                             int32_t* count_host);
 
 /* ---- query the kNN graph: best-first beam search from given seeds ----
  * Input: the dense data set `data` (n rows of f64, f32 or bf16), the dense `queries` (the same d and

@@ -252,6 +252,7 @@ const OptDesc kOptions[] = {
     {"knn_general", &rpt_options::knn_general},
     {"graph_general", &rpt_options::graph_general},
     {"graph_refine_general", &rpt_options::graph_refine_general},
+    {"graph_csr_masked", &rpt_options::graph_csr_masked},
     {"graph_search_nofilter", &rpt_options::graph_search_nofilter},
     {"graph_search_csr_stream", &rpt_options::graph_search_csr_stream},
     {"graph_prepare_csr_resident", &rpt_options::graph_prepare_csr_resident},
@@ -1166,7 +1167,7 @@ int32_t check_graph_metric(int32_t metric) {
 }
 
 // rpt_knn_graph_dev (has_metric false: the metric bits in flags are refused) and
-// rpt_knn_graph_metric_dev
+// rpt_knn_graph_metric_dev; csr: rpt_knn_graph_csr_dev and rpt_knn_graph_csr_metric_dev
 int32_t graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k, bool has_metric,
                   int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
                   int32_t* count_dev, bool csr = false) {
@@ -1179,7 +1180,7 @@ int32_t graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t 
     return fail(RPT_E_UNSUPPORTED, "the kNN graph is built under metricL2 only (no metric flags)");
   RPT_ARG((flags & ~RPT_GRAPH_ACCUMULATE) == 0, "flags must be 0 or RPT_GRAPH_ACCUMULATE");
   if (csr) RPT_ARG(data->csr, "rpt_knn_graph_csr_* takes CSR data only (dense rows: rpt_knn_graph_*)");
-  else if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph takes dense data only (not CSR rows)");
+  else if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph takes dense data only (not CSR rows: rpt_knn_graph_csr_*, rpt_knn_graph_csr_metric_*)");
   if (f->xtopo)
     return fail(RPT_E_UNSUPPORTED, "the kNN graph takes batch forests only (not a streamed forest)");
   RPT_ARG(data->n == f->n && data->d == f->d && data->dtype == f->dtype,
@@ -1188,7 +1189,7 @@ int32_t graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t 
   RPT_ARG(f->n <= 0x7fffffff, "graph too large");
   RPT_ARG(f->n == 0 || (ids_dev && dist_dev && count_dev), "NULL output");
   RPT_HIP(hipSetDevice(ctx->device));
-  if (csr) return knn_graph_csr_dev(ctx, f, data, k, flags, ids_dev, dist_dev, count_dev);
+  if (csr) return knn_graph_csr_dev(ctx, f, data, k, metric, flags, ids_dev, dist_dev, count_dev);
   return knn_graph_dev(ctx, f, data, k, metric, flags, ids_dev, dist_dev, count_dev);
 }
 
@@ -1267,6 +1268,22 @@ int32_t rpt_knn_graph_csr_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* d
   });
 }
 
+int32_t rpt_knn_graph_csr_metric_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                                     int32_t metric, int32_t flags, int32_t* ids_dev,
+                                     double* dist_dev, int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    return graph_dev(ctx, f, data, k, true, metric, flags, ids_dev, dist_dev, count_dev, true);
+  });
+}
+
+int32_t rpt_knn_graph_csr_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                                      int32_t metric, int32_t flags, int32_t* ids_host,
+                                      double* dist_host, int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return graph_host(ctx, f, data, k, true, metric, flags, ids_host, dist_host, count_host, true);
+  });
+}
+
 int32_t rpt_knn_graph_last_pairs(rpt_ctx* ctx, int64_t* pairs) {
   return guarded([&]() -> int32_t {
     RPT_ARG(ctx && pairs, "NULL argument");
@@ -1288,7 +1305,7 @@ int32_t check_refine(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t r
     return fail(RPT_E_UNSUPPORTED, "the kNN graph is refined under metricL2 only (no metric flags)");
   RPT_ARG(flags == 0, "flags must be 0");
   if (csr) RPT_ARG(data->csr, "rpt_knn_graph_refine_csr_* takes CSR data only (dense rows: rpt_knn_graph_refine_*)");
-  else if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph refinement takes dense data only (not CSR rows)");
+  else if (data->csr) return fail(RPT_E_UNSUPPORTED, "the kNN graph refinement takes dense data only (not CSR rows: rpt_knn_graph_refine_csr_*, rpt_knn_graph_refine_csr_metric_*)");
   RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
   RPT_ARG(reverse >= 0 && reverse <= RPT_GRAPH_MAX_K, "reverse must be in [0,64] (RPT_GRAPH_MAX_K)");
   RPT_ARG(iters >= 1, "iters must be at least 1");
@@ -1329,7 +1346,7 @@ int32_t refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t rev
     RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags, csr));
     RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
     RPT_HIP(hipSetDevice(ctx->device));
-    if (csr) return knn_graph_refine_csr_dev(ctx, data, k, reverse, iters, ids_dev, dist_dev, count_dev);
+    if (csr) return knn_graph_refine_csr_dev(ctx, data, k, reverse, iters, metric, ids_dev, dist_dev, count_dev);
     return knn_graph_refine_dev(ctx, data, k, reverse, iters, metric, ids_dev, dist_dev, count_dev);
   }
 }
@@ -1354,7 +1371,7 @@ int32_t refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t re
       RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
       RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
     }
-    if (csr) RPT_TRY(knn_graph_refine_csr_dev(ctx, data, k, reverse, iters, ids.p, dist.p, cnt.p));
+    if (csr) RPT_TRY(knn_graph_refine_csr_dev(ctx, data, k, reverse, iters, metric, ids.p, dist.p, cnt.p));
     else RPT_TRY(knn_graph_refine_dev(ctx, data, k, reverse, iters, metric, ids.p, dist.p, cnt.p));
     RPT_HIP(stream_sync(ctx->stream));
     if (n) {
@@ -1413,6 +1430,24 @@ int32_t rpt_knn_graph_refine_csr_host(rpt_ctx* ctx, const rpt_dataset* data, int
                                       int32_t* ids_host, double* dist_host, int32_t* count_host) {
   return guarded([&]() -> int32_t {
     return refine_host(ctx, data, k, reverse, iters, false, 0, flags, ids_host, dist_host, count_host, true);
+  });
+}
+
+int32_t rpt_knn_graph_refine_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                            int32_t reverse, int32_t iters, int32_t metric,
+                                            int32_t flags, int32_t* ids_dev, double* dist_dev,
+                                            int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    return refine_dev(ctx, data, k, reverse, iters, true, metric, flags, ids_dev, dist_dev, count_dev, true);
+  });
+}
+
+int32_t rpt_knn_graph_refine_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                             int32_t reverse, int32_t iters, int32_t metric,
+                                             int32_t flags, int32_t* ids_host, double* dist_host,
+                                             int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return refine_host(ctx, data, k, reverse, iters, true, metric, flags, ids_host, dist_host, count_host, true);
   });
 }
 

@@ -184,6 +184,7 @@ struct rpt_options {
   int64_t knn_general = 0;      // kNN: unfused general path
   int64_t graph_general = 0;    // kNN graph: every leaf on the tiled kernel (64-row blocks), not the one-workgroup leaf kernel
   int64_t graph_refine_general = 0;  // kNN graph refinement: one point per workgroup for every k and reverse
+  int64_t graph_csr_masked = 0;  // kNN graph on CSR rows under cosine / inner: the presence-masked fold for every call
   int64_t graph_search_nofilter = 0;  // graph search: no visited filter (only the beam itself is checked before a distance)
   int64_t graph_search_csr_stream = 0;  // graph search on CSR rows: every query passes through LDS in pieces (none stays resident)
   int64_t graph_prepare_csr_resident = 0;  // graph preparation on CSR rows: entries of a point's neighbours up to which they
@@ -438,13 +439,15 @@ int32_t knn_graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int3
 int32_t knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
                              int32_t iters, int32_t metric, int32_t* ids_dev, double* dist_dev,
                              int32_t* count_dev);
-// ---- the same two on CSR rows under L2 (graph_csr.hip) -------------------------------------------
-// arguments checked by the caller (CSR data, f64 or f32 values, of the forest's shape); the
-// statistics go where knn_graph_dev's and knn_graph_refine_dev's go
+// ---- the same two on CSR rows (graph_csr.hip) ----------------------------------------------------
+// arguments checked by the caller (CSR data, f64 or f32 values, of the forest's shape; metric as
+// knn_graph_dev's, the cosine / inner-product distances from dotS, rptree_hip.h); the statistics go
+// where knn_graph_dev's and knn_graph_refine_dev's go
 int32_t knn_graph_csr_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
-                          int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+                          int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                          int32_t* count_dev);
 int32_t knn_graph_refine_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
-                                 int32_t iters, int32_t* ids_dev, double* dist_dev,
+                                 int32_t iters, int32_t metric, int32_t* ids_dev, double* dist_dev,
                                  int32_t* count_dev);
 // synchronises the stream
 int32_t knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* updates, int64_t* candidates);

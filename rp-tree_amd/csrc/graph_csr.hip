@@ -1,5 +1,6 @@
 // graph_csr.hip — the kNN graph of the indexed points and its NN-descent rounds on SVector (CSR)
-// rows under L2 (rpt_knn_graph_csr_*, rpt_knn_graph_refine_csr_*).
+// rows under L2 (rpt_knn_graph_csr_*, rpt_knn_graph_refine_csr_*) and under the cosine / inner-product
+// distances (rpt_knn_graph_csr_metric_*, rpt_knn_graph_refine_csr_metric_*; behind the L2 notes).
 //
 // dist(i, j) is graph.hip's: metricDDL2 as a left fold in double over dense(x_i), dense(x_j), the
 // rows with every absent column as +0.0.  A column where both rows hold +0.0 adds (+0.0 - +0.0)^2 =
@@ -27,6 +28,23 @@
 // Rows whose columns do not ascend strictly give an unspecified answer; every access stays inside
 // the row (a cursor never passes its row's end, a scatter checks its window) and every loop
 // advances a cursor, so the kernels stay in bounds and terminate.
+//
+// Cosine / inner product: the same three kernels instantiated on the distance (M), as graph.hip's.
+// dist(i, j) comes from dotS(x_i, x_j): the left fold acc + x_c * y_c from +0.0 over the columns
+// stored in BOTH rows, ascending (rptree_hip.h).  Under cosine the rows' cached dotS(x, x)
+// (rpt_dataset::sqnorm) travel next to the ids.
+//   Zero-filled windows give dotS while every stored value is finite: a column one row lacks adds
+//   x * (+0.0) = +-0.0, and an acc that starts at +0.0 is never -0.0 (a sum is -0.0 only when both
+//   operands are), so acc + (+-0.0) is acc.  This is the path that is timed.
+//   A stored inf or NaN breaks that (inf * 0 = NaN where dotS takes no product at all).  The leaf
+//   kernels therefore read the data set's statistic stats[0] (knn.hip row_sqnorm_csr_kernel: the
+//   largest dotS(x, x), as bits; finite exactly when every stored value is finite and no square
+//   overflows) on the device and branch uniformly: when it is not finite, or with the context option
+//   graph_csr_masked, every staged row also leaves a 32-bit presence word (bit c: the row stores
+//   column c0 + c) and a product is folded only where both rows' bits are set.  Nothing is read
+//   back to the host, and the answer does not depend on the path.
+//   The join's two-pointer merge needs no mask: under a metric it folds a step only when both sides
+//   take (ci == cj), and nothing is left to fold behind x_i's last column.
 #include <string.h>
 
 #include <algorithm>
@@ -49,7 +67,8 @@ struct GBlock {  // graph.hip's: rows [row0, row0 + 64) (tiled) or all rows (lea
   int32_t row0;
 };
 
-// graph.hip's tile_fold under L2: 4 x 4 pairs over cw columns
+// graph.hip's tile_fold: 4 x 4 pairs over cw columns
+template <int M>
 __device__ inline void tile_fold(const double* bufA, int ra, int sa, const double* bufB, int rb,
                                  int sb, int cw, double (&acc)[16]) {
   const double* pa = bufA + ra * kLS;
@@ -64,8 +83,46 @@ __device__ inline void tile_fold(const double* bufA, int ra, int sa, const doubl
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
-      for (int v = 0; v < 4; ++v) acc[u * 4 + v] = fold_step<kGraphL2>(acc[u * 4 + v], a[u], b[v]);
+      for (int v = 0; v < 4; ++v) acc[u * 4 + v] = fold_step<M>(acc[u * 4 + v], a[u], b[v]);
   }
+}
+
+// tile_fold under a metric with presence words (pmA / pmB: one per buffer row, bit c = the row
+// stores column c of the window): a product enters only where both rows store the column, and a
+// column that no pair of the tile shares is not read at all
+template <int M>
+__device__ inline void tile_fold_masked(const double* bufA, int ra, int sa, const unsigned* pmA,
+                                        const double* bufB, int rb, int sb, const unsigned* pmB,
+                                        int cw, double (&acc)[16]) {
+  const double* pa = bufA + ra * kLS;
+  const double* pb = bufB + rb * kLS;
+  unsigned ma[4], mb[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) ma[u] = pmA[ra + u * sa];
+#pragma unroll
+  for (int v = 0; v < 4; ++v) mb[v] = pmB[rb + v * sb];
+  unsigned todo = (ma[0] | ma[1] | ma[2] | ma[3]) & (mb[0] | mb[1] | mb[2] | mb[3]);
+  if (cw < 32) todo &= (1u << cw) - 1u;
+  while (todo) {  // ascending columns
+    const int c = __ffs((int)todo) - 1;
+    todo &= todo - 1u;
+    double a[4], b[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a[u] = pa[u * sa * kLS + c];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) b[v] = pb[v * sb * kLS + c];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+        if ((ma[u] & mb[v]) >> c & 1u) acc[u * 4 + v] = fold_step<M>(acc[u * 4 + v], a[u], b[v]);
+  }
+}
+
+// whether the metric kernels take the presence-masked fold: forced, or the largest dotS(x, x) of the
+// data set (stats[0], its bits with the sign cleared) is inf or NaN
+__device__ inline bool masked_fold(const unsigned long long* __restrict__ stats, int force) {
+  return force != 0 || stats[0] >= 0x7ff0000000000000ULL;
 }
 
 __global__ void graph_csr_init_kernel(int64_t n, int k, int32_t* __restrict__ ids,
@@ -113,10 +170,12 @@ __device__ inline int block_min_col(int v, int* wmin) {
 
 // The window [c0, c0 + cw) of one row into brow[0 .. cw): the row's two lanes zero it, then scatter
 // the row's entries of the window, one taking the even and one the odd entries from the cursor on.
-// Both lanes of a pair call it together (live == the pair owns a buffer row).
-template <class TV>
-__device__ inline void stage_window(RowCursor& rc, bool live, int h, int c0, int cw, double* brow,
-                                    const int32_t* __restrict__ col, const TV* __restrict__ val) {
+// Both lanes of a pair call it together (live == the pair owns a buffer row).  kMask: returns the
+// presence bits of the entries THIS lane scattered (bit c: column c0 + c), else 0.
+template <class TV, bool kMask = false>
+__device__ inline unsigned stage_window(RowCursor& rc, bool live, int h, int c0, int cw, double* brow,
+                                        const int32_t* __restrict__ col, const TV* __restrict__ val) {
+  [[maybe_unused]] unsigned bits = 0;
   if (live)
     for (int c = h; c < cw; c += 2) brow[c] = 0.0;
   wave_sync();  // the pair's zeros are in place before either lane scatters
@@ -125,7 +184,10 @@ __device__ inline void stage_window(RowCursor& rc, bool live, int h, int c0, int
   while (at < rc.end) {
     const int c = col[at];
     if (c >= c1) break;
-    if (live && c >= c0) brow[c - c0] = widen(val[at]);
+    if (live && c >= c0) {
+      brow[c - c0] = widen(val[at]);
+      if constexpr (kMask) bits |= 1u << (c - c0);
+    }
     at += 2;
   }
   const int64_t other = __shfl_xor(at, 1);
@@ -133,17 +195,21 @@ __device__ inline void stage_window(RowCursor& rc, bool live, int h, int c0, int
   if (np > rc.end) np = rc.end;
   rc.pos = np;
   rc.next = np < rc.end ? col[np] : kNoCol;
+  return bits;
 }
 
 // ---- leaves of up to 128 points: one workgroup per leaf, every pair once ----------------------
 // dynamic LDS: lds_doubles = max(4 ng (4 ng + 1), 4 ng * kLS) doubles (the window, later the
-// distance matrix), then 4 ng ints (the leaf's ids) and 4 ints (the waves' smallest columns)
-template <class TV>
+// distance matrix), then 4 ng ints (the leaf's ids) and 4 ints (the waves' smallest columns).
+// Cosine: 4 ng more doubles, the rows' norms rn[id], at the END of the doubles (graph.hip's place).
+// Cosine / inner: 4 ng more ints behind the others, the presence words of the staged rows.
+template <class TV, int M>
 __global__ __launch_bounds__(kThreads) void graph_csr_leaf_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const TV* __restrict__ val,
     int d, const int32_t* __restrict__ perm_t, const GBlock* __restrict__ blocks, int k,
     int lds_doubles, int32_t* __restrict__ ids, double* __restrict__ dist,
-    int32_t* __restrict__ count) {
+    int32_t* __restrict__ count, const double* __restrict__ rn,
+    const unsigned long long* __restrict__ stats, int force_masked) {
   extern __shared__ double smem[];
   double* buf = smem;
   int* sid = reinterpret_cast<int*>(smem + lds_doubles);
@@ -154,7 +220,15 @@ __global__ __launch_bounds__(kThreads) void graph_csr_leaf_kernel(
   const int ng = (s + 3) >> 2;  // row groups: group g holds the rows g, g + ng, g + 2 ng, g + 3 ng
   const int P = 4 * ng;
   int* wmin = sid + P;
-  for (int r = tid; r < P; r += kThreads) sid[r] = r < s ? perm_t[blk.off + r] : -1;
+  [[maybe_unused]] unsigned* pmask = reinterpret_cast<unsigned*>(wmin + 4);
+  [[maybe_unused]] double* snorm = smem + lds_doubles - P;
+  bool masked = false;  // L2: a constant, the masked branch is not instantiated
+  if constexpr (M != kGraphL2) masked = masked_fold(stats, force_masked);
+  for (int r = tid; r < P; r += kThreads) {
+    const int id = r < s ? perm_t[blk.off + r] : -1;
+    sid[r] = id;
+    if constexpr (M == kGraphCosine) snorm[r] = id >= 0 ? rn[id] : 0.0;
+  }
 
   // tiles (gi <= gj) of the upper triangle, row-major; up to three per lane
   const int ntiles = ng * (ng + 1) / 2;
@@ -188,11 +262,21 @@ __global__ __launch_bounds__(kThreads) void graph_csr_leaf_kernel(
     const int c0 = block_min_col(rc.next, wmin);  // ... and the last window has been read
     if (c0 == kNoCol) break;
     const int cw = d - c0 < kCW ? d - c0 : kCW;
-    stage_window<TV>(rc, live, h, c0, cw, buf + myrow * kLS, col, val);
-    __syncthreads();
+    if (!masked) {
+      stage_window<TV>(rc, live, h, c0, cw, buf + myrow * kLS, col, val);
+      __syncthreads();
 #pragma unroll
-    for (int u = 0; u < 3; ++u)
-      if (gi[u] >= 0) tile_fold(buf, gi[u], ng, buf, gj[u], ng, cw, acc[u]);
+      for (int u = 0; u < 3; ++u)
+        if (gi[u] >= 0) tile_fold<M>(buf, gi[u], ng, buf, gj[u], ng, cw, acc[u]);
+    } else if constexpr (M != kGraphL2) {
+      unsigned bits = stage_window<TV, true>(rc, live, h, c0, cw, buf + myrow * kLS, col, val);
+      bits |= __shfl_xor(bits, 1);
+      if (live && h == 0) pmask[myrow] = bits;
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 3; ++u)
+        if (gi[u] >= 0) tile_fold_masked<M>(buf, gi[u], ng, pmask, buf, gj[u], ng, pmask, cw, acc[u]);
+    }
   }
   __syncthreads();
 
@@ -207,7 +291,9 @@ __global__ __launch_bounds__(kThreads) void graph_csr_leaf_kernel(
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
           const int ri = gi[u] + ng * a, rj = gj[u] + ng * b;
-          const double v = fold_finish<kGraphL2>(acc[u][a * 4 + b], 0.0, 0.0);
+          double v;
+          if constexpr (M == kGraphCosine) v = fold_finish<M>(acc[u][a * 4 + b], snorm[ri], snorm[rj]);
+          else v = fold_finish<M>(acc[u][a * 4 + b], 0.0, 0.0);
           D[ri * SD + rj] = v;
           D[rj * SD + ri] = v;
         }
@@ -260,30 +346,40 @@ __global__ __launch_bounds__(kThreads) void graph_csr_leaf_kernel(
 // ---- any leaf: 64 rows of a leaf per workgroup against the leaf in blocks of 64 ---------------
 // dynamic LDS: 2 * 64 * kLS doubles (the windows of the two blocks, rows 0 .. 63 and 64 .. 127 of
 // one buffer; later the 64 x 65 distance block), 64 k doubles (the rows' lists), then ints: 64 k
-// list ids, 64 counts, 64 changed flags, 64 + 64 row ids, 4 smallest columns
-template <class TV>
+// list ids, 64 counts, 64 changed flags, 64 + 64 row ids, 4 smallest columns.  Cosine: 64 + 64 more
+// doubles behind the lists' (the norms of the two blocks' rows).  Cosine / inner: 64 + 64 more ints
+// at the end, the presence words of the staged rows.
+template <class TV, int M>
 __global__ __launch_bounds__(kThreads) void graph_csr_tiled_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const TV* __restrict__ val,
     int d, const int32_t* __restrict__ perm_t, const GBlock* __restrict__ blocks, int k,
-    int32_t* __restrict__ ids, double* __restrict__ dist, int32_t* __restrict__ count) {
+    int32_t* __restrict__ ids, double* __restrict__ dist, int32_t* __restrict__ count,
+    const double* __restrict__ rn, const unsigned long long* __restrict__ stats, int force_masked) {
   extern __shared__ double smem[];
+  constexpr int kNorms = M == kGraphCosine ? 2 * kTB : 0;
   double* bufA = smem;
   double* bufB = smem + kTB * kLS;
   double* lst_d = smem + 2 * kTB * kLS;
-  int* lst_i = reinterpret_cast<int*>(lst_d + kTB * k);
+  [[maybe_unused]] double* nrmA = lst_d + kTB * k;
+  [[maybe_unused]] double* nrmB = nrmA + kTB;
+  int* lst_i = reinterpret_cast<int*>(lst_d + kTB * k + kNorms);
   int* lst_c = lst_i + kTB * k;
   int* lst_ch = lst_c + kTB;
   int* sidA = lst_ch + kTB;
   int* sidB = sidA + kTB;
   int* wmin = sidB + kTB;
+  [[maybe_unused]] unsigned* pmask = reinterpret_cast<unsigned*>(wmin + 4);
   const GBlock blk = blocks[blockIdx.x];
   const int s = blk.n;
   if (s < 2) return;
+  bool masked = false;  // L2: a constant, the masked branch is not instantiated
+  if constexpr (M != kGraphL2) masked = masked_fold(stats, force_masked);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nr = s - blk.row0 < kTB ? s - blk.row0 : kTB;
   if (tid < kTB) {
     const int g = tid < nr ? perm_t[blk.off + blk.row0 + tid] : -1;
     sidA[tid] = g;
+    if constexpr (M == kGraphCosine) nrmA[tid] = g >= 0 ? rn[g] : 0.0;
     int c = g >= 0 ? count[g] : 0;
     lst_c[tid] = c < 0 ? 0 : (c > k ? k : c);
     lst_ch[tid] = 0;
@@ -304,7 +400,11 @@ __global__ __launch_bounds__(kThreads) void graph_csr_tiled_kernel(
   for (int cb = 0; cb < s; cb += kTB) {
     const int nc = s - cb < kTB ? s - cb : kTB;
     __syncthreads();  // the last block's selection is over
-    if (tid < kTB) sidB[tid] = tid < nc ? perm_t[blk.off + cb + tid] : -1;
+    if (tid < kTB) {
+      const int g = tid < nc ? perm_t[blk.off + cb + tid] : -1;
+      sidB[tid] = g;
+      if constexpr (M == kGraphCosine) nrmB[tid] = g >= 0 ? rn[g] : 0.0;
+    }
     RowCursor rc;
     {
       int id = -1;
@@ -322,17 +422,29 @@ __global__ __launch_bounds__(kThreads) void graph_csr_tiled_kernel(
       const int c0 = block_min_col(rc.next, wmin);
       if (c0 == kNoCol) break;
       const int cw = d - c0 < kCW ? d - c0 : kCW;
-      stage_window<TV>(rc, true, h, c0, cw, smem + myrow * kLS, col, val);
-      __syncthreads();
-      tile_fold(bufA, gi, 16, bufB, gj, 16, cw, acc);
+      if (!masked) {
+        stage_window<TV>(rc, true, h, c0, cw, smem + myrow * kLS, col, val);
+        __syncthreads();
+        tile_fold<M>(bufA, gi, 16, bufB, gj, 16, cw, acc);
+      } else if constexpr (M != kGraphL2) {
+        unsigned bits = stage_window<TV, true>(rc, true, h, c0, cw, smem + myrow * kLS, col, val);
+        bits |= __shfl_xor(bits, 1);
+        if (h == 0) pmask[myrow] = bits;
+        __syncthreads();
+        tile_fold_masked<M>(bufA, gi, 16, pmask, bufB, gj, 16, pmask + kTB, cw, acc);
+      }
     }
     __syncthreads();
     double* D = smem;
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-      for (int b = 0; b < 4; ++b)
-        D[(gi + 16 * a) * SD + gj + 16 * b] = fold_finish<kGraphL2>(acc[a * 4 + b], 0.0, 0.0);
+      for (int b = 0; b < 4; ++b) {
+        double v;
+        if constexpr (M == kGraphCosine) v = fold_finish<M>(acc[a * 4 + b], nrmA[gi + 16 * a], nrmB[gj + 16 * b]);
+        else v = fold_finish<M>(acc[a * 4 + b], 0.0, 0.0);
+        D[(gi + 16 * a) * SD + gj + 16 * b] = v;
+      }
     __syncthreads();
     for (int r = wave; r < nr; r += 4) {
       const int me = sidA[r];
@@ -365,52 +477,72 @@ __global__ __launch_bounds__(kThreads) void graph_csr_tiled_kernel(
   }
 }
 
-template <class TV>
+template <class TV, int M>
 int32_t launch_graph_csr(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
                          bool general, int smax, const GBlock* blocks_dev, int64_t nblocks,
                          int32_t* ids, double* dist, int32_t* count) {
   const TV* val = static_cast<const TV*>(data->val);
   const int d = data->d;
+  // the norms, and behind them the statistics (ensure_sqnorm); L2 reads neither
+  const double* rn = M == kGraphL2 ? nullptr : data->sqnorm;
+  const unsigned long long* stats =
+      M == kGraphL2 ? nullptr : reinterpret_cast<const unsigned long long*>(data->sqnorm + data->n);
+  const int force = ctx->opt.graph_csr_masked != 0;
   static DeviceOnce attr_once[2];
   if (!general) {
     const int ng = (smax + 3) / 4, P = 4 * ng;
-    const int lds_doubles = std::max(P * (P + 1), P * kLS);
-    const size_t smem = (size_t)lds_doubles * 8 + (size_t)(P + 4) * 4;
+    const int lds_doubles = std::max(P * (P + 1), P * kLS) + (M == kGraphCosine ? P : 0);
+    const size_t smem = (size_t)lds_doubles * 8 + (size_t)(P + 4 + (M == kGraphL2 ? 0 : P)) * 4;
     RPT_TRY(attr_once[0].run(ctx->device, [&]() -> int32_t {
-      RPT_HIP(hipFuncSetAttribute((const void*)graph_csr_leaf_kernel<TV>,
+      RPT_HIP(hipFuncSetAttribute((const void*)graph_csr_leaf_kernel<TV, M>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
       return RPT_OK;
     }));
     for (int32_t t = 0; t < f->T; ++t)
-      hipLaunchKernelGGL((graph_csr_leaf_kernel<TV>), dim3((unsigned)nblocks), dim3(kThreads), smem,
+      hipLaunchKernelGGL((graph_csr_leaf_kernel<TV, M>), dim3((unsigned)nblocks), dim3(kThreads), smem,
                          ctx->stream, data->rowptr, data->col, val, d,
-                         f->perm.p + (int64_t)t * f->n, blocks_dev, k, lds_doubles, ids, dist, count);
+                         f->perm.p + (int64_t)t * f->n, blocks_dev, k, lds_doubles, ids, dist, count,
+                         rn, stats, force);
   } else {
-    const size_t smem = (size_t)(2 * kTB * kLS + kTB * k) * 8 + (size_t)(kTB * k + 4 * kTB + 4) * 4;
+    const size_t smem = (size_t)(2 * kTB * kLS + kTB * k + (M == kGraphCosine ? 2 * kTB : 0)) * 8 +
+                        (size_t)(kTB * k + 4 * kTB + 4 + (M == kGraphL2 ? 0 : 2 * kTB)) * 4;
     RPT_TRY(attr_once[1].run(ctx->device, [&]() -> int32_t {
-      RPT_HIP(hipFuncSetAttribute((const void*)graph_csr_tiled_kernel<TV>,
+      RPT_HIP(hipFuncSetAttribute((const void*)graph_csr_tiled_kernel<TV, M>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
       return RPT_OK;
     }));
     for (int32_t t = 0; t < f->T; ++t)
-      hipLaunchKernelGGL((graph_csr_tiled_kernel<TV>), dim3((unsigned)nblocks), dim3(kThreads), smem,
+      hipLaunchKernelGGL((graph_csr_tiled_kernel<TV, M>), dim3((unsigned)nblocks), dim3(kThreads), smem,
                          ctx->stream, data->rowptr, data->col, val, d,
-                         f->perm.p + (int64_t)t * f->n, blocks_dev, k, ids, dist, count);
+                         f->perm.p + (int64_t)t * f->n, blocks_dev, k, ids, dist, count, rn, stats,
+                         force);
   }
   RPT_HIP(hipGetLastError());
   return RPT_OK;
 }
 
-// dynamic LDS, per wave (wave_bytes): kPiece doubles and kPiece ints (a piece of x_i's values and
-// columns), H ints (the hash set, later the new candidates), k + r ints (B(i))
 template <class TV>
+int32_t launch_graph_csr_metric(int m, rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
+                                bool general, int smax, const GBlock* blocks_dev, int64_t nblocks,
+                                int32_t* ids, double* dist, int32_t* count) {
+  if (m == kGraphCosine)
+    return launch_graph_csr<TV, kGraphCosine>(ctx, f, data, k, general, smax, blocks_dev, nblocks, ids, dist, count);
+  if (m == kGraphInner)
+    return launch_graph_csr<TV, kGraphInner>(ctx, f, data, k, general, smax, blocks_dev, nblocks, ids, dist, count);
+  return launch_graph_csr<TV, kGraphL2>(ctx, f, data, k, general, smax, blocks_dev, nblocks, ids, dist, count);
+}
+
+// dynamic LDS, per wave (wave_bytes): kPiece doubles and kPiece ints (a piece of x_i's values and
+// columns), H ints (the hash set, later the new candidates), k + r ints (B(i)).  rn: the rows'
+// dotS(x, x) (cosine only).
+template <class TV, int M>
 __global__ __launch_bounds__(256) void refine_join_csr_kernel(
     RefineState* st, const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
     const TV* __restrict__ val, int64_t n, int k, int r, int H, int wave_bytes,
     const int32_t* __restrict__ ids, const double* __restrict__ dist,
     const int32_t* __restrict__ count, const int64_t* __restrict__ roff,
     const int32_t* __restrict__ rsrc, const double* __restrict__ rdist, int32_t* __restrict__ oids,
-    double* __restrict__ odist, int32_t* __restrict__ ocount) {
+    double* __restrict__ odist, int32_t* __restrict__ ocount, const double* __restrict__ rn) {
   if (!st->active) return;
   extern __shared__ double smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
@@ -485,6 +617,8 @@ __global__ __launch_bounds__(256) void refine_join_csr_kernel(
     n_cand += (unsigned long long)m;
 
     const int64_t ib = rowptr[i], ie = rowptr[i + 1];
+    [[maybe_unused]] double ni = 0.0;
+    if constexpr (M == kGraphCosine) ni = rn[i];
     bool changed = false;
     for (int b0 = 0; b0 < m; b0 += 64) {
       const int nrows = m - b0 < 64 ? m - b0 : 64;
@@ -515,7 +649,11 @@ __global__ __launch_bounds__(256) void refine_join_csr_kernel(
           while (ii < np) {  // every step takes an entry of x_i or of the candidate
             const int ci = pc[ii];
             const bool take_i = ci <= cj, take_j = cj <= ci;
-            acc = fold_step<kGraphL2>(acc, take_i ? pv[ii] : 0.0, take_j ? vj : 0.0);
+            if constexpr (M == kGraphL2) {
+              acc = fold_step<kGraphL2>(acc, take_i ? pv[ii] : 0.0, take_j ? vj : 0.0);
+            } else {  // dotS: only a column both rows store
+              if (take_i && take_j) acc = fold_step<M>(acc, pv[ii], vj);
+            }
             if (take_i) ++ii;
             if (take_j) {
               ++jp;
@@ -528,12 +666,18 @@ __global__ __launch_bounds__(256) void refine_join_csr_kernel(
           }
         }
       }
-      while (jp < je) {  // what the candidate holds behind x_i's last column
-        acc = fold_step<kGraphL2>(acc, 0.0, vj);
-        ++jp;
-        if (jp < je) vj = widen(val[jp]);
+      if constexpr (M == kGraphL2) {
+        while (jp < je) {  // what the candidate holds behind x_i's last column
+          acc = fold_step<kGraphL2>(acc, 0.0, vj);
+          ++jp;
+          if (jp < je) vj = widen(val[jp]);
+        }
       }
-      changed |= wave_merge(ld, lid, c, k, fold_finish<kGraphL2>(acc, 0.0, 0.0), my, lane < nrows, 0.0, -1, false);
+      double dv;
+      if constexpr (M == kGraphL2) dv = fold_finish<kGraphL2>(acc, 0.0, 0.0);
+      else if constexpr (M == kGraphCosine) dv = fold_finish<M>(acc, ni, my >= 0 ? rn[my] : 0.0);
+      else dv = fold_finish<M>(acc, 0.0, 0.0);
+      changed |= wave_merge(ld, lid, c, k, dv, my, lane < nrows, 0.0, -1, false);
     }
 
     if (lane < k) {
@@ -556,32 +700,44 @@ __global__ __launch_bounds__(256) void refine_join_csr_kernel(
   }
 }
 
-template <class TV>
+template <class TV, int M>
 int32_t launch_join_csr(rpt_ctx* ctx, RefineState* st, const rpt_dataset* data, int k, int r, int H,
                         int wave_bytes, int W, const int32_t* ids, const double* dist,
                         const int32_t* count, const int64_t* roff, const int32_t* rsrc,
                         const double* rdist, int32_t* oids, double* odist, int32_t* ocount) {
   static DeviceOnce attr_once;
   RPT_TRY(attr_once.run(ctx->device, [&]() -> int32_t {
-    RPT_HIP(hipFuncSetAttribute((const void*)refine_join_csr_kernel<TV>,
+    RPT_HIP(hipFuncSetAttribute((const void*)refine_join_csr_kernel<TV, M>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
     return RPT_OK;
   }));
   const int64_t want = (data->n + W - 1) / W;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)ctx->n_cu * 16));
-  hipLaunchKernelGGL((refine_join_csr_kernel<TV>), dim3(grid), dim3(64 * W), (size_t)wave_bytes * W,
+  hipLaunchKernelGGL((refine_join_csr_kernel<TV, M>), dim3(grid), dim3(64 * W), (size_t)wave_bytes * W,
                      ctx->stream, st, data->rowptr, data->col, static_cast<const TV*>(data->val),
                      data->n, k, r, H, wave_bytes, ids, dist, count, roff, rsrc, rdist, oids, odist,
-                     ocount);
+                     ocount, M == kGraphCosine ? data->sqnorm : nullptr);
   return RPT_OK;
+}
+
+template <class TV, class... A>
+int32_t launch_join_csr_metric(int m, A&&... a) {
+  if (m == kGraphCosine) return launch_join_csr<TV, kGraphCosine>(a...);
+  if (m == kGraphInner) return launch_join_csr<TV, kGraphInner>(a...);
+  return launch_join_csr<TV, kGraphL2>(a...);
 }
 
 }  // namespace
 
 int32_t knn_graph_csr_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
-                          int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+                          int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                          int32_t* count_dev) {
   ctx->last_graph_pairs = 0;
   if (f->n == 0) return RPT_OK;
+  const int m = graph_metric_of(metric);
+  // the rows' dotS(x, x) and their statistics, cached on the dataset: the inner product reads the
+  // statistics too (which fold the leaf kernels take)
+  if (m != kGraphL2) RPT_TRY(ensure_sqnorm(ctx, data));
   // the leaf table: the same for every tree (Internal.hs:289,495,503)
   std::vector<Node> nodes;
   enumerate_topology(f->n, f->L, f->min_leaf, nodes);
@@ -618,13 +774,15 @@ int32_t knn_graph_csr_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, 
   ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
   const int64_t nb = (int64_t)blocks.size();
   if (data->dtype == RPT_F64)
-    return launch_graph_csr<double>(ctx, f, data, k, general, (int)smax, bdev.p, nb, ids_dev, dist_dev, count_dev);
-  return launch_graph_csr<float>(ctx, f, data, k, general, (int)smax, bdev.p, nb, ids_dev, dist_dev, count_dev);
+    return launch_graph_csr_metric<double>(m, ctx, f, data, k, general, (int)smax, bdev.p, nb, ids_dev, dist_dev, count_dev);
+  return launch_graph_csr_metric<float>(m, ctx, f, data, k, general, (int)smax, bdev.p, nb, ids_dev, dist_dev, count_dev);
 }
 
 int32_t knn_graph_refine_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
-                                 int32_t iters, int32_t* ids_dev, double* dist_dev,
+                                 int32_t iters, int32_t metric, int32_t* ids_dev, double* dist_dev,
                                  int32_t* count_dev) {
+  const int m = graph_metric_of(metric);
+  if (m == kGraphCosine) RPT_TRY(ensure_sqnorm(ctx, data));  // the join needs no mask, so no statistics
   if (!ctx->refine_state_dev) {
     hipError_t e = dev_alloc(&ctx->refine_state_dev, sizeof(RefineState));
     if (e != hipSuccess)
@@ -671,11 +829,11 @@ int32_t knn_graph_refine_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t 
                            dist_dev, count_dev, roff.p, cur.p, rsrc.p, rdist.p);
       }
       if (data->dtype == RPT_F64)
-        RPT_TRY(launch_join_csr<double>(ctx, st, data, k, r, H, wave_bytes, W, ids_dev, dist_dev, count_dev,
-                                        roff.p, rsrc.p, rdist.p, sids.p, sdist.p, scount.p));
+        RPT_TRY(launch_join_csr_metric<double>(m, ctx, st, data, k, r, H, wave_bytes, W, ids_dev, dist_dev,
+                                               count_dev, roff.p, rsrc.p, rdist.p, sids.p, sdist.p, scount.p));
       else
-        RPT_TRY(launch_join_csr<float>(ctx, st, data, k, r, H, wave_bytes, W, ids_dev, dist_dev, count_dev,
-                                       roff.p, rsrc.p, rdist.p, sids.p, sdist.p, scount.p));
+        RPT_TRY(launch_join_csr_metric<float>(m, ctx, st, data, k, r, H, wave_bytes, W, ids_dev, dist_dev,
+                                              count_dev, roff.p, rsrc.p, rdist.p, sids.p, sdist.p, scount.p));
       hipLaunchKernelGGL(refine_copy_kernel, dim3(grid_e), dim3(256), 0, ctx->stream, st, n, k, sids.p,
                          sdist.p, scount.p, ids_dev, dist_dev, count_dev);
     }

@@ -501,6 +501,54 @@ inline GraphResult knnGraphRefineSV(Context& ctx, const Dataset& data, const Gra
   return out;
 }
 
+// knnGraphSV under another distance (rpt_knn_graph_csr_metric_host): Metric::Cosine / Metric::Inner
+// over the indices both rows store (the left fold of the shared columns' products from +0.0, the
+// definition knnBatch uses on SVector data); Metric::L2 gives knnGraphSV's bits.  While every stored
+// value is finite that is knnGraph(tts, k, metric) on the dense-ified rows bit for bit; with a stored
+// inf or NaN it is not, and the answer is this definition.  accumulate must be a result under the
+// same metric (not detected).
+inline GraphResult knnGraphSV(const RPForest& tts, int k, Metric metric, const GraphResult* accumulate = nullptr) {
+  const size_t n = (size_t)tts.data->n;
+  GraphResult g;
+  if (accumulate) {
+    if (accumulate->k != k || accumulate->count.size() != n)
+      throw RPTError(RPT_E_ARG, "accumulate: a result of another data set or k");
+    g = *accumulate;
+  }
+  g.k = k;
+  g.ids.resize(n * (size_t)(k > 0 ? k : 0) + 1);  // + 1: non-NULL pointers for an empty data set
+  g.dist.resize(n * (size_t)(k > 0 ? k : 0) + 1);
+  g.count.resize(n + 1);
+  check(rpt_knn_graph_csr_metric_host(tts.ctx->get(), tts.get(), tts.data->get(), k, metric_flags(metric),
+                                      accumulate ? RPT_GRAPH_ACCUMULATE : 0, g.ids.data(), g.dist.data(),
+                                      g.count.data()));
+  g.ids.resize(n * (size_t)k);
+  g.dist.resize(n * (size_t)k);
+  g.count.resize(n);
+  return g;
+}
+
+// knnGraphRefineSV under another distance (rpt_knn_graph_refine_csr_metric_host); the graph's stored
+// distances must be that metric's (knnGraphSV's under the same Metric; another is not detected)
+inline GraphResult knnGraphRefineSV(Context& ctx, const Dataset& data, const GraphResult& g, Metric metric,
+                                    int iters = 1, int reverse = -1, RefineStats* stats = nullptr) {
+  const size_t n = (size_t)data.n;
+  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0) || g.dist.size() != g.ids.size())
+    throw RPTError(RPT_E_ARG, "knnGraphRefineSV: a graph of another data set or k");
+  GraphResult out = g;
+  out.ids.resize(out.ids.size() + 1);  // + 1: non-NULL pointers for an empty data set
+  out.dist.resize(out.dist.size() + 1);
+  out.count.resize(n + 1);
+  check(rpt_knn_graph_refine_csr_metric_host(ctx.get(), data.get(), g.k, reverse < 0 ? g.k : reverse, iters,
+                                             metric_flags(metric), 0, out.ids.data(), out.dist.data(),
+                                             out.count.data()));
+  out.ids.resize(n * (size_t)g.k);
+  out.dist.resize(n * (size_t)g.k);
+  out.count.resize(n);
+  if (stats) check(rpt_knn_graph_refine_last(ctx.get(), &stats->rounds, &stats->updates, &stats->candidates));
+  return out;
+}
+
 // A kNN graph made ready for graphSearch (rpt_graph_prepare_host) -> a graph of kout columns; `g`
 // is not modified.  diversify: walking a row in stored order, a neighbour is dropped when an
 // already kept neighbour of the row is nearer to it than the point itself is (a plain <, the

@@ -41,6 +41,7 @@ __all__ = [
     "knnGraphRefine", "knnGraphRefineDev", "knnGraphRefineLast",
     "knnGraphMetric", "knnGraphMetricDev", "knnGraphRefineMetric", "knnGraphRefineMetricDev",
     "knnGraphSV", "knnGraphSVDev", "knnGraphRefineSV", "knnGraphRefineSVDev",
+    "knnGraphMetricSV", "knnGraphMetricSVDev", "knnGraphRefineMetricSV", "knnGraphRefineMetricSVDev",
     "graphSearch", "graphSearchDev", "graphSearchLast", "graphSearchSV", "graphSearchSVDev",
     "graphPrepare", "graphPrepareDev", "graphPrepareLast", "graphPrepareSV", "graphPrepareSVDev",
 ]
@@ -870,7 +871,8 @@ def knnGraphMetric(distf, k, forest, accumulate=None):
     bits as knnGraph), metricCosine or metricInner; the distances are those host functions bit for
     bit (the left-fold dot in double for every dtype), a zero row is NaN under metricCosine and
     ranks last.  accumulate: an earlier answer UNDER THE SAME distf (another is not detected: the
-    stored distances are taken as stored).  Everything else as knnGraph."""
+    stored distances are taken as stored).  Everything else as knnGraph.  Dense data only: SVector
+    (CSR) rows are refused, knnGraphMetricSV takes them."""
     metric = _metric_flag(distf)
     ctx, n = forest.ctx, forest.N
     if accumulate is None:
@@ -930,6 +932,44 @@ def knnGraphSVDev(k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
     check(lib().rpt_knn_graph_csr_dev(forest.ctx._h, forest._h, forest.data._h, int(k),
                                       RPT_GRAPH_ACCUMULATE if accumulate else 0, C.c_void_p(ids_ptr),
                                       C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
+
+
+def knnGraphMetricSV(distf, k, forest, accumulate=None):
+    """knnGraphSV under another distance (rpt_knn_graph_csr_metric_host).  distf: None / metricL2
+    (the same bits as knnGraphSV), metricCosine or metricInner, evaluated over the indices both rows
+    store (see metricInner; the definition knnBatch uses on SVector data): the left fold of the
+    products of the shared columns from +0.0, in double.  While every stored value is finite that
+    is knnGraphMetric on the dense-ified rows bit for bit; with a stored inf or NaN it is not (the
+    dense fold meets inf * 0), and the answer is this definition either way.  An empty or all-zero
+    row is NaN under metricCosine and ranks last, by id; two rows that share no index are at
+    metricInner distance -0.0, which ties with +0.0.  accumulate: an earlier answer UNDER THE SAME
+    distf.  Everything else as knnGraphSV.  (knnGraphMetric itself takes dense data only.)"""
+    metric = _metric_flag(distf)
+    ctx, n = forest.ctx, forest.N
+    if accumulate is None:
+        flags = 0
+        ids = np.empty((n, k), dtype=np.int32)
+        dist = np.empty((n, k), dtype=np.float64)
+        cnt = np.empty(n, dtype=np.int32)
+    else:
+        flags = RPT_GRAPH_ACCUMULATE
+        ids = np.array(accumulate[0], dtype=np.int32, order="C")
+        dist = np.array(accumulate[1], dtype=np.float64, order="C")
+        cnt = np.array(accumulate[2], dtype=np.int32, order="C")
+        if ids.shape != (n, k) or dist.shape != (n, k) or cnt.shape != (n,):
+            raise ValueError("accumulate must be (ids[n][k], dist[n][k], count[n]) of this forest's n and k")
+    check(lib().rpt_knn_graph_csr_metric_host(ctx._h, forest._h, forest.data._h, int(k), metric, flags,
+                                              _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnGraphMetricSVDev(distf, k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
+    """knnGraphMetricSV into device arrays (rpt_knn_graph_csr_metric_dev); the arrays and the
+    synchronisation as knnGraphDev's."""
+    metric = _metric_flag(distf)
+    check(lib().rpt_knn_graph_csr_metric_dev(forest.ctx._h, forest._h, forest.data._h, int(k),
+                                             metric, RPT_GRAPH_ACCUMULATE if accumulate else 0,
+                                             C.c_void_p(ids_ptr), C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
 def knnGraphLastPairs(ctx=None):
@@ -1009,7 +1049,8 @@ def knnGraphRefineMetric(distf, graph, data, iters=1, reverse=None, ctx=None):
     metricL2 (the same bits as knnGraphRefine), metricCosine or metricInner; distances not already
     in row i are those host functions bit for bit.  The graph's stored distances must be distf's
     (knnGraphMetric's under the same distf; another metric is not detected).  Everything else as
-    knnGraphRefine."""
+    knnGraphRefine.  Dense data only: SVector (CSR) rows are refused, knnGraphRefineMetricSV takes
+    them."""
     metric = _metric_flag(distf)
     ds = _refine_data(data)
     ctx = ctx or ds.ctx
@@ -1032,6 +1073,36 @@ def knnGraphRefineMetricDev(distf, k, data, ids_ptr, dist_ptr, count_ptr, iters=
     check(lib().rpt_knn_graph_refine_metric_dev(ds.ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
                                                 int(iters), metric, 0, C.c_void_p(ids_ptr),
                                                 C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
+
+
+def knnGraphRefineMetricSV(distf, graph, data, iters=1, reverse=None, ctx=None):
+    """knnGraphRefineSV under another distance (rpt_knn_graph_refine_csr_metric_host).  distf: None /
+    metricL2 (the same bits as knnGraphRefineSV), metricCosine or metricInner over the indices both
+    rows store, as knnGraphMetricSV defines them.  The graph's stored distances must be distf's
+    (knnGraphMetricSV's under the same distf; another metric is not detected).  Everything else as
+    knnGraphRefineSV.  (knnGraphRefineMetric itself takes dense data only.)"""
+    metric = _metric_flag(distf)
+    ds = _refine_data(data)
+    ctx = ctx or ds.ctx
+    ids = np.array(graph[0], dtype=np.int32, order="C")
+    dist = np.array(graph[1], dtype=np.float64, order="C")
+    cnt = np.array(graph[2], dtype=np.int32, order="C")
+    if ids.ndim != 2 or ids.shape[0] != ds.n or dist.shape != ids.shape or cnt.shape != (ds.n,):
+        raise ValueError("graph must be (ids[n][k], dist[n][k], count[n]) over the data set's n rows")
+    k = ids.shape[1]
+    check(lib().rpt_knn_graph_refine_csr_metric_host(ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
+                                                     int(iters), metric, 0, _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnGraphRefineMetricSVDev(distf, k, data, ids_ptr, dist_ptr, count_ptr, iters=1, reverse=None):
+    """knnGraphRefineMetricSV on device arrays in place (rpt_knn_graph_refine_csr_metric_dev); the
+    arrays and the synchronisation as knnGraphRefineDev's."""
+    metric = _metric_flag(distf)
+    ds = _refine_data(data)
+    check(lib().rpt_knn_graph_refine_csr_metric_dev(ds.ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
+                                                    int(iters), metric, 0, C.c_void_p(ids_ptr),
+                                                    C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
 def knnGraphRefineLast(ctx=None):

@@ -88,6 +88,10 @@ SYMBOLS = {
     "rpt_knn_graph_csr_host": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "rpt_knn_graph_refine_csr_dev": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_knn_graph_refine_csr_host": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "rpt_knn_graph_csr_metric_dev": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rpt_knn_graph_csr_metric_host": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rpt_knn_graph_refine_csr_metric_dev": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "rpt_knn_graph_refine_csr_metric_host": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_csr_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
