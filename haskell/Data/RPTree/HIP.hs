@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -61,6 +61,8 @@ foreign import ccall safe "rpt_graph_search_host" c_graph_search_host :: Ptr Ctx
 foreign import ccall safe "rpt_graph_search_csr_host" c_graph_search_csr_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_host" c_graph_prepare_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_csr_host" c_graph_prepare_csr_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_graph_search_csr_metric_host" c_graph_search_csr_metric_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_graph_prepare_csr_metric_host" c_graph_prepare_csr_metric_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_csr_metric_host" c_knn_csr_metric_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_recall_hits_csr_metric_host" c_recall_hits_csr_metric :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
@@ -387,6 +389,22 @@ graphSearchSVHIP ctx ds qs nq kg (gids, gcount) s seeds k ef = do
       c_graph_search_csr_host ctx ds qs (fromIntegral kg) pg pc (fromIntegral s) ps (fromIntegral k) (fromIntegral ef) 0 0 a b)))))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
+-- | 'graphSearchSVHIP' under another distance (rpt_graph_search_csr_metric_host): 'MetricCosine' /
+-- 'MetricInner' over the indices both the query and the row store (the left fold of the shared
+-- indices' products from +0.0, as 'knnGraphMetricSVHIP' defines them); 'MetricL2' gives
+-- 'graphSearchSVHIP's bits.  While every stored value is finite the answer is 'graphSearchHIP' under
+-- the same 'Metric' on the dense-ified data set and queries bit for bit.  A query without nonzeros is
+-- NaN from everything under 'MetricCosine' and gets its answers ordered by id.
+graphSearchMetricSVHIP :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Metric -> Int -> Int
+                       -> (VS.Vector Int32, VS.Vector Int32) -> Int -> VS.Vector Int32 -> Int -> Int
+                       -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+graphSearchMetricSVHIP ctx ds qs m nq kg (gids, gcount) s seeds k ef = do
+  ids <- VSM.new (nq * k); dist <- VSM.new (nq * k); cnt <- VSM.new nq
+  VS.unsafeWith gids (\pg -> VS.unsafeWith gcount (\pc -> VS.unsafeWith seeds (\ps ->
+    VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
+      c_graph_search_csr_metric_host ctx ds qs (fromIntegral kg) pg pc (fromIntegral s) ps (fromIntegral k) (fromIntegral ef) (metricFlag m) 0 a b)))))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
 -- | A kNN graph made ready for 'graphSearchHIP' (rpt_graph_prepare_host), PyNNDescent's search graph.
 -- @diversify@: walking a row in stored order, a neighbour is dropped when an already kept neighbour
 -- of the row is nearer to it than the point itself is (a plain <; the pair distance is the metric's
@@ -419,6 +437,22 @@ graphPrepareSVHIP ctx ds n k kout diversify reverse (i0, d0, c0) = do
   VS.unsafeWith i0 (\pi -> VS.unsafeWith d0 (\pd -> VS.unsafeWith c0 (\pc ->
     VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
       c_graph_prepare_csr_host ctx ds (fromIntegral k) pi pd pc (fromIntegral kout) 0 flags a b)))))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | 'graphPrepareSVHIP' under another distance (rpt_graph_prepare_csr_metric_host): the pair distances
+-- of @diversify@ are 'MetricCosine' / 'MetricInner' over the indices both rows store, the metric the
+-- graph's stored distances must have been computed under ('knnGraphMetricSVHIP',
+-- 'knnGraphRefineMetricSVHIP'); 'MetricL2' gives 'graphPrepareSVHIP's bits.  Under 'MetricInner'
+-- @diversify@ costs recall.
+graphPrepareMetricSVHIP :: Ptr Ctx -> Ptr Dataset -> Metric -> Int -> Int -> Int -> Bool -> Bool
+                        -> (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+                        -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+graphPrepareMetricSVHIP ctx ds m n k kout diversify reverse (i0, d0, c0) = do
+  ids <- VSM.new (n * kout); dist <- VSM.new (n * kout); cnt <- VSM.new n
+  let flags = (if diversify then 1 else 0) + (if reverse then 2 else 0)
+  VS.unsafeWith i0 (\pi -> VS.unsafeWith d0 (\pd -> VS.unsafeWith c0 (\pc ->
+    VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
+      c_graph_prepare_csr_metric_host ctx ds (fromIntegral k) pi pd pc (fromIntegral kout) (metricFlag m) flags a b)))))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | SVector rows as a CSR dataset on the device (rpt_dataset_csr_host), for the extent of the

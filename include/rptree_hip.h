@@ -157,11 +157,13 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *   graph_search_nofilter (0 / 1)  graph search: no visited filter, only the beam itself is checked
  *                                  before a distance is computed (rpt_graph_search_*)
  *   graph_search_csr_stream (0 / 1)  graph search on CSR rows: every query passes through LDS in
- *                                  pieces, none stays resident (rpt_graph_search_csr_*)
+ *                                  pieces, none stays resident (rpt_graph_search_csr_*,
+ *                                  rpt_graph_search_csr_metric_*)
  *   graph_prepare_csr_resident (0, n, -1)  graph preparation on CSR rows: a point's neighbours are
  *                                  staged in LDS when they hold at most this many entries together
  *                                  (0 = the built-in cap of 1536, n > 0 = min(n, 1536), -1 = no point
- *                                  is resident; rpt_graph_prepare_csr_*)
+ *                                  is resident; rpt_graph_prepare_csr_*,
+ *                                  rpt_graph_prepare_csr_metric_*)
  *   brute_csr_tile (0 auto, n)     brute force over CSR rows: queries per workgroup (1, 2, 4 or 8; other
  *                                  values round down; halved while the tile does not fit LDS; auto
  *                                  takes up to 4)
@@ -613,8 +615,10 @@ int32_t rpt_knn_graph_refine_csr_host(rpt_ctx* ctx, const rpt_dataset* data, int
  * Everything else as rpt_knn_graph_csr_* / rpt_knn_graph_refine_csr_*; an error leaves the context
  * usable.  The graph under either metric (the inner product for the statistic alone) and the
  * refinement under cosine cache the rows' dotS(x, x) and their statistics on the data set, 8 bytes
- * per row, on their first call.  Not built: rpt_graph_search_csr_* and rpt_graph_prepare_csr_*
- * under a metric (RPT_E_UNSUPPORTED), streamed forests, the reference's right-fold innerSS order. */
+ * per row, on their first call.  Such a graph is prepared and searched by
+ * rpt_graph_prepare_csr_metric_* and rpt_graph_search_csr_metric_* (below); rpt_graph_search_csr_* and
+ * rpt_graph_prepare_csr_* themselves keep refusing a metric (RPT_E_UNSUPPORTED).  Not built:
+ * streamed forests, the reference's right-fold innerSS order. */
 int32_t rpt_knn_graph_csr_metric_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k,
                                      int32_t metric, int32_t flags, int32_t* ids_dev,
                                      double* dist_dev, int32_t* count_dev);
@@ -711,7 +715,8 @@ int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evalua
  *                seeds.  A query and a row without nonzeros are at distance 0.
  *   metric       must be 0.  RPT_KNN_METRIC_COSINE and RPT_KNN_METRIC_INNER: RPT_E_UNSUPPORTED (the
  *                parameter is there so that they need no new symbol); any other value, both bits
- *                together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG.
+ *                together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG.  The two distances are served by
+ *                rpt_graph_search_csr_metric_* (below), which the message names.
  *   The query in LDS  A candidate's row is merged against the query's (column, value) pairs.  A
  *                query of at most min(d, 2048) entries stays in LDS for its whole search; a longer
  *                one passes through LDS in pieces of 64 per offer.  The context option
@@ -818,7 +823,8 @@ int32_t rpt_graph_prepare_last(rpt_ctx* ctx, int64_t* pairs, int64_t* occluded, 
  *                same graph.  Two rows without nonzeros are at distance 0 (0 < 0 is false: kept).
  *   metric       must be 0.  RPT_KNN_METRIC_COSINE and RPT_KNN_METRIC_INNER: RPT_E_UNSUPPORTED (the
  *                parameter is there so that they need no new symbol); any other value, both bits
- *                together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG.
+ *                together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG.  The two distances are served by
+ *                rpt_graph_prepare_csr_metric_* (below), which the message names.
  *   The neighbours in LDS  A pair's distance is a two-pointer merge over the two rows' (column,
  *                value) pairs.  Every neighbour row takes part in c - 1 pairs, so a point whose
  *                neighbours hold at most 1536 entries together (12 bytes each: two workgroups of
@@ -843,6 +849,71 @@ int32_t rpt_graph_prepare_csr_host(rpt_ctx* ctx, const rpt_dataset* data, int32_
                                    const double* dist_host, const int32_t* count_host, int32_t kout,
                                    int32_t metric, int32_t flags, int32_t* out_ids_host, double* out_dist_host,
                                    int32_t* out_count_host);
+
+/* ---- query and prepare the kNN graph on SVector (CSR) rows, under cosine / inner product ----
+ * rpt_graph_search_csr_metric_* and rpt_graph_prepare_csr_metric_* are rpt_graph_search_csr_* and
+ * rpt_graph_prepare_csr_* with the same parameter lists, word for word (`metric` already stands before
+ * `flags`), and with `metric` honoured: 0, RPT_KNN_METRIC_COSINE or RPT_KNN_METRIC_INNER.  They
+ * prepare and search the graph that rpt_knn_graph_csr_metric_* / rpt_knn_graph_refine_csr_metric_*
+ * build.  Everything stated for the L2 entry points carries over word for word (the beam, the offers
+ * and the seeds, Kept(i) and its plain <, Union(i), the order (distance, id), counts and unused slots,
+ * termination after at most n expansions, _host validating before anything is uploaded, _dev skipping
+ * what is out of range, n = 0 / 1 and nq = 0, rpt_prof_* class 3, the options graph_search_nofilter,
+ * graph_search_csr_stream and graph_prepare_csr_resident, on none of which the answer depends);
+ * rpt_graph_search_last and rpt_graph_prepare_last serve these calls too.  The one thing that changes
+ * is the distance, and it is the definition rpt_knn_csr_metric_* and rpt_knn_graph_csr_metric_* use,
+ * word for word: dotS(x, y) starts at +0.0, takes the columns stored in BOTH rows in ascending
+ * column order and folds acc = acc + x_c * y_c, every product and sum rounded on its own, f32
+ * values widened exactly, no FMA.
+ *   metric == 0            the bits of rpt_graph_search_csr_* / rpt_graph_prepare_csr_*
+ *   RPT_KNN_METRIC_INNER   dist(x, y) = -dotS(x, y)
+ *   RPT_KNN_METRIC_COSINE  dist(x, y) = 1 - dotS(x, y) / (sqrt(dotS(x, x)) * sqrt(dotS(y, y))), the
+ *                          norms cached on the data set and, for the search, on the query set (8
+ *                          bytes per row, on the first call); an empty or all-zero row or query is
+ *                          at NaN from everything
+ * NaN ranks behind every number, NaNs among themselves by id, so a query without nonzeros under
+ * cosine still gets min(k, what the search reached) answers, ordered by id; -0.0 (the inner distance
+ * of two rows that share no column) ties with +0.0, the id decides and the stored bits are the
+ * computed ones.  In the preparation a NaN never occludes and is never occluded (a plain <).
+ *   The merge    For dotS the two-pointer merge of the L2 kernels is the definition itself: a product
+ *                is taken only where both cursors stand on one column, a step that advances one side
+ *                does no arithmetic, and the walk ends with the shorter row: no tail, no zero-filled
+ *                window, no presence word.
+ *   Stored inf and NaN  While every stored value is finite, the answers are those of
+ *                rpt_graph_search_* / rpt_graph_prepare_* under the same metric on the dense-ified
+ *                rows bit for bit (a column only one row stores would add x * (+0.0) = +-0.0 to an
+ *                accumulator that is never -0.0).  With a stored inf or NaN they are not: the dense
+ *                fold meets inf * 0 = NaN where dotS takes no product.  The answer is dotS in both
+ *                cases.
+ *   LDS          What the L2 kernels take.  The cosine preparation keeps the neighbours' norms in
+ *                registers (lane r: neighbour r) and fetches a pair's two by shuffle, so a workgroup
+ *                stays at 80 928 B at k = 64 and two share a CU.
+ *   Ascending columns  as above: unspecified answer, in bounds, terminates.
+ * Errors: any other `metric` value, both metric bits together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG
+ * (a metric bit in `flags` too).  Dense data: RPT_E_ARG, the message names rpt_graph_search_* /
+ * rpt_graph_prepare_*, which keep refusing CSR data (RPT_E_UNSUPPORTED).  Everything else as
+ * rpt_graph_search_csr_* / rpt_graph_prepare_csr_*; an error leaves the context usable.  Not built:
+ * streamed forests, the reference's right-fold innerSS order. */
+int32_t rpt_graph_search_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                        int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev,
+                                        int32_t s, const int32_t* seeds_dev, int32_t k, int32_t ef,
+                                        int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                                        int32_t* count_dev);
+int32_t rpt_graph_search_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                         int32_t kg, const int32_t* gids_host, const int32_t* gcount_host,
+                                         int32_t s, const int32_t* seeds_host, int32_t k, int32_t ef,
+                                         int32_t metric, int32_t flags, int32_t* ids_host, double* dist_host,
+                                         int32_t* count_host);
+int32_t rpt_graph_prepare_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                         const int32_t* ids_dev, const double* dist_dev,
+                                         const int32_t* count_dev, int32_t kout, int32_t metric,
+                                         int32_t flags, int32_t* out_ids_dev, double* out_dist_dev,
+                                         int32_t* out_count_dev);
+int32_t rpt_graph_prepare_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                          const int32_t* ids_host, const double* dist_host,
+                                          const int32_t* count_host, int32_t kout, int32_t metric,
+                                          int32_t flags, int32_t* out_ids_host, double* out_dist_host,
+                                          int32_t* out_count_host);
 
 /* multi-GPU merge: G per-shard results (shard g holds trees [g*T/G, (g+1)*T/G)), gathered
  * shard-major as ids_dev[G][nq][k] etc. (e.g. by an RCCL all-gather), merged into the

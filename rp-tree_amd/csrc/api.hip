@@ -1463,18 +1463,25 @@ int32_t rpt_knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* update
 
 // ---- beam search over a kNN graph -------------------------------------------------------------
 namespace {
-// csr: the rpt_graph_search_csr_* entry points (CSR data and queries, L2 only)
+// csr: the rpt_graph_search_csr_* entry points (CSR data and queries, L2 only); csr_metric: the
+// rpt_graph_search_csr_metric_* ones (the same, under every metric)
 int32_t check_search(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
-                     int32_t s, int32_t k, int32_t ef, int32_t metric, int32_t flags, bool csr = false) {
+                     int32_t s, int32_t k, int32_t ef, int32_t metric, int32_t flags, bool csr = false,
+                     bool csr_metric = false) {
   RPT_ARG(ctx && data && queries, "NULL argument");
   RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
   RPT_TRY(check_graph_metric(metric));
-  if (csr && metric != 0)
-    return fail(RPT_E_UNSUPPORTED, "the graph search on CSR rows is built under metricL2 only (metric must be 0)");
+  if (csr && !csr_metric && metric != 0)
+    return fail(RPT_E_UNSUPPORTED, "the graph search on CSR rows is built under metricL2 only (metric must be 0) "
+                                   "by rpt_graph_search_csr_*; cosine / inner product: rpt_graph_search_csr_metric_*");
   RPT_ARG(flags == 0, "flags must be 0");
   RPT_ARG(data->csr == queries->csr, "data and queries must both be dense or both CSR");
-  if (csr) RPT_ARG(data->csr, "rpt_graph_search_csr_* takes CSR data only (dense rows: rpt_graph_search_*)");
-  else if (data->csr) return fail(RPT_E_UNSUPPORTED, "the graph search takes dense data only (not CSR rows)");
+  if (csr_metric)
+    RPT_ARG(data->csr, "rpt_graph_search_csr_metric_* takes CSR data only (dense rows: rpt_graph_search_*)");
+  else if (csr) RPT_ARG(data->csr, "rpt_graph_search_csr_* takes CSR data only (dense rows: rpt_graph_search_*)");
+  else if (data->csr)
+    return fail(RPT_E_UNSUPPORTED, "the graph search takes dense data only (not CSR rows: rpt_graph_search_csr_*, "
+                                   "rpt_graph_search_csr_metric_*)");
   RPT_ARG(data->d == queries->d && data->dtype == queries->dtype,
           "queries differ from the data set in d or dtype");
   RPT_ARG(kg >= 1 && kg <= RPT_GRAPH_MAX_K, "kg must be in [1,64] (RPT_GRAPH_MAX_K)");
@@ -1514,15 +1521,15 @@ int32_t check_search_arrays(int64_t n, int64_t nq, int32_t kg, const int32_t* gi
 int32_t search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
                    const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s, const int32_t* seeds_dev,
                    int32_t k, int32_t ef, int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
-                   int32_t* count_dev, bool csr) {
+                   int32_t* count_dev, bool csr, bool csr_metric = false) {
   if (ctx) dev_set_stream(ctx->stream);
-  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, csr));
+  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, csr, csr_metric));
   RPT_ARG(data->n == 0 || (gids_dev && gcount_dev), "NULL graph arrays");
   RPT_ARG(queries->n == 0 || (seeds_dev && ids_dev && dist_dev && count_dev), "NULL seeds or output");
   RPT_HIP(hipSetDevice(ctx->device));
   if (csr)
-    return graph_search_csr_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, ids_dev,
-                                dist_dev, count_dev);
+    return graph_search_csr_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric,
+                                ids_dev, dist_dev, count_dev);
   return graph_search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric,
                           ids_dev, dist_dev, count_dev);
 }
@@ -1530,9 +1537,10 @@ int32_t search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* que
 int32_t search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
                     const int32_t* gids_host, const int32_t* gcount_host, int32_t s,
                     const int32_t* seeds_host, int32_t k, int32_t ef, int32_t metric, int32_t flags,
-                    int32_t* ids_host, double* dist_host, int32_t* count_host, bool csr) {
+                    int32_t* ids_host, double* dist_host, int32_t* count_host, bool csr,
+                    bool csr_metric = false) {
   if (ctx) dev_set_stream(ctx->stream);
-  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, csr));
+  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, csr, csr_metric));
   const int64_t n = data->n, nq = queries->n;
   RPT_ARG(n == 0 || (gids_host && gcount_host), "NULL graph arrays");
   RPT_ARG(nq == 0 || (seeds_host && ids_host && dist_host && count_host), "NULL seeds or output");
@@ -1552,8 +1560,8 @@ int32_t search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* qu
   }
   if (nq) RPT_HIP(hipMemcpy(seeds.p, seeds_host, (size_t)nq * s * 4, hipMemcpyHostToDevice));
   if (csr)
-    RPT_TRY(graph_search_csr_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, ids.p, dist.p,
-                                 cnt.p));
+    RPT_TRY(graph_search_csr_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, metric, ids.p,
+                                 dist.p, cnt.p));
   else
     RPT_TRY(graph_search_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, metric, ids.p,
                              dist.p, cnt.p));
@@ -1609,6 +1617,28 @@ int32_t rpt_graph_search_csr_host(rpt_ctx* ctx, const rpt_dataset* data, const r
   });
 }
 
+int32_t rpt_graph_search_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                        int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev,
+                                        int32_t s, const int32_t* seeds_dev, int32_t k, int32_t ef,
+                                        int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                                        int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    return search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric, flags,
+                      ids_dev, dist_dev, count_dev, true, true);
+  });
+}
+
+int32_t rpt_graph_search_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                         int32_t kg, const int32_t* gids_host, const int32_t* gcount_host,
+                                         int32_t s, const int32_t* seeds_host, int32_t k, int32_t ef,
+                                         int32_t metric, int32_t flags, int32_t* ids_host, double* dist_host,
+                                         int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return search_host(ctx, data, queries, kg, gids_host, gcount_host, s, seeds_host, k, ef, metric, flags,
+                       ids_host, dist_host, count_host, true, true);
+  });
+}
+
 int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated) {
   return guarded([&]() -> int32_t {
     if (ctx) dev_set_stream(ctx->stream);
@@ -1620,19 +1650,25 @@ int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evalua
 
 // ---- a kNN graph made ready for the search -------------------------------------------------------
 namespace {
-// csr: the rpt_graph_prepare_csr_* entry points (CSR data, L2 only)
+// csr: the rpt_graph_prepare_csr_* entry points (CSR data, L2 only); csr_metric: the
+// rpt_graph_prepare_csr_metric_* ones (the same, under every metric)
 int32_t check_prepare(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t kout, int32_t metric,
-                      int32_t flags, bool csr = false) {
+                      int32_t flags, bool csr = false, bool csr_metric = false) {
   RPT_ARG(ctx && data, "NULL argument");
   RPT_ARG(data->ctx == ctx, "handles belong to another context");
   RPT_TRY(check_graph_metric(metric));
-  if (csr && metric != 0)
+  if (csr && !csr_metric && metric != 0)
     return fail(RPT_E_UNSUPPORTED,
-                "the graph preparation on CSR rows is built under metricL2 only (metric must be 0)");
+                "the graph preparation on CSR rows is built under metricL2 only (metric must be 0) by "
+                "rpt_graph_prepare_csr_*; cosine / inner product: rpt_graph_prepare_csr_metric_*");
   RPT_ARG((flags & ~(RPT_GRAPH_PREP_DIVERSIFY | RPT_GRAPH_PREP_REVERSE)) == 0,
           "flags must be an or of RPT_GRAPH_PREP_DIVERSIFY and RPT_GRAPH_PREP_REVERSE");
-  if (csr) RPT_ARG(data->csr, "rpt_graph_prepare_csr_* takes CSR data only (dense rows: rpt_graph_prepare_*)");
-  else if (data->csr) return fail(RPT_E_UNSUPPORTED, "the graph preparation takes dense data only (not CSR rows)");
+  if (csr_metric)
+    RPT_ARG(data->csr, "rpt_graph_prepare_csr_metric_* takes CSR data only (dense rows: rpt_graph_prepare_*)");
+  else if (csr) RPT_ARG(data->csr, "rpt_graph_prepare_csr_* takes CSR data only (dense rows: rpt_graph_prepare_*)");
+  else if (data->csr)
+    return fail(RPT_E_UNSUPPORTED, "the graph preparation takes dense data only (not CSR rows: "
+                                   "rpt_graph_prepare_csr_*, rpt_graph_prepare_csr_metric_*)");
   RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
   RPT_ARG(kout >= 1 && kout <= RPT_GRAPH_MAX_K, "kout must be in [1,64] (RPT_GRAPH_MAX_K)");
   RPT_ARG(data->n <= 0x7fffffff, "graph too large");
@@ -1642,9 +1678,9 @@ int32_t check_prepare(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t 
 int32_t prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
                     const double* dist_dev, const int32_t* count_dev, int32_t kout, int32_t metric,
                     int32_t flags, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev,
-                    bool csr) {
+                    bool csr, bool csr_metric = false) {
   if (ctx) dev_set_stream(ctx->stream);
-  RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags, csr));
+  RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags, csr, csr_metric));
   RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
   RPT_ARG(data->n == 0 || (out_ids_dev && out_dist_dev && out_count_dev), "NULL output");
   RPT_HIP(hipSetDevice(ctx->device));
@@ -1655,9 +1691,9 @@ int32_t prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int3
 int32_t prepare_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_host,
                      const double* dist_host, const int32_t* count_host, int32_t kout, int32_t metric,
                      int32_t flags, int32_t* out_ids_host, double* out_dist_host, int32_t* out_count_host,
-                     bool csr) {
+                     bool csr, bool csr_metric = false) {
   if (ctx) dev_set_stream(ctx->stream);
-  RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags, csr));
+  RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags, csr, csr_metric));
   const int64_t n = data->n;
   RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
   RPT_ARG(n == 0 || (out_ids_host && out_dist_host && out_count_host), "NULL output");
@@ -1724,6 +1760,28 @@ int32_t rpt_graph_prepare_csr_host(rpt_ctx* ctx, const rpt_dataset* data, int32_
   return guarded([&]() -> int32_t {
     return prepare_host(ctx, data, k, ids_host, dist_host, count_host, kout, metric, flags, out_ids_host,
                         out_dist_host, out_count_host, true);
+  });
+}
+
+int32_t rpt_graph_prepare_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                         const int32_t* ids_dev, const double* dist_dev,
+                                         const int32_t* count_dev, int32_t kout, int32_t metric,
+                                         int32_t flags, int32_t* out_ids_dev, double* out_dist_dev,
+                                         int32_t* out_count_dev) {
+  return guarded([&]() -> int32_t {
+    return prepare_dev(ctx, data, k, ids_dev, dist_dev, count_dev, kout, metric, flags, out_ids_dev,
+                       out_dist_dev, out_count_dev, true, true);
+  });
+}
+
+int32_t rpt_graph_prepare_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
+                                          const int32_t* ids_host, const double* dist_host,
+                                          const int32_t* count_host, int32_t kout, int32_t metric,
+                                          int32_t flags, int32_t* out_ids_host, double* out_dist_host,
+                                          int32_t* out_count_host) {
+  return guarded([&]() -> int32_t {
+    return prepare_host(ctx, data, k, ids_host, dist_host, count_host, kout, metric, flags, out_ids_host,
+                        out_dist_host, out_count_host, true, true);
   });
 }
 

@@ -459,18 +459,19 @@ int32_t graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
                          const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
                          const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
                          int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
-// the same on CSR rows under L2 (graph_search_csr.hip): CSR data and queries of one d and dtype (f64
-// or f32 values); the statistics go where graph_search_dev's go
+// the same on CSR rows (graph_search_csr.hip): CSR data and queries of one d and dtype (f64 or f32
+// values); metric as knn_graph_dev's, the cosine / inner-product distances from dotS (rptree_hip.h);
+// the statistics go where graph_search_dev's go
 int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
                              int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
-                             const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t* ids_dev,
-                             double* dist_dev, int32_t* count_dev);
+                             const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
+                             int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
 // synchronises the stream
 int32_t graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
 // ---- a kNN graph made ready for the search (graph_prepare.hip) ---------------------------------
 // arguments checked by the caller (k and kout <= 64, flags an or of RPT_GRAPH_PREP_DIVERSIFY /
-// _REVERSE; metric as knn_graph_dev's, 0 for CSR data: rows of f64 or f32 values, which take
-// graph_diversify_csr_kernel); the input arrays are read only and not validated: entries out of
+// _REVERSE; metric as knn_graph_dev's; CSR data: rows of f64 or f32 values, which take
+// graph_diversify_csr_kernel, the cosine / inner-product distances from dotS); the input arrays are read only and not validated: entries out of
 // range are skipped; enqueued on the ctx stream
 int32_t graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
                           const double* dist_dev, const int32_t* count_dev, int32_t kout, int32_t metric,

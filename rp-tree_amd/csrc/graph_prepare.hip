@@ -1,5 +1,6 @@
 // graph_prepare.hip — a kNN graph made ready for the search (rpt_graph_prepare_* on dense rows,
-// rpt_graph_prepare_csr_* on SVector rows under L2): occluded
+// rpt_graph_prepare_csr_* on SVector rows under L2, rpt_graph_prepare_csr_metric_* on SVector rows
+// under cosine / inner product): occluded
 // neighbours dropped (DIVERSIFY), reverse edges added (REVERSE), the degree capped at kout.
 //
 // Kept(i): the valid entries of row i; with DIVERSIFY, in stored order, e_m stays unless a kept
@@ -33,6 +34,11 @@
 //                          values are widened once); any other point's lanes walk their two rows
 //                          through global loads.  The choice is per point and wave-uniform, both paths
 //                          fold the same entries in the same order.
+//                          Under cosine / inner product (rpt_graph_prepare_csr_metric_*, M != kGraphL2)
+//                          the distance of a pair comes from dotS (rptree_hip.h): a step folds only
+//                          where both cursors stand on one column, and the walk ends with the shorter
+//                          row.  Cosine takes the two neighbours' dotS(x, x) from a register of lane r
+//                          (neighbour r) by two shuffles per pair: no LDS is added (kResCap below).
 //   rev_zero / _degree / _scan / _fill (REVERSE; graph_dev.h) the CSR of the reverse edges of Kept
 //   prep_merge_kernel      one wave per point holds the output row one entry per lane: Kept(i)
 //                          enters it (as it stands when it is sorted, else through wave_merge), then
@@ -234,6 +240,11 @@ constexpr int kNoCol = 0x7fffffff;  // a cursor at its row's end (a column is be
 // 74 752 B at k = 10).  The C3 point (k = 10, rows of 784 x 0.19 = 149 entries: 1 490 +- 35 per point
 // if the neighbours were average rows) lies below the cap; measured there, neighbours are short
 // rows, 1 245 entries per point on average and 1 404 at the most.
+// Cosine needs dot(x, x) of the two neighbours of every pair.  k more doubles per wave would make the
+// workgroup 80 928 + 4 x 512 = 82 976 B at k = 64, above the 81 920 B that two workgroups per CU may
+// take each, and halve the occupancy.  So the norms stay out of LDS: lane r holds neighbour r's in a
+// register and a pair fetches its two with __shfl.  The cosine kernel's workgroup is the L2 kernel's:
+// 4 x ((1 536 + 2 x 64 + 33) x 8 + (1 536 + 2 x 64) x 4) = 4 x 20 232 = 80 928 B at k = 64.
 constexpr int kResCap = 1536;
 
 // where the rows of a pair are read: the entries staged in the wave's LDS, or the data set.
@@ -266,10 +277,51 @@ struct GlobalRows {
 //           entry 0, which exists whenever the loop runs, and its value is not used
 //   global  the entries are carried in registers and only a side that moved loads its next one (32.8
 //           against 44.0 ms: reading both every step doubles the loads)
-template <class R, class I>
+// Cosine / inner product (M != kGraphL2): dotS of the two rows.  The same steps, but only a step
+// that takes both sides folds, and the loop runs while both cursors are live: no tail, no entry 0 read
+// for a finished cursor.
+template <int M, class R, class I>
 __device__ __forceinline__ double pair_fold(const R& r, I ap, I ae, I bp, I be) {
   double acc = 0.0;
-  if constexpr (R::kReadBoth) {
+  if constexpr (M != kGraphL2 && R::kReadBoth) {
+    while (ap < ae && bp < be) {
+      const int ca = r.col(ap), cb = r.col(bp);
+      const double va = r.val(ap), vb = r.val(bp);
+      const bool take_a = ca <= cb, take_b = cb <= ca;
+      if (take_a && take_b) acc = fold_step<M>(acc, va, vb);
+      ap += take_a ? 1 : 0;
+      bp += take_b ? 1 : 0;
+    }
+  } else if constexpr (M != kGraphL2) {
+    int ca = kNoCol, cb = kNoCol;
+    double va = 0.0, vb = 0.0;
+    if (ap < ae) {
+      ca = r.col(ap);
+      va = r.val(ap);
+    }
+    if (bp < be) {
+      cb = r.col(bp);
+      vb = r.val(bp);
+    }
+    while (ap < ae && bp < be) {
+      const bool take_a = ca <= cb, take_b = cb <= ca;
+      if (take_a && take_b) acc = fold_step<M>(acc, va, vb);
+      if (take_a) {
+        ++ap;
+        if (ap < ae) {
+          ca = r.col(ap);
+          va = r.val(ap);
+        }
+      }
+      if (take_b) {
+        ++bp;
+        if (bp < be) {
+          cb = r.col(bp);
+          vb = r.val(bp);
+        }
+      }
+    }
+  } else if constexpr (R::kReadBoth) {
     while (ap < ae || bp < be) {
       const bool ha = ap < ae, hb = bp < be;
       const I ia = ha ? ap : (I)0, ib = hb ? bp : (I)0;
@@ -318,14 +370,15 @@ __device__ __forceinline__ double pair_fold(const R& r, I ap, I ae, I bp, I be) 
 
 // dynamic LDS, per wave (wave_bytes): cap doubles (staged values), k doubles (stored distances), k
 // 64-bit row positions (into the staged entries when the point is resident, else into col / val),
-// NA + 1 words (the ballots), cap ints (staged columns), k ints (ids), k ints (row lengths)
-template <class TV, int NA>
+// NA + 1 words (the ballots), cap ints (staged columns), k ints (ids), k ints (row lengths).
+// rn: dot(x, x) of the data rows (cosine; kept in registers, not in LDS)
+template <class TV, int M, int NA>
 __global__ __launch_bounds__(256) void graph_diversify_csr_kernel(
     PrepState* st, const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
     const TV* __restrict__ val, int64_t n, int k, int cap, int wave_bytes,
     const int32_t* __restrict__ ids, const double* __restrict__ dist,
     const int32_t* __restrict__ count, int32_t* __restrict__ kids, double* __restrict__ kdist,
-    int32_t* __restrict__ kcount) {
+    int32_t* __restrict__ kcount, const double* __restrict__ rn) {
   extern __shared__ double smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
   double* ev = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + (size_t)wave * wave_bytes);
@@ -359,8 +412,10 @@ __global__ __launch_bounds__(256) void graph_diversify_csr_kernel(
       // cap + 1, so that the sum fits an int) places the rows in the staged entries
       long long rb = 0;
       int len = 0;
+      double nrm = 0.0;  // lane r: dot(x, x) of the r-th neighbour (cosine)
       if (lane < cc) {
         const int v = sid[lane];
+        if constexpr (M == kGraphCosine) nrm = rn[v];
         rb = rowptr[v];
         const long long l64 = rowptr[v + 1] - rb;
         len = l64 < 0 ? 0 : (l64 > (long long)kNoCol ? kNoCol : (int)l64);
@@ -398,13 +453,18 @@ __global__ __launch_bounds__(256) void graph_diversify_csr_kernel(
           pair_of(p, l, m);
           if (resident) {
             const int pa = (int)pos[l], pb = (int)pos[m];
-            acc = pair_fold(LdsRows{ec, ev}, pa, pa + rl[l], pb, pb + rl[m]);
+            acc = pair_fold<M>(LdsRows{ec, ev}, pa, pa + rl[l], pb, pb + rl[m]);
           } else {
             const long long pa = pos[l], pb = pos[m];
-            acc = pair_fold(GlobalRows<TV>{col, val}, pa, pa + rl[l], pb, pb + rl[m]);
+            acc = pair_fold<M>(GlobalRows<TV>{col, val}, pa, pa + rl[l], pb, pb + rl[m]);
           }
         }
-        const bool occ = p < P && fold_finish<kGraphL2>(acc, 0.0, 0.0) < sd[m];
+        double n_l = 0.0, n_m = 0.0;
+        if constexpr (M == kGraphCosine) {  // by all 64 lanes; a pair behind P asks for lane 0 twice
+          n_l = __shfl(nrm, l);
+          n_m = __shfl(nrm, m);
+        }
+        const bool occ = p < P && fold_finish<M>(acc, n_l, n_m) < sd[m];
         const unsigned long long b = __ballot(occ);
         if (lane == 0) bal[a] = b;
       }
@@ -547,32 +607,41 @@ int32_t launch_diversify_metric(int m, int na, const DivArgs& a) {
   return launch_diversify_na<TD, kGraphL2>(na, a);
 }
 
-template <class TV, int NA>
+template <class TV, int M, int NA>
 int32_t launch_diversify_csr(const DivArgs& a) {
   static DeviceOnce attr_once;
   RPT_TRY(attr_once.run(a.ctx->device, [&]() -> int32_t {
-    RPT_HIP(hipFuncSetAttribute((const void*)graph_diversify_csr_kernel<TV, NA>,
+    RPT_HIP(hipFuncSetAttribute((const void*)graph_diversify_csr_kernel<TV, M, NA>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
     return RPT_OK;
   }));
   constexpr int W = 4;
   const int64_t want = (a.data->n + W - 1) / W;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)a.ctx->n_cu * 16));
-  hipLaunchKernelGGL((graph_diversify_csr_kernel<TV, NA>), dim3(grid), dim3(64 * W), (size_t)a.wave_bytes * W,
+  hipLaunchKernelGGL((graph_diversify_csr_kernel<TV, M, NA>), dim3(grid), dim3(64 * W), (size_t)a.wave_bytes * W,
                      a.ctx->stream, a.st, a.data->rowptr, a.data->col, static_cast<const TV*>(a.data->val),
-                     a.data->n, a.k, a.cap, a.wave_bytes, a.ids, a.dist, a.count, a.kids, a.kdist, a.kcount);
+                     a.data->n, a.k, a.cap, a.wave_bytes, a.ids, a.dist, a.count, a.kids, a.kdist, a.kcount,
+                     M == kGraphCosine ? a.data->sqnorm : nullptr);
   return RPT_OK;
 }
 
+// the distance of a launch: the kernel is instantiated per value type, metric and accumulator count
+template <class TV, int NA>
+int32_t launch_diversify_csr_metric(int m, const DivArgs& a) {
+  if (m == kGraphCosine) return launch_diversify_csr<TV, kGraphCosine, NA>(a);
+  if (m == kGraphInner) return launch_diversify_csr<TV, kGraphInner, NA>(a);
+  return launch_diversify_csr<TV, kGraphL2, NA>(a);
+}
+
 template <class TV>
-int32_t launch_diversify_csr_na(int na, const DivArgs& a) {
+int32_t launch_diversify_csr_na(int m, int na, const DivArgs& a) {
   switch (na) {
-    case 1: return launch_diversify_csr<TV, 1>(a);
-    case 2: return launch_diversify_csr<TV, 2>(a);
-    case 4: return launch_diversify_csr<TV, 4>(a);
-    case 8: return launch_diversify_csr<TV, 8>(a);
-    case 16: return launch_diversify_csr<TV, 16>(a);
-    default: return launch_diversify_csr<TV, 32>(a);
+    case 1: return launch_diversify_csr_metric<TV, 1>(m, a);
+    case 2: return launch_diversify_csr_metric<TV, 2>(m, a);
+    case 4: return launch_diversify_csr_metric<TV, 4>(m, a);
+    case 8: return launch_diversify_csr_metric<TV, 8>(m, a);
+    case 16: return launch_diversify_csr_metric<TV, 16>(m, a);
+    default: return launch_diversify_csr_metric<TV, 32>(m, a);
   }
 }
 
@@ -630,8 +699,8 @@ int32_t graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, cons
     if (diversify) {
       const DivArgs a{ctx, st, data, k, wave_bytes, cap, ids_dev, count_dev, dist_dev, kids.p, kcount.p, kdist.p};
       if (data->csr) {
-        if (data->dtype == RPT_F64) RPT_TRY(launch_diversify_csr_na<double>(na, a));
-        else RPT_TRY(launch_diversify_csr_na<float>(na, a));
+        if (data->dtype == RPT_F64) RPT_TRY(launch_diversify_csr_na<double>(m, na, a));
+        else RPT_TRY(launch_diversify_csr_na<float>(m, na, a));
       } else {
         switch (data->dtype) {
           case RPT_F64: RPT_TRY(launch_diversify_metric<double>(m, na, a)); break;

@@ -1,5 +1,5 @@
 // graph_search_csr.hip — the beam search over a kNN graph on SVector (CSR) rows under L2
-// (rpt_graph_search_csr_*).
+// (rpt_graph_search_csr_*) and under cosine / inner product (rpt_graph_search_csr_metric_*).
 //
 // The answer is the definition of include/rptree_hip.h for rpt_graph_search_* with dist(q, v) =
 // metricDDL2's left fold over dense(q), dense(x_v) (graph_csr.hip: absent columns +0.0, f32 values
@@ -24,6 +24,14 @@
 // same entries in the same order.
 // Rows whose columns do not ascend strictly give an unspecified answer; a cursor never passes its
 // row's end and every step of a walk advances one, so the kernel stays in bounds and terminates.
+//
+// Cosine / inner product (M != kGraphL2): the distance comes from dotS (rptree_hip.h), the left fold
+// of x_c * y_c over the columns stored in BOTH rows, which is what the two-pointer walk meets when
+// both cursors stand on one column.  So a step folds only then, a step that advances one side does no
+// arithmetic, a lane stops when its candidate row or the query's entries are over, and there is no
+// tail.  No zero stands in for an absent entry: a stored inf or NaN meets only what the other row
+// stores.  Cosine reads dotS(q, q) once per query and dotS(x_v, x_v) in the epilogue, both from
+// rpt_dataset::sqnorm (the same fold), as graph_search.hip does; LDS is what the L2 kernel takes.
 #include <algorithm>
 
 #include "graph_dev.h"
@@ -46,11 +54,29 @@ struct RowWalk {
   double vj;
 };
 
-// folds the query entries pc/pv[0 .. np) and what the candidate holds up to the last of them
-template <class TV>
+// L2: folds the query entries pc/pv[0 .. np) and what the candidate holds up to the last of them.
+// Cosine / inner product: folds the columns that pc[0 .. np) and the candidate both hold, and stops
+// at the end of either.
+template <class TV, int M>
 __device__ __forceinline__ double merge_piece(double acc, const int* pc, const double* pv, int np, RowWalk& w,
                                               const int32_t* __restrict__ col, const TV* __restrict__ val) {
   int ii = 0;
+  if constexpr (M != kGraphL2) {
+    while (ii < np && w.jp < w.je) {  // every step advances the query, the candidate or both
+      const int ci = pc[ii];
+      const bool take_q = ci <= w.cj, take_j = w.cj <= ci;
+      if (take_q && take_j) acc = fold_step<M>(acc, pv[ii], w.vj);
+      if (take_q) ++ii;
+      if (take_j) {
+        ++w.jp;
+        if (w.jp < w.je) {
+          w.cj = col[w.jp];
+          w.vj = widen(val[w.jp]);
+        }
+      }
+    }
+    return acc;
+  }
   while (ii < np) {  // every step takes an entry of the query or of the candidate
     const int ci = pc[ii];
     const bool take_q = ci <= w.cj, take_j = w.cj <= ci;
@@ -68,7 +94,7 @@ __device__ __forceinline__ double merge_piece(double acc, const int* pc, const d
   return acc;
 }
 
-template <class TV>
+template <class TV, int M>
 __global__ __launch_bounds__(256) void graph_search_csr_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const TV* __restrict__ val,
     const int64_t* __restrict__ qrowptr, const int32_t* __restrict__ qcol, const TV* __restrict__ qval,
@@ -98,6 +124,8 @@ __global__ __launch_bounds__(256) void graph_search_csr_kernel(
     if (filter)
       for (int p = lane; p < a.H; p += 64) tab[p] = kEmpty;
     wave_sync();
+    double qnorm = 0.0;
+    if constexpr (M == kGraphCosine) qnorm = a.qn[qi];
 
     int c = 0;  // entries of the beam
     int s0 = 0;
@@ -124,9 +152,12 @@ __global__ __launch_bounds__(256) void graph_search_csr_kernel(
       }
       double acc = 0.0;
       if (resident) {
-        if (my >= 0) acc = merge_piece<TV>(acc, qc, qv, (int)(qe - qb), w, col, val);
+        if (my >= 0) acc = merge_piece<TV, M>(acc, qc, qv, (int)(qe - qb), w, col, val);
       } else {
         for (int64_t p0 = qb; p0 < qe; p0 += kPiece) {
+          if constexpr (M != kGraphL2) {  // wave-uniform: every candidate row of the offer is over
+            if (!__ballot(w.jp < w.je)) break;
+          }
           const int np = qe - p0 < kPiece ? (int)(qe - p0) : kPiece;
           wave_sync();  // the last piece has been read
           if (lane < np) {
@@ -134,15 +165,19 @@ __global__ __launch_bounds__(256) void graph_search_csr_kernel(
             qv[lane] = widen(qval[p0 + lane]);
           }
           wave_sync();
-          if (my >= 0) acc = merge_piece<TV>(acc, qc, qv, np, w, col, val);
+          if (my >= 0) acc = merge_piece<TV, M>(acc, qc, qv, np, w, col, val);
         }
       }
-      while (w.jp < w.je) {  // what the candidate holds behind the query's last column
-        acc = fold_step<kGraphL2>(acc, 0.0, w.vj);
-        ++w.jp;
-        if (w.jp < w.je) w.vj = widen(val[w.jp]);
+      if constexpr (M == kGraphL2) {
+        while (w.jp < w.je) {  // what the candidate holds behind the query's last column
+          acc = fold_step<kGraphL2>(acc, 0.0, w.vj);
+          ++w.jp;
+          if (w.jp < w.je) w.vj = widen(val[w.jp]);
+        }
       }
-      const double cd = fold_finish<kGraphL2>(acc, 0.0, 0.0);
+      double nrm = 0.0;
+      if constexpr (M == kGraphCosine) nrm = my >= 0 ? a.rn[my] : 0.0;
+      const double cd = fold_finish<M>(acc, qnorm, nrm);
 
       // ---- into the beam, one at a time, by the order of before()
       beam_insert(bd, bi, c, ef, nj, lane, nrows, cd, my);
@@ -156,31 +191,44 @@ __global__ __launch_bounds__(256) void graph_search_csr_kernel(
   }
 }
 
-template <class TV>
+template <class TV, int M>
 int32_t launch_search_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
                           const SearchArgs& a) {
   static DeviceOnce attr_once;
   RPT_TRY(attr_once.run(ctx->device, [&]() -> int32_t {
-    RPT_HIP(hipFuncSetAttribute((const void*)graph_search_csr_kernel<TV>,
+    RPT_HIP(hipFuncSetAttribute((const void*)graph_search_csr_kernel<TV, M>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
     return RPT_OK;
   }));
   const int W = 4;
   const int64_t want = (a.nq + W - 1) / W;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)ctx->n_cu * 64));
-  hipLaunchKernelGGL((graph_search_csr_kernel<TV>), dim3(grid), dim3(64 * W), (size_t)a.wave_bytes * W,
+  hipLaunchKernelGGL((graph_search_csr_kernel<TV, M>), dim3(grid), dim3(64 * W), (size_t)a.wave_bytes * W,
                      ctx->stream, data->rowptr, data->col, static_cast<const TV*>(data->val),
                      queries->rowptr, queries->col, static_cast<const TV*>(queries->val), a);
   RPT_HIP(hipGetLastError());
   return RPT_OK;
 }
 
+template <class TV>
+int32_t launch_search_csr_metric(int m, rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                 const SearchArgs& a) {
+  if (m == kGraphCosine) return launch_search_csr<TV, kGraphCosine>(ctx, data, queries, a);
+  if (m == kGraphInner) return launch_search_csr<TV, kGraphInner>(ctx, data, queries, a);
+  return launch_search_csr<TV, kGraphL2>(ctx, data, queries, a);
+}
+
 }  // namespace
 
 int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
                              int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
-                             const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t* ids_dev,
-                             double* dist_dev, int32_t* count_dev) {
+                             const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
+                             int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  const int m = graph_metric_of(metric);
+  if (m == kGraphCosine) {  // the rows' dotS(x, x), cached on the two datasets
+    RPT_TRY(ensure_sqnorm(ctx, data));
+    RPT_TRY(ensure_sqnorm(ctx, queries));
+  }
   SearchArgs a = {};
   a.n = data->n;
   a.nq = queries->n;
@@ -209,6 +257,8 @@ int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_da
   a.gids = gids_dev;
   a.gcount = gcount_dev;
   a.seeds = seeds_dev;
+  a.rn = m == kGraphCosine ? data->sqnorm : nullptr;
+  a.qn = m == kGraphCosine ? queries->sqnorm : nullptr;
   a.ids = ids_dev;
   a.dist = dist_dev;
   a.count = count_dev;
@@ -218,8 +268,8 @@ int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_da
   hipLaunchKernelGGL(search_begin_kernel, dim3(1), dim3(64), 0, ctx->stream, a.st);
   RPT_HIP(hipGetLastError());
   if (a.nq == 0) return RPT_OK;
-  if (data->dtype == RPT_F64) return launch_search_csr<double>(ctx, data, queries, a);
-  return launch_search_csr<float>(ctx, data, queries, a);
+  if (data->dtype == RPT_F64) return launch_search_csr_metric<double>(m, ctx, data, queries, a);
+  return launch_search_csr_metric<float>(m, ctx, data, queries, a);
 }
 
 }  // namespace rpt

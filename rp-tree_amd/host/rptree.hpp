@@ -614,6 +614,23 @@ inline GraphResult graphPrepareSV(const RPForest& tts, const GraphResult& g, int
   return graphPrepareSV(*tts.ctx, *tts.data, g, kout, diversify, reverse, stats);
 }
 
+// graphPrepareSV under another distance (rpt_graph_prepare_csr_metric_host): Metric::Cosine /
+// Metric::Inner over the indices both rows store, as knnGraphSV(tts, k, metric) defines them, which
+// must be the metric the graph's distances were computed under; Metric::L2 gives graphPrepareSV's
+// bits.  While every stored value is finite that is graphPrepare(ctx, data, g, metric, ...) on the
+// dense-ified rows bit for bit.  Under Metric::Inner diversify costs recall.
+inline GraphResult graphPrepareSV(Context& ctx, const Dataset& data, const GraphResult& g, Metric metric,
+                                  int kout = -1, bool diversify = true, bool reverse = true,
+                                  PrepareStats* stats = nullptr) {
+  return graphPrepareVia(rpt_graph_prepare_csr_metric_host, "graphPrepareSV", ctx, data, g, metric_flags(metric),
+                         kout, diversify, reverse, stats);
+}
+// ... over the data set of a forest
+inline GraphResult graphPrepareSV(const RPForest& tts, const GraphResult& g, Metric metric, int kout = -1,
+                                  bool diversify = true, bool reverse = true, PrepareStats* stats = nullptr) {
+  return graphPrepareSV(*tts.ctx, *tts.data, g, metric, kout, diversify, reverse, stats);
+}
+
 // Query a kNN graph: best-first beam search (rpt_graph_search_host).  g: a graph over `data`
 // (knnGraph's, knnGraphRefine's; only ids and count are read), qs: dense queries of the data's d,
 // seeds: [nq][s] start ids (s <= 64, -1 = unused slot), ef: entries of the beam (k <= ef <= 256).
@@ -710,6 +727,51 @@ inline KnnResult graphSearchSV(const RPForest& tts, const GraphResult& g, const 
   for (size_t i = 0; i < nq; ++i)
     for (int e = cnt[i]; e < seed_k; ++e) seeds[i * (size_t)seed_k + (size_t)e] = -1;
   return graphSearchSV(*tts.ctx, *tts.data, g, qs, k, ef, seeds, seed_k, stats);
+}
+
+// graphSearchSV under another distance (rpt_graph_search_csr_metric_host): Metric::Cosine /
+// Metric::Inner over the indices both the query and the row store, as knnGraphSV(tts, k, metric)
+// defines them (bit-equal to bruteKnn(ctx, data, qs, k, metric)'s); Metric::L2 gives graphSearchSV's
+// bits.  While every stored value is finite that is graphSearch(..., metric) on the dense-ified data
+// set and queries bit for bit.  A query without nonzeros is NaN from everything under Metric::Cosine
+// and gets its answers ordered by id.
+inline KnnResult graphSearchSV(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs,
+                               Metric metric, int k, int ef, const std::vector<int32_t>& seeds, int s,
+                               SearchStats* stats = nullptr) {
+  const size_t n = (size_t)data.n, nq = (size_t)qs.n;
+  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0))
+    throw RPTError(RPT_E_ARG, "graphSearchSV: a graph of another data set");
+  if (s < 1 || seeds.size() != nq * (size_t)s) throw RPTError(RPT_E_ARG, "graphSearchSV: seeds must be [nq][s]");
+  const int32_t none = -1;  // non-NULL pointers for empty inputs
+  KnnResult r;
+  r.k = k;
+  r.ids.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
+  r.dist.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
+  r.count.resize(nq + 1);
+  check(rpt_graph_search_csr_metric_host(ctx.get(), data.get(), qs.get(), g.k, n ? g.ids.data() : &none,
+                                         n ? g.count.data() : &none, s, nq ? seeds.data() : &none, k, ef,
+                                         metric_flags(metric), 0, r.ids.data(), r.dist.data(), r.count.data()));
+  r.ids.resize(nq * (size_t)k);
+  r.dist.resize(nq * (size_t)k);
+  r.count.resize(nq);
+  if (stats) check(rpt_graph_search_last(ctx.get(), &stats->expansions, &stats->evaluated));
+  return r;
+}
+// ... the seeds taken from a batch forest over the CSR set under the same metric (Metric::Cosine /
+// Inner: rpt_knn_csr_metric_host with RPT_KNN_DEDUP)
+inline KnnResult graphSearchSV(const RPForest& tts, const GraphResult& g, const Dataset& qs, Metric metric, int k,
+                               int ef, int seed_k = 8, SearchStats* stats = nullptr) {
+  const size_t nq = (size_t)qs.n;
+  if (seed_k < 1) throw RPTError(RPT_E_ARG, "graphSearchSV: seed_k must be at least 1");
+  std::vector<int32_t> seeds(nq * (size_t)seed_k + 1), cnt(nq + 1);
+  std::vector<double> dist(nq * (size_t)seed_k + 1);
+  check((metric == Metric::L2 ? rpt_knn_host : rpt_knn_csr_metric_host)(
+      tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), seed_k, RPT_KNN_DEDUP | metric_flags(metric),
+      seeds.data(), dist.data(), cnt.data()));
+  seeds.resize(nq * (size_t)seed_k);
+  for (size_t i = 0; i < nq; ++i)
+    for (int e = cnt[i]; e < seed_k; ++e) seeds[i * (size_t)seed_k + (size_t)e] = -1;
+  return graphSearchSV(*tts.ctx, *tts.data, g, qs, metric, k, ef, seeds, seed_k, stats);
 }
 
 struct BruteResult {

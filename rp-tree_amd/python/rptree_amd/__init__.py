@@ -44,6 +44,7 @@ __all__ = [
     "knnGraphMetricSV", "knnGraphMetricSVDev", "knnGraphRefineMetricSV", "knnGraphRefineMetricSVDev",
     "graphSearch", "graphSearchDev", "graphSearchLast", "graphSearchSV", "graphSearchSVDev",
     "graphPrepare", "graphPrepareDev", "graphPrepareLast", "graphPrepareSV", "graphPrepareSVDev",
+    "graphSearchMetricSV", "graphSearchMetricSVDev", "graphPrepareMetricSV", "graphPrepareMetricSVDev",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -1124,7 +1125,8 @@ def graphSearch(graph, data, qs, k, ef=None, seeds=None, forest=None, seed_k=8, 
     knnBatch(seed_k, forest, qs, dedup=True, metric=metric), and repeatedly offers the graph row of
     the beam's first unexpanded entry until none is left.  The answer is the first k of the beam
     by (distance, id); metric: None / metricL2, metricCosine or metricInner, the distances those
-    host functions bit for bit (L2: on f64 rows).  Unused slots are id -1, distance +inf."""
+    host functions bit for bit (L2: on f64 rows).  Unused slots are id -1, distance +inf.  SVector
+    (CSR) data is refused here: graphSearchSV (L2), graphSearchMetricSV (any of the three)."""
     metric_flag = _metric_flag(metric)
     ds = _refine_data(data)
     ctx = ctx or ds.ctx
@@ -1211,6 +1213,56 @@ def graphSearchSVDev(data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, k, e
                                          C.c_void_p(count_ptr)))
 
 
+def graphSearchMetricSV(distf, graph, data, qs, k, ef=None, seeds=None, forest=None, seed_k=8, ctx=None):
+    """graphSearchSV under another distance (rpt_graph_search_csr_metric_host) -> (ids[nq][k],
+    dist[nq][k], count[nq]).  distf: None / metricL2 (the same bits as graphSearchSV), metricCosine or
+    metricInner over the indices both the query and the row store, as knnGraphMetricSV defines them
+    (those host functions on SVectors bit for bit); while every stored value is finite the answer is
+    graphSearch(metric=distf) on the dense-ified data set and queries bit for bit.  An empty or
+    all-zero query is NaN from everything under metricCosine: it still gets its answers, ordered by
+    id.  graph: e.g. knnGraphMetricSV's, knnGraphRefineMetricSV's or graphPrepareMetricSV's under the
+    same distf.  With `forest` the seeds are the ids of knnBatch(seed_k, forest, qs, dedup=True,
+    metric=distf).  Everything else as graphSearchSV.  (graphSearch(metric=) itself takes dense data
+    only.)"""
+    metric = _metric_flag(distf)
+    ds = _refine_data(data)
+    ctx = ctx or ds.ctx
+    gids = np.ascontiguousarray(graph[0], dtype=np.int32)
+    gcnt = np.ascontiguousarray(graph[-1], dtype=np.int32)
+    if gids.ndim != 2 or gids.shape[0] != ds.n or gcnt.shape != (ds.n,):
+        raise ValueError("graph must be (ids[n][kg], dist[n][kg], count[n]) over the data set's n rows")
+    if ef is None:
+        ef = max(int(k), 32)
+    if seeds is None and forest is None:
+        raise ValueError("graphSearchMetricSV needs seeds or a forest to take them from")
+    qd, nq = _query_dataset(ctx, ds, qs)
+    if seeds is None:
+        sid, _, scnt = knnBatch(int(seed_k), forest, qd, dedup=True, metric=distf)
+        seeds = np.where(np.arange(sid.shape[1])[None, :] < scnt[:, None], sid, -1)
+    seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+    if seeds.ndim != 2 or seeds.shape[0] != nq:
+        raise ValueError("seeds must be [nq][s]")
+    ids = np.empty((nq, k), dtype=np.int32)
+    dist = np.empty((nq, k), dtype=np.float64)
+    cnt = np.empty(nq, dtype=np.int32)
+    check(lib().rpt_graph_search_csr_metric_host(ctx._h, ds._h, qd._h, int(gids.shape[1]), _vp(gids), _vp(gcnt),
+                                                 int(seeds.shape[1]), _vp(seeds), int(k), int(ef), metric, 0,
+                                                 _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def graphSearchMetricSVDev(distf, data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, k, ef, ids_ptr, dist_ptr,
+                           count_ptr):
+    """graphSearchMetricSV on device arrays (rpt_graph_search_csr_metric_dev): data and queries are CSR
+    Datasets; the arrays and the synchronisation as graphSearchDev's."""
+    metric = _metric_flag(distf)
+    ds = _refine_data(data)
+    check(lib().rpt_graph_search_csr_metric_dev(ds.ctx._h, ds._h, queries._h, int(kg), C.c_void_p(gids_ptr),
+                                                C.c_void_p(gcount_ptr), int(s), C.c_void_p(seeds_ptr), int(k),
+                                                int(ef), metric, 0, C.c_void_p(ids_ptr), C.c_void_p(dist_ptr),
+                                                C.c_void_p(count_ptr)))
+
+
 def graphSearchLast(ctx=None):
     """(expansions, evaluated) of the last graphSearch / graphSearchSV call on ctx (rpt_graph_search_last;
     synchronises): beam entries expanded and distances computed, summed over the queries."""
@@ -1257,7 +1309,8 @@ def graphPrepare(graph, data, kout=None, diversify=True, reverse=True, metric=No
     i, at the distance stored there.  The row is the first kout (None = min(64, 2 k)) of that set by
     (distance, id); unused slots are id -1, distance +inf.  metric: None / metricL2, metricCosine or
     metricInner, the one the graph was built under.  Under metricInner, which is no metric,
-    diversify costs recall: pass diversify=False there.  Deterministic; k and kout <= 64."""
+    diversify costs recall: pass diversify=False there.  Deterministic; k and kout <= 64.  SVector
+    (CSR) data is refused here: graphPrepareSV (L2), graphPrepareMetricSV (any of the three)."""
     return _graph_prepare(lib().rpt_graph_prepare_host, graph, data, kout, diversify, reverse,
                           _metric_flag(metric), ctx)
 
@@ -1296,6 +1349,31 @@ def graphPrepareSVDev(k, data, ids_ptr, dist_ptr, count_ptr, kout, out_ids_ptr, 
                                           C.c_void_p(count_ptr), int(kout), 0,
                                           _prepare_flags(diversify, reverse), C.c_void_p(out_ids_ptr),
                                           C.c_void_p(out_dist_ptr), C.c_void_p(out_count_ptr)))
+
+
+def graphPrepareMetricSV(distf, graph, data, kout=None, diversify=True, reverse=True, ctx=None):
+    """graphPrepareSV under another distance (rpt_graph_prepare_csr_metric_host) -> new (ids[n][kout],
+    dist[n][kout], count[n]).  distf: None / metricL2 (the same bits as graphPrepareSV), metricCosine
+    or metricInner over the indices both rows store, as knnGraphMetricSV defines them; it must be the
+    one the graph's stored distances were computed under (knnGraphMetricSV's, knnGraphRefineMetricSV's;
+    not detected).  While every stored value is finite the answer (and graphPrepareLast's numbers) is
+    graphPrepare(metric=distf) on the dense-ified data set bit for bit.  Under metricInner diversify
+    costs recall: pass diversify=False there.  Everything else as graphPrepareSV.
+    (graphPrepare(metric=) itself takes dense data only.)"""
+    return _graph_prepare(lib().rpt_graph_prepare_csr_metric_host, graph, data, kout, diversify, reverse,
+                          _metric_flag(distf), ctx)
+
+
+def graphPrepareMetricSVDev(distf, k, data, ids_ptr, dist_ptr, count_ptr, kout, out_ids_ptr, out_dist_ptr,
+                            out_count_ptr, diversify=True, reverse=True):
+    """graphPrepareMetricSV on device arrays (rpt_graph_prepare_csr_metric_dev): data is a CSR Dataset;
+    the arrays and the synchronisation as graphPrepareDev's."""
+    metric = _metric_flag(distf)
+    ds = _refine_data(data)
+    check(lib().rpt_graph_prepare_csr_metric_dev(ds.ctx._h, ds._h, int(k), C.c_void_p(ids_ptr),
+                                                 C.c_void_p(dist_ptr), C.c_void_p(count_ptr), int(kout), metric,
+                                                 _prepare_flags(diversify, reverse), C.c_void_p(out_ids_ptr),
+                                                 C.c_void_p(out_dist_ptr), C.c_void_p(out_count_ptr)))
 
 
 def graphPrepareLast(ctx=None):

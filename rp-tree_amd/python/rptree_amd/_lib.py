@@ -96,11 +96,15 @@ SYMBOLS = {
     "rpt_graph_search_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_csr_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_csr_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "rpt_graph_search_csr_metric_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "rpt_graph_search_csr_metric_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_last": (i32, [vp, p_i64, p_i64]),
     "rpt_graph_prepare_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_prepare_host": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_prepare_csr_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_prepare_csr_host": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rpt_graph_prepare_csr_metric_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rpt_graph_prepare_csr_metric_host": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_prepare_last": (i32, [vp, p_i64, p_i64, p_i64]),
     "rpt_knn_merge_dev": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp]),
     "rpt_knn_record_layout": (i32, [i64, i32, vp, vp, vp, vp]),
