@@ -1166,6 +1166,37 @@ int32_t check_graph_metric(int32_t metric) {
   return RPT_OK;
 }
 
+// the (ids[n][k], dist[n][k], count[n]) arrays of a _host entry point, staged on the device
+struct Triple {
+  DevBuf<int32_t> ids, cnt;
+  DevBuf<double> dist;
+  size_t n = 0, k = 0;
+  int32_t alloc(int64_t rows, int32_t cols) {
+    n = (size_t)rows, k = (size_t)cols;
+    RPT_TRY(ids.alloc(n * k));
+    RPT_TRY(dist.alloc(n * k));
+    return cnt.alloc(n);
+  }
+  int32_t upload(const int32_t* ids_host, const double* dist_host, const int32_t* count_host) {
+    if (!n) return RPT_OK;
+    RPT_HIP(hipMemcpy(ids.p, ids_host, n * k * 4, hipMemcpyHostToDevice));
+    RPT_HIP(hipMemcpy(dist.p, dist_host, n * k * 8, hipMemcpyHostToDevice));
+    RPT_HIP(hipMemcpy(cnt.p, count_host, n * 4, hipMemcpyHostToDevice));
+    return RPT_OK;
+  }
+  int32_t download(int32_t* ids_host, double* dist_host, int32_t* count_host) {
+    if (!n) return RPT_OK;
+    RPT_HIP(hipMemcpy(ids_host, ids.p, n * k * 4, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(dist_host, dist.p, n * k * 8, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(count_host, cnt.p, n * 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+  }
+};
+
+// the entry points a call came through: rpt_x_* (dense rows), rpt_x_csr_* (CSR rows, L2 only) or
+// rpt_x_csr_metric_* (CSR rows under every metric); graph search and preparation
+enum class Rows { Dense, Csr, CsrMetric };
+
 // rpt_knn_graph_dev (has_metric false: the metric bits in flags are refused) and
 // rpt_knn_graph_metric_dev; csr: rpt_knn_graph_csr_dev and rpt_knn_graph_csr_metric_dev
 int32_t graph_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t k, bool has_metric,
@@ -1201,24 +1232,13 @@ int32_t graph_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, int32_t
   RPT_ARG(k >= 1 && k <= RPT_GRAPH_MAX_K, "k must be in [1,64] (RPT_GRAPH_MAX_K)");
   const int64_t n = f->n;
   RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL output");
-  DevBuf<int32_t> ids, cnt;
-  DevBuf<double> dist;
-  RPT_TRY(ids.alloc((size_t)n * k));
-  RPT_TRY(dist.alloc((size_t)n * k));
-  RPT_TRY(cnt.alloc((size_t)n));
-  if (n && flags == RPT_GRAPH_ACCUMULATE) {  // the arrays are an input too
-    RPT_HIP(hipMemcpy(ids.p, ids_host, (size_t)n * k * 4, hipMemcpyHostToDevice));
-    RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
-    RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
-  }
-  RPT_TRY(graph_dev(ctx, f, data, k, has_metric, metric, flags, ids.p, dist.p, cnt.p, csr));
+  Triple g;
+  RPT_TRY(g.alloc(n, k));
+  if (flags == RPT_GRAPH_ACCUMULATE)  // the arrays are an input too
+    RPT_TRY(g.upload(ids_host, dist_host, count_host));
+  RPT_TRY(graph_dev(ctx, f, data, k, has_metric, metric, flags, g.ids.p, g.dist.p, g.cnt.p, csr));
   RPT_HIP(stream_sync(ctx->stream));
-  if (n) {
-    RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
-    RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)n * k * 8, hipMemcpyDeviceToHost));
-    RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  }
-  return RPT_OK;
+  return g.download(ids_host, dist_host, count_host);
 }
 }  // namespace
 
@@ -1341,48 +1361,30 @@ namespace {
 int32_t refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse, int32_t iters,
                    bool has_metric, int32_t metric, int32_t flags, int32_t* ids_dev,
                    double* dist_dev, int32_t* count_dev, bool csr = false) {
-  {
-    if (ctx) dev_set_stream(ctx->stream);
-    RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags, csr));
-    RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
-    RPT_HIP(hipSetDevice(ctx->device));
-    if (csr) return knn_graph_refine_csr_dev(ctx, data, k, reverse, iters, metric, ids_dev, dist_dev, count_dev);
-    return knn_graph_refine_dev(ctx, data, k, reverse, iters, metric, ids_dev, dist_dev, count_dev);
-  }
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags, csr));
+  RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
+  RPT_HIP(hipSetDevice(ctx->device));
+  if (csr) return knn_graph_refine_csr_dev(ctx, data, k, reverse, iters, metric, ids_dev, dist_dev, count_dev);
+  return knn_graph_refine_dev(ctx, data, k, reverse, iters, metric, ids_dev, dist_dev, count_dev);
 }
 
 int32_t refine_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse, int32_t iters,
                     bool has_metric, int32_t metric, int32_t flags, int32_t* ids_host,
                     double* dist_host, int32_t* count_host, bool csr = false) {
-  {
-    if (ctx) dev_set_stream(ctx->stream);
-    RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags, csr));
-    const int64_t n = data->n;
-    RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
-    RPT_TRY(check_graph_rows(n, k, ids_host, count_host));  // before anything is uploaded
-    RPT_HIP(hipSetDevice(ctx->device));
-    DevBuf<int32_t> ids, cnt;
-    DevBuf<double> dist;
-    RPT_TRY(ids.alloc((size_t)n * k));
-    RPT_TRY(dist.alloc((size_t)n * k));
-    RPT_TRY(cnt.alloc((size_t)n));
-    if (n) {
-      RPT_HIP(hipMemcpy(ids.p, ids_host, (size_t)n * k * 4, hipMemcpyHostToDevice));
-      RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
-      RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    if (csr) RPT_TRY(knn_graph_refine_csr_dev(ctx, data, k, reverse, iters, metric, ids.p, dist.p, cnt.p));
-    else RPT_TRY(knn_graph_refine_dev(ctx, data, k, reverse, iters, metric, ids.p, dist.p, cnt.p));
-    RPT_HIP(stream_sync(ctx->stream));
-    if (n) {
-      RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
-      RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)n * k * 8, hipMemcpyDeviceToHost));
-      RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    }
-    return RPT_OK;
-  }
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_TRY(check_refine(ctx, data, k, reverse, iters, has_metric, metric, flags, csr));
+  const int64_t n = data->n;
+  RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
+  RPT_TRY(check_graph_rows(n, k, ids_host, count_host));  // before anything is uploaded
+  RPT_HIP(hipSetDevice(ctx->device));
+  Triple g;
+  RPT_TRY(g.alloc(n, k));
+  RPT_TRY(g.upload(ids_host, dist_host, count_host));
+  RPT_TRY(refine_dev(ctx, data, k, reverse, iters, has_metric, metric, flags, g.ids.p, g.dist.p, g.cnt.p, csr));
+  RPT_HIP(stream_sync(ctx->stream));
+  return g.download(ids_host, dist_host, count_host);
 }
-
 }  // namespace
 
 int32_t rpt_knn_graph_refine_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t reverse,
@@ -1463,22 +1465,22 @@ int32_t rpt_knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* update
 
 // ---- beam search over a kNN graph -------------------------------------------------------------
 namespace {
-// csr: the rpt_graph_search_csr_* entry points (CSR data and queries, L2 only); csr_metric: the
-// rpt_graph_search_csr_metric_* ones (the same, under every metric)
+// Rows::Csr: the rpt_graph_search_csr_* entry points (CSR data and queries, L2 only); Rows::CsrMetric:
+// the rpt_graph_search_csr_metric_* ones (the same, under every metric)
 int32_t check_search(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
-                     int32_t s, int32_t k, int32_t ef, int32_t metric, int32_t flags, bool csr = false,
-                     bool csr_metric = false) {
+                     int32_t s, int32_t k, int32_t ef, int32_t metric, int32_t flags, Rows rows) {
   RPT_ARG(ctx && data && queries, "NULL argument");
   RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
   RPT_TRY(check_graph_metric(metric));
-  if (csr && !csr_metric && metric != 0)
+  if (rows == Rows::Csr && metric != 0)
     return fail(RPT_E_UNSUPPORTED, "the graph search on CSR rows is built under metricL2 only (metric must be 0) "
                                    "by rpt_graph_search_csr_*; cosine / inner product: rpt_graph_search_csr_metric_*");
   RPT_ARG(flags == 0, "flags must be 0");
   RPT_ARG(data->csr == queries->csr, "data and queries must both be dense or both CSR");
-  if (csr_metric)
+  if (rows == Rows::CsrMetric)
     RPT_ARG(data->csr, "rpt_graph_search_csr_metric_* takes CSR data only (dense rows: rpt_graph_search_*)");
-  else if (csr) RPT_ARG(data->csr, "rpt_graph_search_csr_* takes CSR data only (dense rows: rpt_graph_search_*)");
+  else if (rows == Rows::Csr)
+    RPT_ARG(data->csr, "rpt_graph_search_csr_* takes CSR data only (dense rows: rpt_graph_search_*)");
   else if (data->csr)
     return fail(RPT_E_UNSUPPORTED, "the graph search takes dense data only (not CSR rows: rpt_graph_search_csr_*, "
                                    "rpt_graph_search_csr_metric_*)");
@@ -1521,13 +1523,13 @@ int32_t check_search_arrays(int64_t n, int64_t nq, int32_t kg, const int32_t* gi
 int32_t search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
                    const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s, const int32_t* seeds_dev,
                    int32_t k, int32_t ef, int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
-                   int32_t* count_dev, bool csr, bool csr_metric = false) {
+                   int32_t* count_dev, Rows rows) {
   if (ctx) dev_set_stream(ctx->stream);
-  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, csr, csr_metric));
+  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, rows));
   RPT_ARG(data->n == 0 || (gids_dev && gcount_dev), "NULL graph arrays");
   RPT_ARG(queries->n == 0 || (seeds_dev && ids_dev && dist_dev && count_dev), "NULL seeds or output");
   RPT_HIP(hipSetDevice(ctx->device));
-  if (csr)
+  if (rows != Rows::Dense)
     return graph_search_csr_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric,
                                 ids_dev, dist_dev, count_dev);
   return graph_search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric,
@@ -1537,41 +1539,29 @@ int32_t search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* que
 int32_t search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
                     const int32_t* gids_host, const int32_t* gcount_host, int32_t s,
                     const int32_t* seeds_host, int32_t k, int32_t ef, int32_t metric, int32_t flags,
-                    int32_t* ids_host, double* dist_host, int32_t* count_host, bool csr,
-                    bool csr_metric = false) {
+                    int32_t* ids_host, double* dist_host, int32_t* count_host, Rows rows) {
   if (ctx) dev_set_stream(ctx->stream);
-  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, csr, csr_metric));
+  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, rows));
   const int64_t n = data->n, nq = queries->n;
   RPT_ARG(n == 0 || (gids_host && gcount_host), "NULL graph arrays");
   RPT_ARG(nq == 0 || (seeds_host && ids_host && dist_host && count_host), "NULL seeds or output");
   RPT_TRY(check_search_arrays(n, nq, kg, gids_host, gcount_host, s, seeds_host));
   RPT_HIP(hipSetDevice(ctx->device));
-  DevBuf<int32_t> gids, gcnt, seeds, ids, cnt;
-  DevBuf<double> dist;
+  DevBuf<int32_t> gids, gcnt, seeds;
+  Triple out;
   RPT_TRY(gids.alloc((size_t)n * kg));
   RPT_TRY(gcnt.alloc((size_t)n));
   RPT_TRY(seeds.alloc((size_t)nq * s));
-  RPT_TRY(ids.alloc((size_t)nq * k));
-  RPT_TRY(dist.alloc((size_t)nq * k));
-  RPT_TRY(cnt.alloc((size_t)nq));
+  RPT_TRY(out.alloc(nq, k));
   if (n) {
     RPT_HIP(hipMemcpy(gids.p, gids_host, (size_t)n * kg * 4, hipMemcpyHostToDevice));
     RPT_HIP(hipMemcpy(gcnt.p, gcount_host, (size_t)n * 4, hipMemcpyHostToDevice));
   }
   if (nq) RPT_HIP(hipMemcpy(seeds.p, seeds_host, (size_t)nq * s * 4, hipMemcpyHostToDevice));
-  if (csr)
-    RPT_TRY(graph_search_csr_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, metric, ids.p,
-                                 dist.p, cnt.p));
-  else
-    RPT_TRY(graph_search_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, metric, ids.p,
-                             dist.p, cnt.p));
+  RPT_TRY(search_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, metric, flags, out.ids.p,
+                     out.dist.p, out.cnt.p, rows));
   RPT_HIP(stream_sync(ctx->stream));
-  if (nq) {
-    RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-    RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-    RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-  }
-  return RPT_OK;
+  return out.download(ids_host, dist_host, count_host);
 }
 }  // namespace
 
@@ -1581,7 +1571,7 @@ int32_t rpt_graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_da
                              int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
   return guarded([&]() -> int32_t {
     return search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric, flags,
-                      ids_dev, dist_dev, count_dev, false);
+                      ids_dev, dist_dev, count_dev, Rows::Dense);
   });
 }
 
@@ -1592,7 +1582,7 @@ int32_t rpt_graph_search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_d
                               int32_t* count_host) {
   return guarded([&]() -> int32_t {
     return search_host(ctx, data, queries, kg, gids_host, gcount_host, s, seeds_host, k, ef, metric, flags,
-                       ids_host, dist_host, count_host, false);
+                       ids_host, dist_host, count_host, Rows::Dense);
   });
 }
 
@@ -1602,7 +1592,7 @@ int32_t rpt_graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rp
                                  int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
   return guarded([&]() -> int32_t {
     return search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric, flags,
-                      ids_dev, dist_dev, count_dev, true);
+                      ids_dev, dist_dev, count_dev, Rows::Csr);
   });
 }
 
@@ -1613,7 +1603,7 @@ int32_t rpt_graph_search_csr_host(rpt_ctx* ctx, const rpt_dataset* data, const r
                                   int32_t* count_host) {
   return guarded([&]() -> int32_t {
     return search_host(ctx, data, queries, kg, gids_host, gcount_host, s, seeds_host, k, ef, metric, flags,
-                       ids_host, dist_host, count_host, true);
+                       ids_host, dist_host, count_host, Rows::Csr);
   });
 }
 
@@ -1624,7 +1614,7 @@ int32_t rpt_graph_search_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, c
                                         int32_t* count_dev) {
   return guarded([&]() -> int32_t {
     return search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric, flags,
-                      ids_dev, dist_dev, count_dev, true, true);
+                      ids_dev, dist_dev, count_dev, Rows::CsrMetric);
   });
 }
 
@@ -1635,7 +1625,7 @@ int32_t rpt_graph_search_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data, 
                                          int32_t* count_host) {
   return guarded([&]() -> int32_t {
     return search_host(ctx, data, queries, kg, gids_host, gcount_host, s, seeds_host, k, ef, metric, flags,
-                       ids_host, dist_host, count_host, true, true);
+                       ids_host, dist_host, count_host, Rows::CsrMetric);
   });
 }
 
@@ -1650,22 +1640,23 @@ int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evalua
 
 // ---- a kNN graph made ready for the search -------------------------------------------------------
 namespace {
-// csr: the rpt_graph_prepare_csr_* entry points (CSR data, L2 only); csr_metric: the
+// Rows::Csr: the rpt_graph_prepare_csr_* entry points (CSR data, L2 only); Rows::CsrMetric: the
 // rpt_graph_prepare_csr_metric_* ones (the same, under every metric)
 int32_t check_prepare(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t kout, int32_t metric,
-                      int32_t flags, bool csr = false, bool csr_metric = false) {
+                      int32_t flags, Rows rows) {
   RPT_ARG(ctx && data, "NULL argument");
   RPT_ARG(data->ctx == ctx, "handles belong to another context");
   RPT_TRY(check_graph_metric(metric));
-  if (csr && !csr_metric && metric != 0)
+  if (rows == Rows::Csr && metric != 0)
     return fail(RPT_E_UNSUPPORTED,
                 "the graph preparation on CSR rows is built under metricL2 only (metric must be 0) by "
                 "rpt_graph_prepare_csr_*; cosine / inner product: rpt_graph_prepare_csr_metric_*");
   RPT_ARG((flags & ~(RPT_GRAPH_PREP_DIVERSIFY | RPT_GRAPH_PREP_REVERSE)) == 0,
           "flags must be an or of RPT_GRAPH_PREP_DIVERSIFY and RPT_GRAPH_PREP_REVERSE");
-  if (csr_metric)
+  if (rows == Rows::CsrMetric)
     RPT_ARG(data->csr, "rpt_graph_prepare_csr_metric_* takes CSR data only (dense rows: rpt_graph_prepare_*)");
-  else if (csr) RPT_ARG(data->csr, "rpt_graph_prepare_csr_* takes CSR data only (dense rows: rpt_graph_prepare_*)");
+  else if (rows == Rows::Csr)
+    RPT_ARG(data->csr, "rpt_graph_prepare_csr_* takes CSR data only (dense rows: rpt_graph_prepare_*)");
   else if (data->csr)
     return fail(RPT_E_UNSUPPORTED, "the graph preparation takes dense data only (not CSR rows: "
                                    "rpt_graph_prepare_csr_*, rpt_graph_prepare_csr_metric_*)");
@@ -1678,9 +1669,9 @@ int32_t check_prepare(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, int32_t 
 int32_t prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_dev,
                     const double* dist_dev, const int32_t* count_dev, int32_t kout, int32_t metric,
                     int32_t flags, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev,
-                    bool csr, bool csr_metric = false) {
+                    Rows rows) {
   if (ctx) dev_set_stream(ctx->stream);
-  RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags, csr, csr_metric));
+  RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags, rows));
   RPT_ARG(data->n == 0 || (ids_dev && dist_dev && count_dev), "NULL graph arrays");
   RPT_ARG(data->n == 0 || (out_ids_dev && out_dist_dev && out_count_dev), "NULL output");
   RPT_HIP(hipSetDevice(ctx->device));
@@ -1691,35 +1682,22 @@ int32_t prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int3
 int32_t prepare_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, const int32_t* ids_host,
                      const double* dist_host, const int32_t* count_host, int32_t kout, int32_t metric,
                      int32_t flags, int32_t* out_ids_host, double* out_dist_host, int32_t* out_count_host,
-                     bool csr, bool csr_metric = false) {
+                     Rows rows) {
   if (ctx) dev_set_stream(ctx->stream);
-  RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags, csr, csr_metric));
+  RPT_TRY(check_prepare(ctx, data, k, kout, metric, flags, rows));
   const int64_t n = data->n;
   RPT_ARG(n == 0 || (ids_host && dist_host && count_host), "NULL graph arrays");
   RPT_ARG(n == 0 || (out_ids_host && out_dist_host && out_count_host), "NULL output");
   RPT_TRY(check_graph_rows(n, k, ids_host, count_host));  // before anything is uploaded
   RPT_HIP(hipSetDevice(ctx->device));
-  DevBuf<int32_t> ids, cnt, oids, ocnt;
-  DevBuf<double> dist, odist;
-  RPT_TRY(ids.alloc((size_t)n * k));
-  RPT_TRY(dist.alloc((size_t)n * k));
-  RPT_TRY(cnt.alloc((size_t)n));
-  RPT_TRY(oids.alloc((size_t)n * kout));
-  RPT_TRY(odist.alloc((size_t)n * kout));
-  RPT_TRY(ocnt.alloc((size_t)n));
-  if (n) {
-    RPT_HIP(hipMemcpy(ids.p, ids_host, (size_t)n * k * 4, hipMemcpyHostToDevice));
-    RPT_HIP(hipMemcpy(dist.p, dist_host, (size_t)n * k * 8, hipMemcpyHostToDevice));
-    RPT_HIP(hipMemcpy(cnt.p, count_host, (size_t)n * 4, hipMemcpyHostToDevice));
-  }
-  RPT_TRY(graph_prepare_dev(ctx, data, k, ids.p, dist.p, cnt.p, kout, metric, flags, oids.p, odist.p, ocnt.p));
+  Triple g, out;
+  RPT_TRY(g.alloc(n, k));
+  RPT_TRY(out.alloc(n, kout));
+  RPT_TRY(g.upload(ids_host, dist_host, count_host));
+  RPT_TRY(prepare_dev(ctx, data, k, g.ids.p, g.dist.p, g.cnt.p, kout, metric, flags, out.ids.p, out.dist.p,
+                      out.cnt.p, rows));
   RPT_HIP(stream_sync(ctx->stream));
-  if (n) {
-    RPT_HIP(hipMemcpy(out_ids_host, oids.p, (size_t)n * kout * 4, hipMemcpyDeviceToHost));
-    RPT_HIP(hipMemcpy(out_dist_host, odist.p, (size_t)n * kout * 8, hipMemcpyDeviceToHost));
-    RPT_HIP(hipMemcpy(out_count_host, ocnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  }
-  return RPT_OK;
+  return out.download(out_ids_host, out_dist_host, out_count_host);
 }
 }  // namespace
 
@@ -1729,7 +1707,7 @@ int32_t rpt_graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, 
                               int32_t* out_count_dev) {
   return guarded([&]() -> int32_t {
     return prepare_dev(ctx, data, k, ids_dev, dist_dev, count_dev, kout, metric, flags, out_ids_dev,
-                       out_dist_dev, out_count_dev, false);
+                       out_dist_dev, out_count_dev, Rows::Dense);
   });
 }
 
@@ -1739,7 +1717,7 @@ int32_t rpt_graph_prepare_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t k,
                                int32_t* out_count_host) {
   return guarded([&]() -> int32_t {
     return prepare_host(ctx, data, k, ids_host, dist_host, count_host, kout, metric, flags, out_ids_host,
-                        out_dist_host, out_count_host, false);
+                        out_dist_host, out_count_host, Rows::Dense);
   });
 }
 
@@ -1749,7 +1727,7 @@ int32_t rpt_graph_prepare_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t
                                   double* out_dist_dev, int32_t* out_count_dev) {
   return guarded([&]() -> int32_t {
     return prepare_dev(ctx, data, k, ids_dev, dist_dev, count_dev, kout, metric, flags, out_ids_dev,
-                       out_dist_dev, out_count_dev, true);
+                       out_dist_dev, out_count_dev, Rows::Csr);
   });
 }
 
@@ -1759,7 +1737,7 @@ int32_t rpt_graph_prepare_csr_host(rpt_ctx* ctx, const rpt_dataset* data, int32_
                                    int32_t* out_ids_host, double* out_dist_host, int32_t* out_count_host) {
   return guarded([&]() -> int32_t {
     return prepare_host(ctx, data, k, ids_host, dist_host, count_host, kout, metric, flags, out_ids_host,
-                        out_dist_host, out_count_host, true);
+                        out_dist_host, out_count_host, Rows::Csr);
   });
 }
 
@@ -1770,7 +1748,7 @@ int32_t rpt_graph_prepare_csr_metric_dev(rpt_ctx* ctx, const rpt_dataset* data, 
                                          int32_t* out_count_dev) {
   return guarded([&]() -> int32_t {
     return prepare_dev(ctx, data, k, ids_dev, dist_dev, count_dev, kout, metric, flags, out_ids_dev,
-                       out_dist_dev, out_count_dev, true, true);
+                       out_dist_dev, out_count_dev, Rows::CsrMetric);
   });
 }
 
@@ -1781,7 +1759,7 @@ int32_t rpt_graph_prepare_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data,
                                           int32_t* out_count_host) {
   return guarded([&]() -> int32_t {
     return prepare_host(ctx, data, k, ids_host, dist_host, count_host, kout, metric, flags, out_ids_host,
-                        out_dist_host, out_count_host, true, true);
+                        out_dist_host, out_count_host, Rows::CsrMetric);
   });
 }
 
@@ -1972,20 +1950,11 @@ int32_t rpt_knn_csr_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* 
     RPT_TRY(check_query(ctx, f, queries));
     RPT_TRY(check_csr_metric(ctx, data, queries, k, flags, 3, kCsrMetricKnnL2, kCsrMetricKnnDense));
     RPT_ARG(ids_host && dist_host && count_host, "NULL output");
-    const int64_t nq = queries->n;
-    DevBuf<int32_t> ids, cnt;
-    DevBuf<double> dist;
-    RPT_TRY(ids.alloc((size_t)nq * k));
-    RPT_TRY(dist.alloc((size_t)nq * k));
-    RPT_TRY(cnt.alloc((size_t)nq));
-    RPT_TRY(rpt_knn_csr_metric_dev(ctx, f, data, queries, k, flags, ids.p, dist.p, cnt.p));
+    Triple out;
+    RPT_TRY(out.alloc(queries->n, k));
+    RPT_TRY(rpt_knn_csr_metric_dev(ctx, f, data, queries, k, flags, out.ids.p, out.dist.p, out.cnt.p));
     RPT_HIP(stream_sync(ctx->stream));
-    if (nq) {
-      RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-      RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-      RPT_HIP(hipMemcpy(count_host, cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    }
-    return RPT_OK;
+    return out.download(ids_host, dist_host, count_host);
   });
 }
 

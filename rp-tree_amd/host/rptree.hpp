@@ -364,7 +364,9 @@ struct GraphResult {
   std::vector<double> dist;    // [n][k]
   std::vector<int32_t> count;  // [n]
 };
-inline GraphResult knnGraph(const RPForest& tts, int k, const GraphResult* accumulate = nullptr) {
+// knnGraph / knnGraphSV around their _host entry point: call(flags, ids, dist, count)
+template <class Call>
+inline GraphResult knnGraphVia(Call call, const RPForest& tts, int k, const GraphResult* accumulate) {
   const size_t n = (size_t)tts.data->n;
   GraphResult g;
   if (accumulate) {
@@ -376,37 +378,30 @@ inline GraphResult knnGraph(const RPForest& tts, int k, const GraphResult* accum
   g.ids.resize(n * (size_t)(k > 0 ? k : 0) + 1);  // + 1: non-NULL pointers for an empty data set
   g.dist.resize(n * (size_t)(k > 0 ? k : 0) + 1);
   g.count.resize(n + 1);
-  check(rpt_knn_graph_host(tts.ctx->get(), tts.get(), tts.data->get(), k,
-                           accumulate ? RPT_GRAPH_ACCUMULATE : 0, g.ids.data(), g.dist.data(),
-                           g.count.data()));
+  check(call(accumulate ? RPT_GRAPH_ACCUMULATE : 0, g.ids.data(), g.dist.data(), g.count.data()));
   g.ids.resize(n * (size_t)k);
   g.dist.resize(n * (size_t)k);
   g.count.resize(n);
   return g;
+}
+inline GraphResult knnGraph(const RPForest& tts, int k, const GraphResult* accumulate = nullptr) {
+  return knnGraphVia(
+      [&](int32_t flags, int32_t* ids, double* dist, int32_t* count) {
+        return rpt_knn_graph_host(tts.ctx->get(), tts.get(), tts.data->get(), k, flags, ids, dist, count);
+      },
+      tts, k, accumulate);
 }
 
 // ... under another distance (rpt_knn_graph_metric_host): Metric::Cosine / Metric::Inner, the
 // distances of RPT_KNN_METRIC_COSINE / _INNER bit for bit (the left-fold dot in double); Metric::L2
 // gives knnGraph's bits.  accumulate must be a result under the same metric (not detected).
 inline GraphResult knnGraph(const RPForest& tts, int k, Metric metric, const GraphResult* accumulate = nullptr) {
-  const size_t n = (size_t)tts.data->n;
-  GraphResult g;
-  if (accumulate) {
-    if (accumulate->k != k || accumulate->count.size() != n)
-      throw RPTError(RPT_E_ARG, "accumulate: a result of another data set or k");
-    g = *accumulate;
-  }
-  g.k = k;
-  g.ids.resize(n * (size_t)(k > 0 ? k : 0) + 1);  // + 1: non-NULL pointers for an empty data set
-  g.dist.resize(n * (size_t)(k > 0 ? k : 0) + 1);
-  g.count.resize(n + 1);
-  check(rpt_knn_graph_metric_host(tts.ctx->get(), tts.get(), tts.data->get(), k, metric_flags(metric),
-                                  accumulate ? RPT_GRAPH_ACCUMULATE : 0, g.ids.data(), g.dist.data(),
-                                  g.count.data()));
-  g.ids.resize(n * (size_t)k);
-  g.dist.resize(n * (size_t)k);
-  g.count.resize(n);
-  return g;
+  return knnGraphVia(
+      [&](int32_t flags, int32_t* ids, double* dist, int32_t* count) {
+        return rpt_knn_graph_metric_host(tts.ctx->get(), tts.get(), tts.data->get(), k, metric_flags(metric), flags,
+                                         ids, dist, count);
+      },
+      tts, k, accumulate);
 }
 
 // NN-descent rounds over a kNN graph (rpt_knn_graph_refine_host) -> the refined graph; `g` is not
@@ -417,43 +412,44 @@ inline GraphResult knnGraph(const RPForest& tts, int k, Metric metric, const Gra
 struct RefineStats {
   int64_t rounds = 0, updates = 0, candidates = 0;
 };
-inline GraphResult knnGraphRefine(Context& ctx, const Dataset& data, const GraphResult& g, int iters = 1,
-                                  int reverse = -1, RefineStats* stats = nullptr) {
+// knnGraphRefine / knnGraphRefineSV around their _host entry point: call(reverse, flags, ids, dist, count),
+// reverse already resolved (-1 -> k)
+template <class Call>
+inline GraphResult knnGraphRefineVia(Call call, const char* who, Context& ctx, const Dataset& data,
+                                     const GraphResult& g, int reverse, RefineStats* stats) {
   const size_t n = (size_t)data.n;
   if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0) || g.dist.size() != g.ids.size())
-    throw RPTError(RPT_E_ARG, "knnGraphRefine: a graph of another data set or k");
+    throw RPTError(RPT_E_ARG, std::string(who) + ": a graph of another data set or k");
   GraphResult out = g;
   out.ids.resize(out.ids.size() + 1);  // + 1: non-NULL pointers for an empty data set
   out.dist.resize(out.dist.size() + 1);
   out.count.resize(n + 1);
-  check(rpt_knn_graph_refine_host(ctx.get(), data.get(), g.k, reverse < 0 ? g.k : reverse, iters, 0,
-                                  out.ids.data(), out.dist.data(), out.count.data()));
+  check(call(reverse < 0 ? g.k : reverse, 0, out.ids.data(), out.dist.data(), out.count.data()));
   out.ids.resize(n * (size_t)g.k);
   out.dist.resize(n * (size_t)g.k);
   out.count.resize(n);
   if (stats) check(rpt_knn_graph_refine_last(ctx.get(), &stats->rounds, &stats->updates, &stats->candidates));
   return out;
 }
+inline GraphResult knnGraphRefine(Context& ctx, const Dataset& data, const GraphResult& g, int iters = 1,
+                                  int reverse = -1, RefineStats* stats = nullptr) {
+  return knnGraphRefineVia(
+      [&](int32_t rev, int32_t flags, int32_t* ids, double* dist, int32_t* count) {
+        return rpt_knn_graph_refine_host(ctx.get(), data.get(), g.k, rev, iters, flags, ids, dist, count);
+      },
+      "knnGraphRefine", ctx, data, g, reverse, stats);
+}
 
 // ... under another distance (rpt_knn_graph_refine_metric_host); the graph's stored distances must
 // be that metric's (knnGraph's under the same Metric; another is not detected)
 inline GraphResult knnGraphRefine(Context& ctx, const Dataset& data, const GraphResult& g, Metric metric,
                                   int iters = 1, int reverse = -1, RefineStats* stats = nullptr) {
-  const size_t n = (size_t)data.n;
-  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0) || g.dist.size() != g.ids.size())
-    throw RPTError(RPT_E_ARG, "knnGraphRefine: a graph of another data set or k");
-  GraphResult out = g;
-  out.ids.resize(out.ids.size() + 1);  // + 1: non-NULL pointers for an empty data set
-  out.dist.resize(out.dist.size() + 1);
-  out.count.resize(n + 1);
-  check(rpt_knn_graph_refine_metric_host(ctx.get(), data.get(), g.k, reverse < 0 ? g.k : reverse, iters,
-                                         metric_flags(metric), 0, out.ids.data(), out.dist.data(),
-                                         out.count.data()));
-  out.ids.resize(n * (size_t)g.k);
-  out.dist.resize(n * (size_t)g.k);
-  out.count.resize(n);
-  if (stats) check(rpt_knn_graph_refine_last(ctx.get(), &stats->rounds, &stats->updates, &stats->candidates));
-  return out;
+  return knnGraphRefineVia(
+      [&](int32_t rev, int32_t flags, int32_t* ids, double* dist, int32_t* count) {
+        return rpt_knn_graph_refine_metric_host(ctx.get(), data.get(), g.k, rev, iters, metric_flags(metric), flags,
+                                                ids, dist, count);
+      },
+      "knnGraphRefine", ctx, data, g, reverse, stats);
 }
 
 // knnGraph of a forest over SVector rows (rpt_knn_graph_csr_host).  The distances are metricDDL2's
@@ -461,44 +457,22 @@ inline GraphResult knnGraphRefine(Context& ctx, const Dataset& data, const Graph
 // knnGraph's on the dense-ified data set with the same forest; the kernels visit only the 32-column
 // windows in which a leaf holds a nonzero.  The rows' indices must ascend strictly.  L2 only.
 inline GraphResult knnGraphSV(const RPForest& tts, int k, const GraphResult* accumulate = nullptr) {
-  const size_t n = (size_t)tts.data->n;
-  GraphResult g;
-  if (accumulate) {
-    if (accumulate->k != k || accumulate->count.size() != n)
-      throw RPTError(RPT_E_ARG, "accumulate: a result of another data set or k");
-    g = *accumulate;
-  }
-  g.k = k;
-  g.ids.resize(n * (size_t)(k > 0 ? k : 0) + 1);  // + 1: non-NULL pointers for an empty data set
-  g.dist.resize(n * (size_t)(k > 0 ? k : 0) + 1);
-  g.count.resize(n + 1);
-  check(rpt_knn_graph_csr_host(tts.ctx->get(), tts.get(), tts.data->get(), k,
-                               accumulate ? RPT_GRAPH_ACCUMULATE : 0, g.ids.data(), g.dist.data(),
-                               g.count.data()));
-  g.ids.resize(n * (size_t)k);
-  g.dist.resize(n * (size_t)k);
-  g.count.resize(n);
-  return g;
+  return knnGraphVia(
+      [&](int32_t flags, int32_t* ids, double* dist, int32_t* count) {
+        return rpt_knn_graph_csr_host(tts.ctx->get(), tts.get(), tts.data->get(), k, flags, ids, dist, count);
+      },
+      tts, k, accumulate);
 }
 
 // knnGraphRefine over SVector rows (rpt_knn_graph_refine_csr_host): the same rounds, the same
 // statistics, bit-equal to knnGraphRefine on the dense-ified data set
 inline GraphResult knnGraphRefineSV(Context& ctx, const Dataset& data, const GraphResult& g, int iters = 1,
                                     int reverse = -1, RefineStats* stats = nullptr) {
-  const size_t n = (size_t)data.n;
-  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0) || g.dist.size() != g.ids.size())
-    throw RPTError(RPT_E_ARG, "knnGraphRefineSV: a graph of another data set or k");
-  GraphResult out = g;
-  out.ids.resize(out.ids.size() + 1);  // + 1: non-NULL pointers for an empty data set
-  out.dist.resize(out.dist.size() + 1);
-  out.count.resize(n + 1);
-  check(rpt_knn_graph_refine_csr_host(ctx.get(), data.get(), g.k, reverse < 0 ? g.k : reverse, iters, 0,
-                                      out.ids.data(), out.dist.data(), out.count.data()));
-  out.ids.resize(n * (size_t)g.k);
-  out.dist.resize(n * (size_t)g.k);
-  out.count.resize(n);
-  if (stats) check(rpt_knn_graph_refine_last(ctx.get(), &stats->rounds, &stats->updates, &stats->candidates));
-  return out;
+  return knnGraphRefineVia(
+      [&](int32_t rev, int32_t flags, int32_t* ids, double* dist, int32_t* count) {
+        return rpt_knn_graph_refine_csr_host(ctx.get(), data.get(), g.k, rev, iters, flags, ids, dist, count);
+      },
+      "knnGraphRefineSV", ctx, data, g, reverse, stats);
 }
 
 // knnGraphSV under another distance (rpt_knn_graph_csr_metric_host): Metric::Cosine / Metric::Inner
@@ -508,45 +482,24 @@ inline GraphResult knnGraphRefineSV(Context& ctx, const Dataset& data, const Gra
 // inf or NaN it is not, and the answer is this definition.  accumulate must be a result under the
 // same metric (not detected).
 inline GraphResult knnGraphSV(const RPForest& tts, int k, Metric metric, const GraphResult* accumulate = nullptr) {
-  const size_t n = (size_t)tts.data->n;
-  GraphResult g;
-  if (accumulate) {
-    if (accumulate->k != k || accumulate->count.size() != n)
-      throw RPTError(RPT_E_ARG, "accumulate: a result of another data set or k");
-    g = *accumulate;
-  }
-  g.k = k;
-  g.ids.resize(n * (size_t)(k > 0 ? k : 0) + 1);  // + 1: non-NULL pointers for an empty data set
-  g.dist.resize(n * (size_t)(k > 0 ? k : 0) + 1);
-  g.count.resize(n + 1);
-  check(rpt_knn_graph_csr_metric_host(tts.ctx->get(), tts.get(), tts.data->get(), k, metric_flags(metric),
-                                      accumulate ? RPT_GRAPH_ACCUMULATE : 0, g.ids.data(), g.dist.data(),
-                                      g.count.data()));
-  g.ids.resize(n * (size_t)k);
-  g.dist.resize(n * (size_t)k);
-  g.count.resize(n);
-  return g;
+  return knnGraphVia(
+      [&](int32_t flags, int32_t* ids, double* dist, int32_t* count) {
+        return rpt_knn_graph_csr_metric_host(tts.ctx->get(), tts.get(), tts.data->get(), k, metric_flags(metric),
+                                             flags, ids, dist, count);
+      },
+      tts, k, accumulate);
 }
 
 // knnGraphRefineSV under another distance (rpt_knn_graph_refine_csr_metric_host); the graph's stored
 // distances must be that metric's (knnGraphSV's under the same Metric; another is not detected)
 inline GraphResult knnGraphRefineSV(Context& ctx, const Dataset& data, const GraphResult& g, Metric metric,
                                     int iters = 1, int reverse = -1, RefineStats* stats = nullptr) {
-  const size_t n = (size_t)data.n;
-  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0) || g.dist.size() != g.ids.size())
-    throw RPTError(RPT_E_ARG, "knnGraphRefineSV: a graph of another data set or k");
-  GraphResult out = g;
-  out.ids.resize(out.ids.size() + 1);  // + 1: non-NULL pointers for an empty data set
-  out.dist.resize(out.dist.size() + 1);
-  out.count.resize(n + 1);
-  check(rpt_knn_graph_refine_csr_metric_host(ctx.get(), data.get(), g.k, reverse < 0 ? g.k : reverse, iters,
-                                             metric_flags(metric), 0, out.ids.data(), out.dist.data(),
-                                             out.count.data()));
-  out.ids.resize(n * (size_t)g.k);
-  out.dist.resize(n * (size_t)g.k);
-  out.count.resize(n);
-  if (stats) check(rpt_knn_graph_refine_last(ctx.get(), &stats->rounds, &stats->updates, &stats->candidates));
-  return out;
+  return knnGraphRefineVia(
+      [&](int32_t rev, int32_t flags, int32_t* ids, double* dist, int32_t* count) {
+        return rpt_knn_graph_refine_csr_metric_host(ctx.get(), data.get(), g.k, rev, iters, metric_flags(metric),
+                                                    flags, ids, dist, count);
+      },
+      "knnGraphRefineSV", ctx, data, g, reverse, stats);
 }
 
 // A kNN graph made ready for graphSearch (rpt_graph_prepare_host) -> a graph of kout columns; `g`
@@ -647,27 +600,55 @@ struct KnnResult {
 struct SearchStats {
   int64_t expansions = 0, evaluated = 0;
 };
-inline KnnResult graphSearch(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs, int k,
-                             int ef, const std::vector<int32_t>& seeds, int s, Metric metric,
-                             SearchStats* stats = nullptr) {
+// graphSearch / graphSearchSV around their _host entry point: call(graph ids, graph count, seeds, flags,
+// ids, dist, count)
+template <class Call>
+inline KnnResult graphSearchVia(Call call, const char* who, Context& ctx, const Dataset& data, const GraphResult& g,
+                                const Dataset& qs, int k, const std::vector<int32_t>& seeds, int s,
+                                SearchStats* stats) {
   const size_t n = (size_t)data.n, nq = (size_t)qs.n;
   if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0))
-    throw RPTError(RPT_E_ARG, "graphSearch: a graph of another data set");
-  if (s < 1 || seeds.size() != nq * (size_t)s) throw RPTError(RPT_E_ARG, "graphSearch: seeds must be [nq][s]");
+    throw RPTError(RPT_E_ARG, std::string(who) + ": a graph of another data set");
+  if (s < 1 || seeds.size() != nq * (size_t)s) throw RPTError(RPT_E_ARG, std::string(who) + ": seeds must be [nq][s]");
   const int32_t none = -1;  // non-NULL pointers for empty inputs
   KnnResult r;
   r.k = k;
   r.ids.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
   r.dist.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
   r.count.resize(nq + 1);
-  check(rpt_graph_search_host(ctx.get(), data.get(), qs.get(), g.k, n ? g.ids.data() : &none,
-                              n ? g.count.data() : &none, s, nq ? seeds.data() : &none, k, ef,
-                              metric_flags(metric), 0, r.ids.data(), r.dist.data(), r.count.data()));
+  check(call(n ? g.ids.data() : &none, n ? g.count.data() : &none, nq ? seeds.data() : &none, 0, r.ids.data(),
+             r.dist.data(), r.count.data()));
   r.ids.resize(nq * (size_t)k);
   r.dist.resize(nq * (size_t)k);
   r.count.resize(nq);
   if (stats) check(rpt_graph_search_last(ctx.get(), &stats->expansions, &stats->evaluated));
   return r;
+}
+// the seeds a forest gives: the ids of its de-duplicated seed_k nearest candidates (entry: rpt_knn_host or
+// rpt_knn_csr_metric_host, with RPT_KNN_DEDUP in flags), slots beyond that answer's count -1
+inline std::vector<int32_t> forestSeeds(const RPForest& tts, const Dataset& qs, int seed_k, decltype(&rpt_knn_host) entry,
+                                        int32_t flags, const char* who) {
+  const size_t nq = (size_t)qs.n;
+  if (seed_k < 1) throw RPTError(RPT_E_ARG, std::string(who) + ": seed_k must be at least 1");
+  std::vector<int32_t> seeds(nq * (size_t)seed_k + 1), cnt(nq + 1);
+  std::vector<double> dist(nq * (size_t)seed_k + 1);
+  check(entry(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), seed_k, flags, seeds.data(), dist.data(),
+              cnt.data()));
+  seeds.resize(nq * (size_t)seed_k);
+  for (size_t i = 0; i < nq; ++i)
+    for (int e = cnt[i]; e < seed_k; ++e) seeds[i * (size_t)seed_k + (size_t)e] = -1;
+  return seeds;
+}
+inline KnnResult graphSearch(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs, int k,
+                             int ef, const std::vector<int32_t>& seeds, int s, Metric metric,
+                             SearchStats* stats = nullptr) {
+  return graphSearchVia(
+      [&](const int32_t* gids, const int32_t* gcount, const int32_t* sd, int32_t flags, int32_t* ids, double* dist,
+          int32_t* count) {
+        return rpt_graph_search_host(ctx.get(), data.get(), qs.get(), g.k, gids, gcount, s, sd, k, ef,
+                                     metric_flags(metric), flags, ids, dist, count);
+      },
+      "graphSearch", ctx, data, g, qs, k, seeds, s, stats);
 }
 inline KnnResult graphSearch(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs, int k,
                              int ef, const std::vector<int32_t>& seeds, int s, SearchStats* stats = nullptr) {
@@ -677,16 +658,9 @@ inline KnnResult graphSearch(Context& ctx, const Dataset& data, const GraphResul
 // (rpt_knn_host with RPT_KNN_DEDUP under the same metric), slots beyond that answer's count -1
 inline KnnResult graphSearch(const RPForest& tts, const GraphResult& g, const Dataset& qs, int k, int ef,
                              Metric metric = Metric::L2, int seed_k = 8, SearchStats* stats = nullptr) {
-  const size_t nq = (size_t)qs.n;
-  if (seed_k < 1) throw RPTError(RPT_E_ARG, "graphSearch: seed_k must be at least 1");
-  std::vector<int32_t> seeds(nq * (size_t)seed_k + 1), cnt(nq + 1);
-  std::vector<double> dist(nq * (size_t)seed_k + 1);
-  check(rpt_knn_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), seed_k,
-                     RPT_KNN_DEDUP | metric_flags(metric), seeds.data(), dist.data(), cnt.data()));
-  seeds.resize(nq * (size_t)seed_k);
-  for (size_t i = 0; i < nq; ++i)
-    for (int e = cnt[i]; e < seed_k; ++e) seeds[i * (size_t)seed_k + (size_t)e] = -1;
-  return graphSearch(*tts.ctx, *tts.data, g, qs, k, ef, seeds, seed_k, metric, stats);
+  return graphSearch(*tts.ctx, *tts.data, g, qs, k, ef,
+                     forestSeeds(tts, qs, seed_k, rpt_knn_host, RPT_KNN_DEDUP | metric_flags(metric), "graphSearch"),
+                     seed_k, metric, stats);
 }
 
 // graphSearch over SVector rows under L2 (rpt_graph_search_csr_host): data and qs are CSR data sets
@@ -695,38 +669,19 @@ inline KnnResult graphSearch(const RPForest& tts, const GraphResult& g, const Da
 // queries with the same graph and seeds.  The rows' indices must ascend strictly.
 inline KnnResult graphSearchSV(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs, int k,
                                int ef, const std::vector<int32_t>& seeds, int s, SearchStats* stats = nullptr) {
-  const size_t n = (size_t)data.n, nq = (size_t)qs.n;
-  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0))
-    throw RPTError(RPT_E_ARG, "graphSearchSV: a graph of another data set");
-  if (s < 1 || seeds.size() != nq * (size_t)s) throw RPTError(RPT_E_ARG, "graphSearchSV: seeds must be [nq][s]");
-  const int32_t none = -1;  // non-NULL pointers for empty inputs
-  KnnResult r;
-  r.k = k;
-  r.ids.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
-  r.dist.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
-  r.count.resize(nq + 1);
-  check(rpt_graph_search_csr_host(ctx.get(), data.get(), qs.get(), g.k, n ? g.ids.data() : &none,
-                                  n ? g.count.data() : &none, s, nq ? seeds.data() : &none, k, ef, 0, 0,
-                                  r.ids.data(), r.dist.data(), r.count.data()));
-  r.ids.resize(nq * (size_t)k);
-  r.dist.resize(nq * (size_t)k);
-  r.count.resize(nq);
-  if (stats) check(rpt_graph_search_last(ctx.get(), &stats->expansions, &stats->evaluated));
-  return r;
+  return graphSearchVia(
+      [&](const int32_t* gids, const int32_t* gcount, const int32_t* sd, int32_t flags, int32_t* ids, double* dist,
+          int32_t* count) {
+        return rpt_graph_search_csr_host(ctx.get(), data.get(), qs.get(), g.k, gids, gcount, s, sd, k, ef, 0, flags,
+                                         ids, dist, count);
+      },
+      "graphSearchSV", ctx, data, g, qs, k, seeds, s, stats);
 }
 // ... the seeds taken from a batch forest over the CSR set, as graphSearch takes them
 inline KnnResult graphSearchSV(const RPForest& tts, const GraphResult& g, const Dataset& qs, int k, int ef,
                                int seed_k = 8, SearchStats* stats = nullptr) {
-  const size_t nq = (size_t)qs.n;
-  if (seed_k < 1) throw RPTError(RPT_E_ARG, "graphSearchSV: seed_k must be at least 1");
-  std::vector<int32_t> seeds(nq * (size_t)seed_k + 1), cnt(nq + 1);
-  std::vector<double> dist(nq * (size_t)seed_k + 1);
-  check(rpt_knn_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), seed_k, RPT_KNN_DEDUP, seeds.data(),
-                     dist.data(), cnt.data()));
-  seeds.resize(nq * (size_t)seed_k);
-  for (size_t i = 0; i < nq; ++i)
-    for (int e = cnt[i]; e < seed_k; ++e) seeds[i * (size_t)seed_k + (size_t)e] = -1;
-  return graphSearchSV(*tts.ctx, *tts.data, g, qs, k, ef, seeds, seed_k, stats);
+  return graphSearchSV(*tts.ctx, *tts.data, g, qs, k, ef,
+                       forestSeeds(tts, qs, seed_k, rpt_knn_host, RPT_KNN_DEDUP, "graphSearchSV"), seed_k, stats);
 }
 
 // graphSearchSV under another distance (rpt_graph_search_csr_metric_host): Metric::Cosine /
@@ -738,40 +693,22 @@ inline KnnResult graphSearchSV(const RPForest& tts, const GraphResult& g, const 
 inline KnnResult graphSearchSV(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs,
                                Metric metric, int k, int ef, const std::vector<int32_t>& seeds, int s,
                                SearchStats* stats = nullptr) {
-  const size_t n = (size_t)data.n, nq = (size_t)qs.n;
-  if (g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0))
-    throw RPTError(RPT_E_ARG, "graphSearchSV: a graph of another data set");
-  if (s < 1 || seeds.size() != nq * (size_t)s) throw RPTError(RPT_E_ARG, "graphSearchSV: seeds must be [nq][s]");
-  const int32_t none = -1;  // non-NULL pointers for empty inputs
-  KnnResult r;
-  r.k = k;
-  r.ids.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
-  r.dist.resize(nq * (size_t)(k > 0 ? k : 0) + 1);
-  r.count.resize(nq + 1);
-  check(rpt_graph_search_csr_metric_host(ctx.get(), data.get(), qs.get(), g.k, n ? g.ids.data() : &none,
-                                         n ? g.count.data() : &none, s, nq ? seeds.data() : &none, k, ef,
-                                         metric_flags(metric), 0, r.ids.data(), r.dist.data(), r.count.data()));
-  r.ids.resize(nq * (size_t)k);
-  r.dist.resize(nq * (size_t)k);
-  r.count.resize(nq);
-  if (stats) check(rpt_graph_search_last(ctx.get(), &stats->expansions, &stats->evaluated));
-  return r;
+  return graphSearchVia(
+      [&](const int32_t* gids, const int32_t* gcount, const int32_t* sd, int32_t flags, int32_t* ids, double* dist,
+          int32_t* count) {
+        return rpt_graph_search_csr_metric_host(ctx.get(), data.get(), qs.get(), g.k, gids, gcount, s, sd, k, ef,
+                                                metric_flags(metric), flags, ids, dist, count);
+      },
+      "graphSearchSV", ctx, data, g, qs, k, seeds, s, stats);
 }
 // ... the seeds taken from a batch forest over the CSR set under the same metric (Metric::Cosine /
 // Inner: rpt_knn_csr_metric_host with RPT_KNN_DEDUP)
 inline KnnResult graphSearchSV(const RPForest& tts, const GraphResult& g, const Dataset& qs, Metric metric, int k,
                                int ef, int seed_k = 8, SearchStats* stats = nullptr) {
-  const size_t nq = (size_t)qs.n;
-  if (seed_k < 1) throw RPTError(RPT_E_ARG, "graphSearchSV: seed_k must be at least 1");
-  std::vector<int32_t> seeds(nq * (size_t)seed_k + 1), cnt(nq + 1);
-  std::vector<double> dist(nq * (size_t)seed_k + 1);
-  check((metric == Metric::L2 ? rpt_knn_host : rpt_knn_csr_metric_host)(
-      tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), seed_k, RPT_KNN_DEDUP | metric_flags(metric),
-      seeds.data(), dist.data(), cnt.data()));
-  seeds.resize(nq * (size_t)seed_k);
-  for (size_t i = 0; i < nq; ++i)
-    for (int e = cnt[i]; e < seed_k; ++e) seeds[i * (size_t)seed_k + (size_t)e] = -1;
-  return graphSearchSV(*tts.ctx, *tts.data, g, qs, metric, k, ef, seeds, seed_k, stats);
+  return graphSearchSV(*tts.ctx, *tts.data, g, qs, metric, k, ef,
+                       forestSeeds(tts, qs, seed_k, metric == Metric::L2 ? rpt_knn_host : rpt_knn_csr_metric_host,
+                                   RPT_KNN_DEDUP | metric_flags(metric), "graphSearchSV"),
+                       seed_k, stats);
 }
 
 struct BruteResult {

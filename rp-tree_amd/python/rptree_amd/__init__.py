@@ -831,6 +831,30 @@ def knnBatch(k, forest, qs, dedup=False, vote=0, reference_metric=False, metric=
     return ids, dist, cnt
 
 
+def _graph_flag(accumulate):
+    return RPT_GRAPH_ACCUMULATE if accumulate else 0
+
+
+def _knn_graph(entry, k, forest, accumulate, metric_flag=None):
+    """knnGraph / knnGraphMetric / knnGraphSV / knnGraphMetricSV around their _host entry point;
+    metric_flag None: the entry point takes no metric word"""
+    ctx, n = forest.ctx, forest.N
+    if accumulate is None:
+        ids = np.empty((n, k), dtype=np.int32)
+        dist = np.empty((n, k), dtype=np.float64)
+        cnt = np.empty(n, dtype=np.int32)
+    else:                                         # copies: the caller's arrays are not modified
+        ids = np.array(accumulate[0], dtype=np.int32, order="C")
+        dist = np.array(accumulate[1], dtype=np.float64, order="C")
+        cnt = np.array(accumulate[2], dtype=np.int32, order="C")
+        if ids.shape != (n, k) or dist.shape != (n, k) or cnt.shape != (n,):
+            raise ValueError("accumulate must be (ids[n][k], dist[n][k], count[n]) of this forest's n and k")
+    metric = () if metric_flag is None else (metric_flag,)
+    check(entry(ctx._h, forest._h, forest.data._h, int(k), *metric, _graph_flag(accumulate is not None),
+                _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
 def knnGraph(k, forest, accumulate=None):
     """kNN graph of the forest's own points (rpt_knn_graph_host): knn (RPTree.hs:174-176) with every
     stored point as the query, built leaf by leaf -> (ids[n][k], dist[n][k], count[n]).  Row i holds
@@ -839,22 +863,7 @@ def knnGraph(k, forest, accumulate=None):
     unused slots are id -1, distance +inf.  accumulate: an earlier (ids, dist, count) over the
     same data set and k (another forest, a tree shard) whose entries join the candidates; the
     result does not depend on the order forests are folded in.  Dense batch forests, k <= 64."""
-    ctx, n = forest.ctx, forest.N
-    if accumulate is None:
-        flags = 0
-        ids = np.empty((n, k), dtype=np.int32)
-        dist = np.empty((n, k), dtype=np.float64)
-        cnt = np.empty(n, dtype=np.int32)
-    else:
-        flags = RPT_GRAPH_ACCUMULATE
-        ids = np.array(accumulate[0], dtype=np.int32, order="C")
-        dist = np.array(accumulate[1], dtype=np.float64, order="C")
-        cnt = np.array(accumulate[2], dtype=np.int32, order="C")
-        if ids.shape != (n, k) or dist.shape != (n, k) or cnt.shape != (n,):
-            raise ValueError("accumulate must be (ids[n][k], dist[n][k], count[n]) of this forest's n and k")
-    check(lib().rpt_knn_graph_host(ctx._h, forest._h, forest.data._h, int(k), flags, _vp(ids),
-                                   _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _knn_graph(lib().rpt_knn_graph_host, k, forest, accumulate)
 
 
 def knnGraphDev(k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
@@ -863,7 +872,7 @@ def knnGraphDev(k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
     synchronised (forest.ctx.sync() before reading); with accumulate the arrays are an input too
     and whatever filled them must have finished (see Dataset.dense_device)."""
     check(lib().rpt_knn_graph_dev(forest.ctx._h, forest._h, forest.data._h, int(k),
-                                  RPT_GRAPH_ACCUMULATE if accumulate else 0, C.c_void_p(ids_ptr),
+                                  _graph_flag(accumulate), C.c_void_p(ids_ptr),
                                   C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
@@ -874,23 +883,7 @@ def knnGraphMetric(distf, k, forest, accumulate=None):
     ranks last.  accumulate: an earlier answer UNDER THE SAME distf (another is not detected: the
     stored distances are taken as stored).  Everything else as knnGraph.  Dense data only: SVector
     (CSR) rows are refused, knnGraphMetricSV takes them."""
-    metric = _metric_flag(distf)
-    ctx, n = forest.ctx, forest.N
-    if accumulate is None:
-        flags = 0
-        ids = np.empty((n, k), dtype=np.int32)
-        dist = np.empty((n, k), dtype=np.float64)
-        cnt = np.empty(n, dtype=np.int32)
-    else:
-        flags = RPT_GRAPH_ACCUMULATE
-        ids = np.array(accumulate[0], dtype=np.int32, order="C")
-        dist = np.array(accumulate[1], dtype=np.float64, order="C")
-        cnt = np.array(accumulate[2], dtype=np.int32, order="C")
-        if ids.shape != (n, k) or dist.shape != (n, k) or cnt.shape != (n,):
-            raise ValueError("accumulate must be (ids[n][k], dist[n][k], count[n]) of this forest's n and k")
-    check(lib().rpt_knn_graph_metric_host(ctx._h, forest._h, forest.data._h, int(k), metric, flags,
-                                          _vp(ids), _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _knn_graph(lib().rpt_knn_graph_metric_host, k, forest, accumulate, _metric_flag(distf))
 
 
 def knnGraphMetricDev(distf, k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
@@ -898,7 +891,7 @@ def knnGraphMetricDev(distf, k, forest, ids_ptr, dist_ptr, count_ptr, accumulate
     synchronisation as knnGraphDev's."""
     metric = _metric_flag(distf)
     check(lib().rpt_knn_graph_metric_dev(forest.ctx._h, forest._h, forest.data._h, int(k),
-                                         metric, RPT_GRAPH_ACCUMULATE if accumulate else 0,
+                                         metric, _graph_flag(accumulate),
                                          C.c_void_p(ids_ptr), C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
@@ -909,29 +902,14 @@ def knnGraphSV(k, forest, accumulate=None):
     the dense-ified data set with the same forest; the kernels visit only the 32-column windows in
     which a leaf holds a nonzero.  Rows must have strictly ascending columns.  accumulate as
     knnGraph's.  Batch forests over CSR data (f64 or f32 values), L2 only, k <= 64."""
-    ctx, n = forest.ctx, forest.N
-    if accumulate is None:
-        flags = 0
-        ids = np.empty((n, k), dtype=np.int32)
-        dist = np.empty((n, k), dtype=np.float64)
-        cnt = np.empty(n, dtype=np.int32)
-    else:
-        flags = RPT_GRAPH_ACCUMULATE
-        ids = np.array(accumulate[0], dtype=np.int32, order="C")
-        dist = np.array(accumulate[1], dtype=np.float64, order="C")
-        cnt = np.array(accumulate[2], dtype=np.int32, order="C")
-        if ids.shape != (n, k) or dist.shape != (n, k) or cnt.shape != (n,):
-            raise ValueError("accumulate must be (ids[n][k], dist[n][k], count[n]) of this forest's n and k")
-    check(lib().rpt_knn_graph_csr_host(ctx._h, forest._h, forest.data._h, int(k), flags, _vp(ids),
-                                       _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _knn_graph(lib().rpt_knn_graph_csr_host, k, forest, accumulate)
 
 
 def knnGraphSVDev(k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
     """knnGraphSV into device arrays (rpt_knn_graph_csr_dev); the arrays and the synchronisation
     as knnGraphDev's."""
     check(lib().rpt_knn_graph_csr_dev(forest.ctx._h, forest._h, forest.data._h, int(k),
-                                      RPT_GRAPH_ACCUMULATE if accumulate else 0, C.c_void_p(ids_ptr),
+                                      _graph_flag(accumulate), C.c_void_p(ids_ptr),
                                       C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
@@ -945,23 +923,7 @@ def knnGraphMetricSV(distf, k, forest, accumulate=None):
     row is NaN under metricCosine and ranks last, by id; two rows that share no index are at
     metricInner distance -0.0, which ties with +0.0.  accumulate: an earlier answer UNDER THE SAME
     distf.  Everything else as knnGraphSV.  (knnGraphMetric itself takes dense data only.)"""
-    metric = _metric_flag(distf)
-    ctx, n = forest.ctx, forest.N
-    if accumulate is None:
-        flags = 0
-        ids = np.empty((n, k), dtype=np.int32)
-        dist = np.empty((n, k), dtype=np.float64)
-        cnt = np.empty(n, dtype=np.int32)
-    else:
-        flags = RPT_GRAPH_ACCUMULATE
-        ids = np.array(accumulate[0], dtype=np.int32, order="C")
-        dist = np.array(accumulate[1], dtype=np.float64, order="C")
-        cnt = np.array(accumulate[2], dtype=np.int32, order="C")
-        if ids.shape != (n, k) or dist.shape != (n, k) or cnt.shape != (n,):
-            raise ValueError("accumulate must be (ids[n][k], dist[n][k], count[n]) of this forest's n and k")
-    check(lib().rpt_knn_graph_csr_metric_host(ctx._h, forest._h, forest.data._h, int(k), metric, flags,
-                                              _vp(ids), _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _knn_graph(lib().rpt_knn_graph_csr_metric_host, k, forest, accumulate, _metric_flag(distf))
 
 
 def knnGraphMetricSVDev(distf, k, forest, ids_ptr, dist_ptr, count_ptr, accumulate=False):
@@ -969,7 +931,7 @@ def knnGraphMetricSVDev(distf, k, forest, ids_ptr, dist_ptr, count_ptr, accumula
     synchronisation as knnGraphDev's."""
     metric = _metric_flag(distf)
     check(lib().rpt_knn_graph_csr_metric_dev(forest.ctx._h, forest._h, forest.data._h, int(k),
-                                             metric, RPT_GRAPH_ACCUMULATE if accumulate else 0,
+                                             metric, _graph_flag(accumulate),
                                              C.c_void_p(ids_ptr), C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
@@ -985,6 +947,22 @@ def _refine_data(data):
     return data if isinstance(data, Dataset) else data.data
 
 
+def _knn_graph_refine(entry, graph, data, iters, reverse, ctx, metric_flag=None):
+    """knnGraphRefine / -SV / -Metric / -MetricSV around their _host entry point; metric_flag None:
+    the entry point takes no metric word"""
+    ds = _refine_data(data)
+    ctx = ctx or ds.ctx
+    ids = np.array(graph[0], dtype=np.int32, order="C")       # copies: refined in place, returned
+    dist = np.array(graph[1], dtype=np.float64, order="C")
+    cnt = np.array(graph[2], dtype=np.int32, order="C")
+    if ids.ndim != 2 or ids.shape[0] != ds.n or dist.shape != ids.shape or cnt.shape != (ds.n,):
+        raise ValueError("graph must be (ids[n][k], dist[n][k], count[n]) over the data set's n rows")
+    k = ids.shape[1]
+    metric = () if metric_flag is None else (metric_flag,)
+    check(entry(ctx._h, ds._h, int(k), int(k if reverse is None else reverse), int(iters), *metric, 0,
+                _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
 def knnGraphRefine(graph, data, iters=1, reverse=None, ctx=None):
     """NN-descent rounds over a kNN graph (rpt_knn_graph_refine_host) -> new (ids, dist, count); the
     input tuple is not modified.  graph: (ids[n][k], dist[n][k], count[n]) over `data`, e.g.
@@ -994,17 +972,7 @@ def knnGraphRefine(graph, data, iters=1, reverse=None, ctx=None):
     neighbours; distances not already in row i are metricDDL2's left fold in double, bit-exact for
     every dtype.  A round that changes nothing ends the sequence.  Deterministic: the same input
     gives the same bits.  k and reverse <= 64."""
-    ds = _refine_data(data)
-    ctx = ctx or ds.ctx
-    ids = np.array(graph[0], dtype=np.int32, order="C")
-    dist = np.array(graph[1], dtype=np.float64, order="C")
-    cnt = np.array(graph[2], dtype=np.int32, order="C")
-    if ids.ndim != 2 or ids.shape[0] != ds.n or dist.shape != ids.shape or cnt.shape != (ds.n,):
-        raise ValueError("graph must be (ids[n][k], dist[n][k], count[n]) over the data set's n rows")
-    k = ids.shape[1]
-    check(lib().rpt_knn_graph_refine_host(ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
-                                          int(iters), 0, _vp(ids), _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _knn_graph_refine(lib().rpt_knn_graph_refine_host, graph, data, iters, reverse, ctx)
 
 
 def knnGraphRefineDev(k, data, ids_ptr, dist_ptr, count_ptr, iters=1, reverse=None):
@@ -1023,17 +991,7 @@ def knnGraphRefineSV(graph, data, iters=1, reverse=None, ctx=None):
     count).  data: a CSR Dataset, or a forest over one.  The distances are metricDDL2's left fold
     over the dense-ified rows, so the answer (and knnGraphRefineLast's numbers) is bit-equal to
     knnGraphRefine on the dense-ified data set.  Everything else as knnGraphRefine."""
-    ds = _refine_data(data)
-    ctx = ctx or ds.ctx
-    ids = np.array(graph[0], dtype=np.int32, order="C")
-    dist = np.array(graph[1], dtype=np.float64, order="C")
-    cnt = np.array(graph[2], dtype=np.int32, order="C")
-    if ids.ndim != 2 or ids.shape[0] != ds.n or dist.shape != ids.shape or cnt.shape != (ds.n,):
-        raise ValueError("graph must be (ids[n][k], dist[n][k], count[n]) over the data set's n rows")
-    k = ids.shape[1]
-    check(lib().rpt_knn_graph_refine_csr_host(ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
-                                              int(iters), 0, _vp(ids), _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _knn_graph_refine(lib().rpt_knn_graph_refine_csr_host, graph, data, iters, reverse, ctx)
 
 
 def knnGraphRefineSVDev(k, data, ids_ptr, dist_ptr, count_ptr, iters=1, reverse=None):
@@ -1052,18 +1010,8 @@ def knnGraphRefineMetric(distf, graph, data, iters=1, reverse=None, ctx=None):
     (knnGraphMetric's under the same distf; another metric is not detected).  Everything else as
     knnGraphRefine.  Dense data only: SVector (CSR) rows are refused, knnGraphRefineMetricSV takes
     them."""
-    metric = _metric_flag(distf)
-    ds = _refine_data(data)
-    ctx = ctx or ds.ctx
-    ids = np.array(graph[0], dtype=np.int32, order="C")
-    dist = np.array(graph[1], dtype=np.float64, order="C")
-    cnt = np.array(graph[2], dtype=np.int32, order="C")
-    if ids.ndim != 2 or ids.shape[0] != ds.n or dist.shape != ids.shape or cnt.shape != (ds.n,):
-        raise ValueError("graph must be (ids[n][k], dist[n][k], count[n]) over the data set's n rows")
-    k = ids.shape[1]
-    check(lib().rpt_knn_graph_refine_metric_host(ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
-                                                 int(iters), metric, 0, _vp(ids), _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _knn_graph_refine(lib().rpt_knn_graph_refine_metric_host, graph, data, iters, reverse, ctx,
+                             _metric_flag(distf))
 
 
 def knnGraphRefineMetricDev(distf, k, data, ids_ptr, dist_ptr, count_ptr, iters=1, reverse=None):
@@ -1082,18 +1030,8 @@ def knnGraphRefineMetricSV(distf, graph, data, iters=1, reverse=None, ctx=None):
     rows store, as knnGraphMetricSV defines them.  The graph's stored distances must be distf's
     (knnGraphMetricSV's under the same distf; another metric is not detected).  Everything else as
     knnGraphRefineSV.  (knnGraphRefineMetric itself takes dense data only.)"""
-    metric = _metric_flag(distf)
-    ds = _refine_data(data)
-    ctx = ctx or ds.ctx
-    ids = np.array(graph[0], dtype=np.int32, order="C")
-    dist = np.array(graph[1], dtype=np.float64, order="C")
-    cnt = np.array(graph[2], dtype=np.int32, order="C")
-    if ids.ndim != 2 or ids.shape[0] != ds.n or dist.shape != ids.shape or cnt.shape != (ds.n,):
-        raise ValueError("graph must be (ids[n][k], dist[n][k], count[n]) over the data set's n rows")
-    k = ids.shape[1]
-    check(lib().rpt_knn_graph_refine_csr_metric_host(ctx._h, ds._h, int(k), int(k if reverse is None else reverse),
-                                                     int(iters), metric, 0, _vp(ids), _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _knn_graph_refine(lib().rpt_knn_graph_refine_csr_metric_host, graph, data, iters, reverse, ctx,
+                             _metric_flag(distf))
 
 
 def knnGraphRefineMetricSVDev(distf, k, data, ids_ptr, dist_ptr, count_ptr, iters=1, reverse=None):
@@ -1116,6 +1054,34 @@ def knnGraphRefineLast(ctx=None):
     return int(a.value), int(b.value), int(c.value)
 
 
+def _graph_search(entry, who, graph, data, qs, k, ef, seeds, forest, seed_k, metric_flag, seed_metric, ctx):
+    """graphSearch / graphSearchSV / graphSearchMetricSV around their _host entry point; seed_metric:
+    the metric of the knnBatch that takes seeds from `forest`"""
+    ds = _refine_data(data)
+    ctx = ctx or ds.ctx
+    gids = np.ascontiguousarray(graph[0], dtype=np.int32)
+    gcnt = np.ascontiguousarray(graph[-1], dtype=np.int32)
+    if gids.ndim != 2 or gids.shape[0] != ds.n or gcnt.shape != (ds.n,):
+        raise ValueError("graph must be (ids[n][kg], dist[n][kg], count[n]) over the data set's n rows")
+    if ef is None:
+        ef = max(int(k), 32)
+    if seeds is None and forest is None:
+        raise ValueError(who + " needs seeds or a forest to take them from")
+    qd, nq = _query_dataset(ctx, ds, qs)
+    if seeds is None:
+        sid, _, scnt = knnBatch(int(seed_k), forest, qd, dedup=True, metric=seed_metric)
+        seeds = np.where(np.arange(sid.shape[1])[None, :] < scnt[:, None], sid, -1)
+    seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+    if seeds.ndim != 2 or seeds.shape[0] != nq:
+        raise ValueError("seeds must be [nq][s]")
+    ids = np.empty((nq, k), dtype=np.int32)
+    dist = np.empty((nq, k), dtype=np.float64)
+    cnt = np.empty(nq, dtype=np.int32)
+    check(entry(ctx._h, ds._h, qd._h, int(gids.shape[1]), _vp(gids), _vp(gcnt), int(seeds.shape[1]),
+                _vp(seeds), int(k), int(ef), metric_flag, 0, _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
 def graphSearch(graph, data, qs, k, ef=None, seeds=None, forest=None, seed_k=8, metric=None, ctx=None):
     """Best-first beam search over a kNN graph (rpt_graph_search_host) -> (ids[nq][k], dist[nq][k],
     count[nq]).  graph: (ids[n][kg], dist[n][kg], count[n]) over `data`, e.g. knnGraph's or
@@ -1127,31 +1093,8 @@ def graphSearch(graph, data, qs, k, ef=None, seeds=None, forest=None, seed_k=8, 
     by (distance, id); metric: None / metricL2, metricCosine or metricInner, the distances those
     host functions bit for bit (L2: on f64 rows).  Unused slots are id -1, distance +inf.  SVector
     (CSR) data is refused here: graphSearchSV (L2), graphSearchMetricSV (any of the three)."""
-    metric_flag = _metric_flag(metric)
-    ds = _refine_data(data)
-    ctx = ctx or ds.ctx
-    gids = np.ascontiguousarray(graph[0], dtype=np.int32)
-    gcnt = np.ascontiguousarray(graph[-1], dtype=np.int32)
-    if gids.ndim != 2 or gids.shape[0] != ds.n or gcnt.shape != (ds.n,):
-        raise ValueError("graph must be (ids[n][kg], dist[n][kg], count[n]) over the data set's n rows")
-    if ef is None:
-        ef = max(int(k), 32)
-    if seeds is None and forest is None:
-        raise ValueError("graphSearch needs seeds or a forest to take them from")
-    qd, nq = _query_dataset(ctx, ds, qs)
-    if seeds is None:
-        sid, _, scnt = knnBatch(int(seed_k), forest, qd, dedup=True, metric=metric)
-        seeds = np.where(np.arange(sid.shape[1])[None, :] < scnt[:, None], sid, -1)
-    seeds = np.ascontiguousarray(seeds, dtype=np.int32)
-    if seeds.ndim != 2 or seeds.shape[0] != nq:
-        raise ValueError("seeds must be [nq][s]")
-    ids = np.empty((nq, k), dtype=np.int32)
-    dist = np.empty((nq, k), dtype=np.float64)
-    cnt = np.empty(nq, dtype=np.int32)
-    check(lib().rpt_graph_search_host(ctx._h, ds._h, qd._h, int(gids.shape[1]), _vp(gids), _vp(gcnt),
-                                      int(seeds.shape[1]), _vp(seeds), int(k), int(ef), metric_flag, 0,
-                                      _vp(ids), _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _graph_search(lib().rpt_graph_search_host, "graphSearch", graph, data, qs, k, ef, seeds, forest,
+                         seed_k, _metric_flag(metric), metric, ctx)
 
 
 def graphSearchDev(data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, k, ef, ids_ptr, dist_ptr, count_ptr,
@@ -1177,30 +1120,8 @@ def graphSearchSV(graph, data, qs, k, ef=None, seeds=None, forest=None, seed_k=8
     bit-equal to graphSearch on the dense-ified data set and queries with the same graph and seeds.
     With `forest` (a batch forest over the CSR set) the seeds are the ids of knnBatch(seed_k, forest,
     qs, dedup=True).  Everything else as graphSearch."""
-    ds = _refine_data(data)
-    ctx = ctx or ds.ctx
-    gids = np.ascontiguousarray(graph[0], dtype=np.int32)
-    gcnt = np.ascontiguousarray(graph[-1], dtype=np.int32)
-    if gids.ndim != 2 or gids.shape[0] != ds.n or gcnt.shape != (ds.n,):
-        raise ValueError("graph must be (ids[n][kg], dist[n][kg], count[n]) over the data set's n rows")
-    if ef is None:
-        ef = max(int(k), 32)
-    if seeds is None and forest is None:
-        raise ValueError("graphSearchSV needs seeds or a forest to take them from")
-    qd, nq = _query_dataset(ctx, ds, qs)
-    if seeds is None:
-        sid, _, scnt = knnBatch(int(seed_k), forest, qd, dedup=True)
-        seeds = np.where(np.arange(sid.shape[1])[None, :] < scnt[:, None], sid, -1)
-    seeds = np.ascontiguousarray(seeds, dtype=np.int32)
-    if seeds.ndim != 2 or seeds.shape[0] != nq:
-        raise ValueError("seeds must be [nq][s]")
-    ids = np.empty((nq, k), dtype=np.int32)
-    dist = np.empty((nq, k), dtype=np.float64)
-    cnt = np.empty(nq, dtype=np.int32)
-    check(lib().rpt_graph_search_csr_host(ctx._h, ds._h, qd._h, int(gids.shape[1]), _vp(gids), _vp(gcnt),
-                                          int(seeds.shape[1]), _vp(seeds), int(k), int(ef), 0, 0,
-                                          _vp(ids), _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _graph_search(lib().rpt_graph_search_csr_host, "graphSearchSV", graph, data, qs, k, ef, seeds,
+                         forest, seed_k, 0, None, ctx)
 
 
 def graphSearchSVDev(data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, k, ef, ids_ptr, dist_ptr, count_ptr):
@@ -1224,31 +1145,8 @@ def graphSearchMetricSV(distf, graph, data, qs, k, ef=None, seeds=None, forest=N
     same distf.  With `forest` the seeds are the ids of knnBatch(seed_k, forest, qs, dedup=True,
     metric=distf).  Everything else as graphSearchSV.  (graphSearch(metric=) itself takes dense data
     only.)"""
-    metric = _metric_flag(distf)
-    ds = _refine_data(data)
-    ctx = ctx or ds.ctx
-    gids = np.ascontiguousarray(graph[0], dtype=np.int32)
-    gcnt = np.ascontiguousarray(graph[-1], dtype=np.int32)
-    if gids.ndim != 2 or gids.shape[0] != ds.n or gcnt.shape != (ds.n,):
-        raise ValueError("graph must be (ids[n][kg], dist[n][kg], count[n]) over the data set's n rows")
-    if ef is None:
-        ef = max(int(k), 32)
-    if seeds is None and forest is None:
-        raise ValueError("graphSearchMetricSV needs seeds or a forest to take them from")
-    qd, nq = _query_dataset(ctx, ds, qs)
-    if seeds is None:
-        sid, _, scnt = knnBatch(int(seed_k), forest, qd, dedup=True, metric=distf)
-        seeds = np.where(np.arange(sid.shape[1])[None, :] < scnt[:, None], sid, -1)
-    seeds = np.ascontiguousarray(seeds, dtype=np.int32)
-    if seeds.ndim != 2 or seeds.shape[0] != nq:
-        raise ValueError("seeds must be [nq][s]")
-    ids = np.empty((nq, k), dtype=np.int32)
-    dist = np.empty((nq, k), dtype=np.float64)
-    cnt = np.empty(nq, dtype=np.int32)
-    check(lib().rpt_graph_search_csr_metric_host(ctx._h, ds._h, qd._h, int(gids.shape[1]), _vp(gids), _vp(gcnt),
-                                                 int(seeds.shape[1]), _vp(seeds), int(k), int(ef), metric, 0,
-                                                 _vp(ids), _vp(dist), _vp(cnt)))
-    return ids, dist, cnt
+    return _graph_search(lib().rpt_graph_search_csr_metric_host, "graphSearchMetricSV", graph, data, qs, k, ef,
+                         seeds, forest, seed_k, _metric_flag(distf), distf, ctx)
 
 
 def graphSearchMetricSVDev(distf, data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, k, ef, ids_ptr, dist_ptr,

@@ -3,6 +3,7 @@ distances (rpt_graph_search_csr_metric_*, rpt_graph_prepare_csr_metric_*) are de
 the dotS distance matrices the GPU tests hand to the restatements equal the dense ones for finite
 values and do NOT with a stored inf or NaN; and the restatement searches a sparse graph as a beam
 search should (no GPU)."""
+import ast
 import inspect
 import os
 import re
@@ -122,8 +123,19 @@ def test_ctypes_table_and_python_mirror():
         "(distf, graph, data, kout=None, diversify=True, reverse=True, ctx=None)"
     # the dense functions say where CSR rows go
     assert "graphSearchMetricSV" in rp.graphSearch.__doc__ and "graphPrepareMetricSV" in rp.graphPrepare.__doc__
+    # the seeds a forest gives are taken under distf: the shared body hands seed_metric to knnBatch, and
+    # graphSearchMetricSV's one call of it binds distf there (and its own entry point to `entry`)
+    assert re.search(r"knnBatch\(int\(seed_k\), forest, qd, dedup=True, metric=seed_metric\)",
+                     inspect.getsource(rp._graph_search))
     src = inspect.getsource(rp.graphSearchMetricSV)
-    assert "rpt_graph_search_csr_metric_host" in src and "dedup=True, metric=distf" in src
+    assert "rpt_graph_search_csr_metric_host" in src
+    calls = [c for c in ast.walk(ast.parse(src)) if isinstance(c, ast.Call) and
+             isinstance(c.func, ast.Name) and c.func.id == "_graph_search"]
+    assert len(calls) == 1 and not calls[0].keywords
+    bound = dict(zip(inspect.signature(rp._graph_search).parameters, calls[0].args))
+    assert ast.unparse(bound["seed_metric"]) == "distf"
+    assert ast.unparse(bound["metric_flag"]) == "_metric_flag(distf)"
+    assert ast.unparse(bound["entry"]) == "lib().rpt_graph_search_csr_metric_host"
     assert "rpt_graph_prepare_csr_metric_host" in inspect.getsource(rp.graphPrepareMetricSV)
 
 
