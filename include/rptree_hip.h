@@ -272,7 +272,8 @@ int32_t rpt_forest_import(rpt_ctx* ctx, const rpt_dataset* ds, const double* R_h
  * builder's mode with rpt_forest_set_mode (the flat on-disk format stores it). */
 int32_t rpt_forest_get_mode(const rpt_forest* f, int32_t* mode);
 int32_t rpt_forest_set_mode(rpt_forest* f, int32_t mode);
-/* number of nodes whose cut went through the exact tie-resolution path (statistics) */
+/* statistics of the batch build.  tie_nodes: nodes (of at least two points, over all trees) whose
+ * cut falls on a tie, p'[nh - 1] == p'[nh]; every such node counts once, whichever kernels split it */
 int32_t rpt_forest_stats(rpt_forest* f, int64_t* tie_nodes, int64_t* big_mid_nodes);
 
 /* ---- split of one level on caller-supplied projections: partitionAtMedian

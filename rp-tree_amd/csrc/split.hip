@@ -4432,6 +4432,12 @@ int32_t build_forest_t(rpt_ctx* ctx, const rpt_dataset* ds, rpt_forest* f, int32
     DevBuf<unsigned int> flags;
   };
   std::list<Deferred> deferred;
+  // The overflow flags of the wave kernels and of csub_kernel are per node, not per (tree, node):
+  // a flagged node is run again for EVERY tree, also for the trees whose wave or block had
+  // finished it and counted its cuts on a tie (and a
+  // wave that overflows below its first level has counted the levels above).  After any such redo
+  // tie_count holds some nodes twice, and the statistic is taken from the finished node arrays.
+  bool recount = false;
 
   for (int level = 0; level < Lused; ++level) {
     for (int b = 0; b < 2; ++b) {
@@ -4500,6 +4506,8 @@ int32_t build_forest_t(rpt_ctx* ctx, const rpt_dataset* ds, rpt_forest* f, int32
         }
         for (unsigned i = 0; i < S; ++i) {
           if (nfl && fl[1 + i]) {
+            // (per node as well: the trees whose block finished this node have counted its cuts)
+            recount = true;
             (mid[i].n > kSmallCap ? big : small).push_back(mid[i]);
             continue;
           }
@@ -4571,6 +4579,7 @@ int32_t build_forest_t(rpt_ctx* ctx, const rpt_dataset* ds, rpt_forest* f, int32
           RPT_TRY(stream_aborted(&aborted));
           if (aborted) return build_forest_t<TK>(ctx, ds, f, mode, true);
           if (novf) {  // run again by the block-level kernel: drop their descendants
+            recount = true;
             std::vector<unsigned int> fl((size_t)S + 1);
             RPT_HIP(hipMemcpy(fl.data(), df.flags.p, fl.size() * 4, hipMemcpyDeviceToHost));
             std::vector<Seg> redo;
@@ -4769,11 +4778,27 @@ int32_t build_forest_t(rpt_ctx* ctx, const rpt_dataset* ds, rpt_forest* f, int32
       RPT_HIP(hipGetLastError());
       redone = true;
     }
-    if (redone) {
-      unsigned long long ties = 0;
-      RPT_HIP(hipMemcpyAsync(&ties, tie_count, 8, hipMemcpyDeviceToHost, st));
+    if (redone || recount) {
+      // cuts on a tie, p'[nh - 1] == p'[nh] in nodes of at least two points, read off thr and mglo
+      // (rare path: heavy ties only)
       RPT_HIP(ctx_sync(ctx));
-      f->tie_nodes = (int64_t)ties;
+      std::vector<Node> topo;
+      enumerate_topology(N, L, f->min_leaf, topo);
+      const size_t cnt = (size_t)T * (size_t)f->nodes;
+      std::vector<double> hthr(cnt), hlo(cnt);
+      if (cnt) {
+        RPT_HIP(hipMemcpy(hthr.data(), f->thr.p, cnt * 8, hipMemcpyDeviceToHost));
+        RPT_HIP(hipMemcpy(hlo.data(), f->mglo.p, cnt * 8, hipMemcpyDeviceToHost));
+      }
+      int64_t ties = 0;
+      for (const Node& nd : topo) {
+        if (nd.leaf || nd.n < 2) continue;
+        for (int t = 0; t < T; ++t) {
+          const size_t h = (size_t)t * (size_t)f->nodes + (size_t)nd.heap;
+          ties += !(hlo[h] < hthr[h]) ? 1 : 0;
+        }
+      }
+      f->tie_nodes = ties;
     }
   }
   return RPT_OK;

@@ -3,9 +3,14 @@ rpt_forest_build_sharded / rpt_knn_sharded*, csrc/comm.hip on librccl) on the on
 box has, context options, shard merges beyond one launch's capacity, and the import of a forest
 built ELSEWHERE (the oracle plays deserialiseRPForest's part, Internal.hs:185-196)."""
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import split_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -51,7 +56,7 @@ def test_sharded_entry_points_one_gpu_equal_the_plain_ones(rp, ctx, case, oracle
     loc, lo, nt = sf.local(0)
     assert (lo, nt) == (0, R.shape[0])
     assert np.array_equal(loc.perm, plain.perm)
-    assert np.array_equal(loc.thr, plain.thr, equal_nan=True)
+    split_ref.assert_same_bits(loc.thr, plain.thr, "thr")
     si, sd, sc = sf.knn([qs], k)                                   # host variant
     assert np.array_equal(si, pi) and np.array_equal(sd, pd) and np.array_equal(sc, pc)
     oi = torch.empty((len(Q), k), dtype=torch.int32, device="cuda")
@@ -391,8 +396,7 @@ def test_every_fallback_option_keeps_the_forest_identical(rp, ctx, oracle):
             f = rp.forestBatch(0, L, ml, T, pnz, d, X, ctx=ctx, hyperplanes=R)
         finally:
             ctx.set_option(name, old)
-        assert np.array_equal(f.perm, fo.perm), name
-        assert np.array_equal(f.thr, fo.thr, equal_nan=True), name
+        split_ref.assert_forest_bits_equal(f, fo, name)
 
 
 @pytest.mark.parametrize("kind", ["cont", "ties", "heavy", "constcol"])
@@ -422,12 +426,10 @@ def test_streaming_on_16bit_codes_is_exact(rp, ctx, oracle, kind, mode):
         g = rp.forestBatch(0, L, ml, T, pnz, d, X, ctx=ctx, hyperplanes=R, mode=m)
     finally:
         ctx.set_option("no_codes", old)
-    for name in ("perm", "thr", "mglo", "mghi"):
-        assert np.array_equal(getattr(f, name), getattr(g, name), equal_nan=True), name
+    split_ref.assert_forest_bits_equal(f, g, "no_codes")
     if mode == "exact":
         fo = oracle.forest_build_dense(X, R, ml, threads=T)
-        for name in ("perm", "thr", "mglo", "mghi"):
-            assert np.array_equal(getattr(f, name), getattr(fo, name), equal_nan=True), name
+        split_ref.assert_forest_bits_equal(f, fo, "oracle")
 
 
 def test_codes_after_the_projection_for_csr_and_bf16_rows(rp, ctx, oracle):
@@ -447,9 +449,7 @@ def test_codes_after_the_projection_for_csr_and_bf16_rows(rp, ctx, oracle):
             f = rp.forestBatch(0, L, ml, T, pnz, d, (rowptr, col, val, d), ctx=ctx, hyperplanes=R)
         finally:
             ctx.set_option("no_pcodes", old)
-        assert np.array_equal(f.perm, fo.perm), off
-        for name in ("thr", "mglo", "mghi"):
-            assert np.array_equal(getattr(f, name), getattr(fo, name), equal_nan=True), (name, off)
+        split_ref.assert_forest_bits_equal(f, fo, "no_pcodes = %d" % off)
     # bf16 rows: codes from the stored keys (default), from proj_bf16x3's epilogue (proj_bf16_codes), or none —
     # short rows (hyperplanes resident in LDS, 64-column pass) and long ones (chunks of four k-steps, 128 columns)
     for (n, d, T, ml) in ((200_000, 64, 3, 50), (140_000, 264, 6, 40)):
@@ -469,8 +469,9 @@ def test_codes_after_the_projection_for_csr_and_bf16_rows(rp, ctx, oracle):
             got.append((f.perm.copy(), f.thr.copy(), f.mglo.copy(), f.mghi.copy()))
             f.close()
         for other in got[1:]:
-            for a, b in zip(got[0], other):
-                assert np.array_equal(a, b, equal_nan=True)
+            assert np.array_equal(got[0][0], other[0])
+            for a, b in zip(got[0][1:], other[1:]):
+                split_ref.assert_same_bits(a, b)
 
 
 @pytest.mark.parametrize("d,dtype", [(600, np.float64), (784, np.float64), (300, np.float64),
@@ -687,7 +688,7 @@ def test_csr_dataset_borrowed_from_hbm(rp, ctx, oracle):
     ds = rp.Dataset.csr_from_torch(ctx, tr, tc, tv, d)
     f = rp._build(ctx, ds, R, 6, 25, rp.RPT_PROJ_AUTO)
     fo = oracle.forest_build_csr(rowptr, col, val, d, R, 25)
-    assert np.array_equal(f.perm, fo.perm) and np.array_equal(f.thr, fo.thr, equal_nan=True)
+    split_ref.assert_forest_bits_equal(f, fo)
     qr, qc, qv = oracle.data_normal_sparse2(6, 8, d, 0.3)
     ids, dist, cnt = rp.knnBatch(5, f, (qr, qc, qv, d))
     g = rp.forestBatch(9, 6, 25, 3, 0.5, d, (rowptr, col, val, d), ctx=ctx, hyperplanes=R)

@@ -27,9 +27,13 @@ each other (the device ranks f32 distances there, the oracle f64 ones: either or
 The test prints how many positions that is and asserts it against the expectation stated at the
 call site."""
 import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import split_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -128,7 +132,7 @@ def test_c1_10k_x16_one_tree_everything_identical(rp, oracle):
     fo = oracle.forest_build_dense(X, f.R, min_leaf, want_proj=True)
     assert np.array_equal(f.perm, fo.perm)
     for name in ("thr", "mglo", "mghi"):
-        assert np.array_equal(getattr(f, name), getattr(fo, name), equal_nan=True), name
+        split_ref.assert_same_bits(getattr(f, name), getattr(fo, name), name)
     P = f.proj()
     assert np.array_equal(P[0, 0], fo.proj[0, 0])          # every point meets the root's vector
     ids, dist, cnt = rp.knnBatch(k, f, Q)
@@ -156,7 +160,7 @@ def test_c2_1m_x128_32_trees(rp, oracle):
     for t in range(T):
         assert np.array_equal(f.perm[t], fo.perm[t]), "tree %d" % t
         for name in ("thr", "mglo", "mghi"):
-            assert np.array_equal(getattr(f, name)[t], getattr(fo, name)[t], equal_nan=True), (name, t)
+            split_ref.assert_same_bits(getattr(f, name)[t], getattr(fo, name)[t], "%s of tree %d" % (name, t))
     # (ii) every tree: a permutation, cuts consistent with the tree's own projections
     for t in range(T):
         assert_permutation(f.perm[t])
@@ -209,7 +213,7 @@ def test_c3_1m_x784_sparse(rp, oracle, torch):
     fo = oracle.forest_build_csr(rowptr, col, val, d, f.R, min_leaf, threads=min(T, NCPU))
     assert np.array_equal(f.perm, fo.perm)
     for name in ("thr", "mglo", "mghi"):
-        assert np.array_equal(getattr(f, name), getattr(fo, name), equal_nan=True), name
+        split_ref.assert_same_bits(getattr(f, name), getattr(fo, name), name)
     # queries: fresh sparse rows of the same distribution
     qr, qc, qv = sparse_uniform_csr(torch, nq, d, 0.19, 4321)
     off, cids = rp.candidatesBatch(f, (qr, qc, qv, d))

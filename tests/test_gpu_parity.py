@@ -10,6 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import knn_f32_ref  # noqa: E402
+import split_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -229,16 +230,17 @@ def test_split_segments_matches_partition_at_median(rp, ctx, oracle):
         ids = perm0[o:o + l]
         nh, order, thr, lo, hi = oracle.partition_at_median(keys[ids])
         assert np.array_equal(perm[o:o + l], ids[order]), "segment %d" % s
-        assert (tm[s, 0], tm[s, 1], tm[s, 2]) == (thr, lo, hi)
+        # as bits: the zero that the order puts at the cut, not just some zero
+        split_ref.assert_same_bits(tm[s], np.array([thr, lo, hi]), "segment %d (thr, mglo, mghi)" % s)
     # untouched tail
     assert np.array_equal(perm[sum(seg_len):], perm0[sum(seg_len):])
 
 
 # ------------------------------------------------------------------ forest build
 def assert_forest_equal(f, fo):
-    assert np.array_equal(f.perm, fo.perm)
-    for a, b in ((f.thr, fo.thr), (f.mglo, fo.mglo), (f.mghi, fo.mghi)):
-        assert np.array_equal(a, b, equal_nan=True)
+    """perm identical; thr / mglo / mghi NaN where the other has NaN and identical BITS elsewhere
+    (np.array_equal cannot tell -0.0 from +0.0)"""
+    split_ref.assert_forest_bits_equal(f, fo)
 
 
 @pytest.mark.parametrize("n,d,T,min_leaf,L", [
@@ -849,7 +851,7 @@ def test_forest_save_load_roundtrip(rp, ctx, small_forest, tmp_path):
     path = str(tmp_path / "forest.npz")
     rp.saveForest(path, f)
     g = rp.loadForest(path, X, ctx=ctx)
-    assert np.array_equal(g.perm, f.perm) and np.array_equal(g.thr, f.thr, equal_nan=True)
+    split_ref.assert_forest_bits_equal(g, f)
     a, b = rp.knnBatch(10, f, Q), rp.knnBatch(10, g, Q)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
     off_a, ids_a = rp.candidatesBatch(f, Q)

@@ -48,6 +48,7 @@ _S = "tests/test_gpu_graph_search.py::"
 _SC = "tests/test_gpu_graph_search_csr.py::"
 _PR = "tests/test_gpu_graph_prepare.py::"
 _PC = "tests/test_gpu_graph_prepare_csr.py::"
+_OK = "tests/test_gpu_forest_own_keys.py::"
 
 # family -> (unpoisoned seconds of the node list on an MI355X, the child's time limit, node ids).
 # The limit is 5 x the unpoisoned time (poison adds two device synchronisations and a fill per
@@ -99,6 +100,15 @@ FAMILIES = {
         _A + "test_codes_after_the_projection_for_csr_and_bf16_rows",
         _P + "test_mid_size_nodes_on_packed_codes[300001-128-cont-float64-exact]",
         _P + "test_mid_size_nodes_on_packed_codes[300000-32-clump-float32-auto]",
+    ]),
+    # the streamed and selection paths (the most scratch) against the split of their own keys
+    "forest_own_keys": (6.2, 120, [
+        _OK + "test_streamed_levels[f32-dups-131080-16]",
+        _OK + "test_streamed_levels[bf16-lattice-131080-64]",               # codes from pcode_kernel
+        _OK + "test_mid_size_nodes_on_packed_codes[f32-clump-300001-16-32]",   # csub_kernel, nodes handed back
+        _OK + "test_streamed_levels[csr_mfma-dups-131080-64]",              # CSR rows in tolerance mode
+        _OK + "test_two_stage_pick[f64_mfma-dups]",
+        _OK + "test_below_the_streamed_levels[f32-dups-16-4097-1]",          # no_stream
     ]),
     "forest_stream": (5.5, 120, [
         _P + "test_streaming_forest_is_the_reference_fold_over_chunks[4000-12-3-20-33]",

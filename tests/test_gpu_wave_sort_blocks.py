@@ -9,9 +9,14 @@ The cases are checked on the CPU first (test_cases_are_what_they_claim, no GPU):
 wave kernel's top nodes and of their descendants follow from N by the halving rule
 (Internal.hs:495,503), the tie counts from the key columns."""
 import contextlib
+import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import split_ref  # noqa: E402
 
 K_CAP = 1024     # points a wave holds (kWCap)
 K_LEVELS = 5     # levels per launch (kWRmax)
@@ -229,8 +234,7 @@ def test_forest_equals_the_oracle_and_the_select_kernel(rp, ctx, oracle, name, n
             g = rp.forestBatch(0, L, ml, T, 0.5, D, X, ctx=ctx, hyperplanes=R, mode=rp.RPT_PROJ_EXACT)
     for t in range(T):
         assert np.array_equal(np.sort(f.perm[t]), np.arange(N)), "tree %d: not a permutation" % t
-    for what in ("perm", "thr", "mglo", "mghi"):
-        a = getattr(f, what)
-        assert np.array_equal(a, getattr(g, what), equal_nan=True), what + ": differs from no_wsort"
-        assert np.array_equal(a, getattr(fo, what), equal_nan=True), what + ": differs from the oracle"
+    # as bits (NaN where NaN): np.array_equal cannot tell the -0.0 of "signed_zero" from +0.0
+    split_ref.assert_forest_bits_equal(f, g, "differs from no_wsort:")
+    split_ref.assert_forest_bits_equal(f, fo, "differs from the oracle:")
     assert f.stats() == g.stats()
