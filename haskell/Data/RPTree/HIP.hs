@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -16,7 +16,7 @@ import Data.Int (Int8, Int32, Int64)
 import Data.Word (Word64)
 import Foreign.C.String (CString, peekCString)
 import Foreign.Marshal.Alloc (alloca)
-import Foreign.Ptr (Ptr)
+import Foreign.Ptr (Ptr, nullPtr)
 import Foreign.Storable (peek)
 import System.IO.Unsafe (unsafePerformIO)
 import qualified Data.IntMap.Strict as IM
@@ -65,6 +65,9 @@ foreign import ccall safe "rpt_graph_search_csr_metric_host" c_graph_search_csr_
 foreign import ccall safe "rpt_graph_prepare_csr_metric_host" c_graph_prepare_csr_metric_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_csr_metric_host" c_knn_csr_metric_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_recall_hits_csr_metric_host" c_recall_hits_csr_metric :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_vote_host" c_knn_vote_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+-- two calls, the first with null outputs returns the total
+foreign import ccall safe "rpt_vote_candidates_host" c_vote_candidates_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Ptr Int64 -> Ptr Int32 -> Ptr Int32 -> Int64 -> Ptr Int64 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
 -- multi-GPU (csrc/comm.hip on librccl): one process drives n devices; per-device arguments are
 -- arrays with one entry per device (Foreign.Marshal.Array.withArray)
@@ -523,3 +526,36 @@ recallWithMetricSVHIP m ctx f ds ntrees dim k qs =
     let rec i = sum [ fromIntegral (hs VS.! (i * ntrees + t)) / fromIntegral k | t <- [0 .. ntrees - 1] ]
                 / fromIntegral ntrees
     pure (V.generate nq rec)
+
+-- | The vote threshold (the reference's commented-out @counts@ / @keepCounts@, RPTree.hs:464-478) for
+-- every row layout and distance (rpt_knn_vote_host): of a query's candidates only the ids that at least
+-- @v@ trees propose are ranked, each once, by (distance, id); the distance is the one 'knnHIP' /
+-- 'knnMetricHIP' / 'knnMetricSVHIP' give for the same data and metric.  @refMetric@ (SVector rows,
+-- 'MetricL2'): the reference's truncating metricSSL2.  @ds@ is the forest's point set, @qd@ the @nq@
+-- queries in the same layout ('withDeviceData' / 'withDeviceDataSV').  Any number of trees and of
+-- candidates, k up to 1024, batch and streamed forests.
+knnVoteHIP :: Metric -> Bool -> Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int -> Int -> Int
+           -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnVoteHIP m refMetric ctx f ds qd nq k v = do
+  let flags = metricFlag m + (if refMetric then 16777216 else 0)     -- RPT_KNN_METRIC_REFERENCE (1 << 24)
+  ids <- VSM.new (max 1 (nq * k)); dist <- VSM.new (max 1 (nq * k)); cnt <- VSM.new (max 1 nq)
+  VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt
+    (c_knn_vote_host ctx f ds qd (fromIntegral k) (fromIntegral v) flags a b))) >>= check
+  (,,) <$> (VS.take (nq * k) <$> VS.freeze ids) <*> (VS.take (nq * k) <$> VS.freeze dist)
+       <*> (VS.take nq <$> VS.freeze cnt)
+
+-- | The voted lists themselves (rpt_vote_candidates_host): @(off, ids, counts)@, the list of query i
+-- is @ids[off i .. off (i + 1))@, ascending, @counts@ the number of trees that propose each id.
+voteCandidatesHIP :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int -> Int
+                  -> IO (VS.Vector Int64, VS.Vector Int32, VS.Vector Int32)
+voteCandidatesHIP ctx f qd nq v = do
+  off <- VSM.new (nq + 1)
+  total <- alloca $ \pt -> do
+    VSM.unsafeWith off (\po -> c_vote_candidates_host ctx f qd (fromIntegral v) po nullPtr nullPtr 0 pt) >>= check
+    peek pt
+  let m = max 1 (fromIntegral total)
+  ids <- VSM.new m; cnt <- VSM.new m
+  alloca $ \pt -> VSM.unsafeWith off (\po -> VSM.unsafeWith ids (\a -> VSM.unsafeWith cnt (\b ->
+    c_vote_candidates_host ctx f qd (fromIntegral v) po a b total pt))) >>= check
+  (,,) <$> VS.freeze off <*> (VS.take (fromIntegral total) <$> VS.freeze ids)
+       <*> (VS.take (fromIntegral total) <$> VS.freeze cnt)

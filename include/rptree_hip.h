@@ -167,6 +167,11 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *   brute_csr_tile (0 auto, n)     brute force over CSR rows: queries per workgroup (1, 2, 4 or 8; other
  *                                  values round down; halved while the tile does not fit LDS; auto
  *                                  takes up to 4)
+ *   knn_vote_lds (0, n)            rpt_knn_vote_*: ids one workgroup sorts in LDS (0 = 16 384, n > 0 =
+ *                                  min(n, 16 384)); queries with more candidates sort in a global slab;
+ *                                  the answer does not depend on it
+ *   knn_vote_slice (0 auto, n)     rpt_knn_vote_*: at most n queries per vote-select slice (auto: by a
+ *                                  fixed scratch budget); the answer does not depend on it
  *   comm_force_exchange            sharded kNN on a ONE-rank communicator still runs record ->
  *                                  ncclAllGather -> merge (set on the communicator's first ctx)
  *   comm_inject_failure            test hook: the device's shard reports a failure (see "Failures"
@@ -180,7 +185,8 @@ int32_t rpt_ctx_get_option(rpt_ctx* ctx, const char* name, int64_t* value);
  * launch of a kernel class while enabled.  which: 0 = projection batch kernels (one launch =
  * one pass over the whole point set for up to 96 hyperplanes), 1 = split work,
  * 2 = query plan (query projections + traversal), 3 = distance/top-k kernel, 4 = the wide
- * (> 32 hyperplanes per pass) MFMA projection launches alone (they are also part of class 0).
+ * (> 32 hyperplanes per pass) MFMA projection launches alone (they are also part of class 0),
+ * 5 = the vote-select kernel of rpt_knn_vote_* / rpt_vote_candidates_host.
  * rpt_prof_get synchronises the stream and returns the accumulated ms and launch count. */
 int32_t rpt_prof_enable(rpt_ctx* ctx, int32_t on);
 int32_t rpt_prof_reset(rpt_ctx* ctx);
@@ -1095,6 +1101,53 @@ int32_t rpt_recall_hits_csr_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_d
                                         const rpt_dataset* queries, int32_t k, int32_t flags,
                                         int32_t* hits_host /*[nq][T]*/,
                                         int32_t* truth_ids_host /*[nq][k], may be NULL*/);
+
+/* ---- vote-threshold kNN for every row layout and distance, no candidate cap ----
+ * The RPT_KNN_VOTE flag of rpt_knn_* keeps its fused path and its caps (dense rows under L2, k <= 64,
+ * at most 1024 trees, a batch forest, at most 16384 candidates and 512 leaves per query); these
+ * entry points serve the same definition everywhere else.
+ * The definition: for a query, take the candidates of all T trees (rpt_candidates' lists);
+ * count(id) is the number of entries equal to id (leaves of one tree are disjoint: the number of
+ * trees that propose id).  The voted list is the ids with count >= v, ascending, each once
+ * (keepCounts' order).  The answer is the first k of the voted list by (distance, id); NaN ranks
+ * last; unused slots are id -1 and distance +inf; count[q] = min(k, number of voted ids).
+ * The distance is exactly the one the non-voting entry point of the same (row layout, dtype, flag)
+ * returns, with its fold order, certificate and exact rerun:
+ *   dense f64, flags 0           metricDDL2's fold: certified cut + exact kernel (rpt_knn_* on f64 rows);
+ *                                a tie wider than k + 8 at the cut is answered by the exact kernel
+ *   dense f32 / bf16, flags 0    the f32 sum in its one fixed order
+ *   dense, _COSINE / _INNER      the left-fold dot of RPT_KNN_METRIC_*
+ *   CSR, flags 0                 the true Euclidean distance of rpt_knn_* on CSR rows
+ *   CSR, _REFERENCE              the reference's truncating metricSSL2
+ *   CSR, _COSINE / _INNER        dotS of rpt_knn_csr_metric_*
+ * v in [1, 65535] (else RPT_E_ARG); k in [1, 1024]; any number of trees; dense f64 / f32 / bf16 and
+ * CSR f64 / f32 data with queries of the same layout and dtype; batch and streamed forests.
+ * `flags` is 0 or exactly one of RPT_KNN_METRIC_COSINE / _INNER / _REFERENCE.  RPT_E_ARG: two of
+ * those bits together, RPT_KNN_METRIC_REFERENCE on dense data, any duplicate-rule bit (the voted
+ * ids are distinct), a RPT_KNN_VOTE field (the threshold is the argument).  An error leaves the
+ * context usable.
+ * No query is refused for its candidate count: a workgroup per query sorts the candidate ids in LDS
+ * (up to 16384 of them; option knn_vote_lds lowers the bound) or, above that, in a slab of global
+ * memory, and compacts the runs of at least v in ascending order.  Scratch is sized from the query
+ * plan and a fixed budget; a batch above it is processed in slices of queries (option
+ * knn_vote_slice bounds a slice).  The answer does not depend on either option.
+ * rpt_knn_last_voted: the voted ids of the last call over all queries = the distances evaluated.
+ * rpt_knn_last_candidates and rpt_knn_last_uncertified are served, rpt_knn_last_tier and
+ * rpt_knn_last_retries read 0.  The _dev variant takes device outputs and returns synchronised.
+ * rpt_vote_candidates_host: the voted lists themselves (the reference's commented-out `counts` /
+ * `keepCounts`), with rpt_candidates' two-call protocol: ids_host NULL returns *total (and
+ * off_host[nq + 1], if given); the second call fills ids_host[cap >= total] and, unless NULL,
+ * counts_host with count(id) of every voted id. */
+int32_t rpt_knn_vote_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                          const rpt_dataset* queries, int32_t k, int32_t v, int32_t flags,
+                          int32_t* ids_host, double* dist_host, int32_t* count_host);
+int32_t rpt_knn_vote_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                         const rpt_dataset* queries, int32_t k, int32_t v, int32_t flags,
+                         int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+int32_t rpt_vote_candidates_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* queries, int32_t v,
+                                 int64_t* off_host /*[nq+1], may be NULL*/, int32_t* ids_host,
+                                 int32_t* counts_host /*may be NULL*/, int64_t cap, int64_t* total);
+int32_t rpt_knn_last_voted(rpt_ctx* ctx, int64_t* total);
 
 #ifdef __cplusplus
 }

@@ -250,6 +250,8 @@ const OptDesc kOptions[] = {
     {"knn_metric_exact", &rpt_options::knn_metric_exact},
     {"knn_csr_pre32", &rpt_options::knn_csr_pre32},
     {"knn_general", &rpt_options::knn_general},
+    {"knn_vote_lds", &rpt_options::knn_vote_lds},
+    {"knn_vote_slice", &rpt_options::knn_vote_slice},
     {"graph_general", &rpt_options::graph_general},
     {"graph_refine_general", &rpt_options::graph_refine_general},
     {"graph_csr_masked", &rpt_options::graph_csr_masked},
@@ -2001,6 +2003,79 @@ int32_t rpt_recall_hits_csr_metric_host(rpt_ctx* ctx, rpt_forest* f, const rpt_d
             "query dtype must have the forest's projection type (f64 vs f32/bf16)");
     RPT_ARG(queries->n * (int64_t)f->T <= 0x7fffffff, "too many (query, tree) pairs for one call");
     return recall_hits(ctx, f, data, queries, k, flags, hits_host, truth_ids_host);
+  });
+}
+
+}  // extern "C"
+
+// ---- the vote threshold for every row layout and distance --------------------------------------
+namespace {
+int32_t check_knn_vote(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* queries, int32_t k,
+                       int32_t v, int32_t flags) {
+  RPT_TRY(check_query(ctx, f, queries));
+  RPT_ARG(data && data->ctx == ctx, "bad data handle");
+  RPT_ARG(data->n == f->n && data->d == f->d, "data shape differs from the forest's");
+  RPT_ARG(data->csr == queries->csr, "data and queries must both be dense or both CSR");
+  RPT_ARG(data->dtype == queries->dtype, "data and query dtype must match");
+  RPT_ARG(proj_dtype(queries->dtype) == f->pdtype,
+          "query dtype must have the forest's projection type (f64 vs f32/bf16)");
+  RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
+  RPT_ARG(v >= 1 && v <= 65535, "rpt_knn_vote_*: v must be in [1, 65535]");
+  RPT_ARG(flags == 0 || flags == RPT_KNN_METRIC_COSINE || flags == RPT_KNN_METRIC_INNER ||
+              flags == RPT_KNN_METRIC_REFERENCE,
+          "rpt_knn_vote_*: flags is 0 or exactly one of RPT_KNN_METRIC_COSINE / _INNER / _REFERENCE (the threshold "
+          "is the argument v, the voted ids are distinct: no duplicate rule)");
+  RPT_ARG(!(flags & RPT_KNN_METRIC_REFERENCE) || data->csr,
+          "rpt_knn_vote_*: RPT_KNN_METRIC_REFERENCE is the CSR rows' metric");
+  return RPT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t rpt_knn_vote_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* queries,
+                         int32_t k, int32_t v, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                         int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_knn_vote(ctx, f, data, queries, k, v, flags));
+    RPT_ARG(ids_dev && dist_dev && count_dev, "NULL output");
+    return knn_vote_dev(ctx, f, data, queries, k, v, flags, ids_dev, dist_dev, count_dev);
+  });
+}
+
+int32_t rpt_knn_vote_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* queries,
+                          int32_t k, int32_t v, int32_t flags, int32_t* ids_host, double* dist_host,
+                          int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_knn_vote(ctx, f, data, queries, k, v, flags));
+    RPT_ARG(ids_host && dist_host && count_host, "NULL output");
+    Triple out;
+    RPT_TRY(out.alloc(queries->n, k));
+    RPT_TRY(knn_vote_dev(ctx, f, data, queries, k, v, flags, out.ids.p, out.dist.p, out.cnt.p));
+    RPT_HIP(stream_sync(ctx->stream));
+    return out.download(ids_host, dist_host, count_host);
+  });
+}
+
+int32_t rpt_vote_candidates_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* queries, int32_t v,
+                                 int64_t* off_host, int32_t* ids_host, int32_t* counts_host, int64_t cap,
+                                 int64_t* total) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_query(ctx, f, queries));
+    RPT_ARG(total, "total is NULL");
+    RPT_ARG(v >= 1 && v <= 65535, "rpt_vote_candidates_host: v must be in [1, 65535]");
+    return vote_candidates(ctx, f, queries, v, off_host, ids_host, counts_host, cap, total);
+  });
+}
+
+int32_t rpt_knn_last_voted(rpt_ctx* ctx, int64_t* total) {
+  return guarded([&]() -> int32_t {
+    RPT_ARG(ctx && total, "NULL argument");
+    *total = ctx->last_voted;
+    return RPT_OK;
   });
 }
 

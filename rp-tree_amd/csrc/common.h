@@ -139,7 +139,7 @@ struct DevBuf {
 
 // kernel classes timed by rpt_prof_* (HIP events on the ctx stream)
 enum { RPT_PROF_PROJECT = 0, RPT_PROF_SPLIT = 1, RPT_PROF_KNN_PLAN = 2, RPT_PROF_KNN_TOPK = 3,
-       RPT_PROF_PROJECT_WIDE = 4, RPT_PROF_CLASSES = 5 };
+       RPT_PROF_PROJECT_WIDE = 4, RPT_PROF_KNN_VOTE = 5, RPT_PROF_CLASSES = 6 };
 
 struct rpt_prof_span {
   hipEvent_t a, b;
@@ -182,6 +182,9 @@ struct rpt_options {
   int64_t knn_metric_exact = 0;  // kNN, cosine / inner product: every query on the exact kernel (no certified cut)
   int64_t knn_csr_pre32 = 0;    // kNN: rank CSR f64 rows on their (u16 column, f32 value) shadow
   int64_t knn_general = 0;      // kNN: unfused general path
+  int64_t knn_vote_lds = 0;     // rpt_knn_vote_*: ids one workgroup sorts in LDS (0 = 16 384, n = min(n, 16 384));
+                                // queries with more candidates sort in a global slab
+  int64_t knn_vote_slice = 0;   // rpt_knn_vote_*: at most this many queries per vote-select slice (0 = by the budget)
   int64_t graph_general = 0;    // kNN graph: every leaf on the tiled kernel (64-row blocks), not the one-workgroup leaf kernel
   int64_t graph_refine_general = 0;  // kNN graph refinement: one point per workgroup for every k and reverse
   int64_t graph_csr_masked = 0;  // kNN graph on CSR rows under cosine / inner: the presence-masked fold for every call
@@ -227,6 +230,7 @@ struct rpt_ctx {
   unsigned long long* metric_unc_dev = nullptr;
   bool metric_unc_pending = false;
   int64_t last_candidates = 0;
+  int64_t last_voted = 0;        // voted ids (= distances evaluated) of the last rpt_knn_vote_* / rpt_vote_candidates_host call
   int64_t last_retries = 0;      // queries of the last fused kNN call that took the in-kernel wider second attempt
   int64_t last_graph_pairs = 0;  // distances the last rpt_knn_graph_* call evaluated
   void* refine_state_dev = nullptr;  // graph_refine.hip: the last rpt_knn_graph_refine_* call's flag and counters
@@ -242,8 +246,8 @@ struct rpt_ctx {
   std::vector<rpt_prof_span> spans;
   std::vector<hipEvent_t> prof_events;  // resolved spans' events, reused (creating a pair per span
                                         // cost ~5 us: 0.07 ms of a profiled C2 build)
-  double prof_ms[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0};
-  int64_t prof_n[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0};
+  double prof_ms[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0, 0};
+  int64_t prof_n[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace rpt {
@@ -399,6 +403,14 @@ int32_t candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, int64_t* o
                    int32_t* ids_host, int64_t cap, int64_t* total);
 int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
                 int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+// the vote threshold over the general kernels (knn.hip knn_vote, knn_vote.hip): arguments checked by the
+// caller; flags: 0 or one of RPT_KNN_METRIC_COSINE / _INNER / _REFERENCE
+int32_t knn_vote_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                     int32_t k, int32_t v, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                     int32_t* count_dev);
+// rpt_candidates' protocol for the voted lists; counts_host may be null
+int32_t vote_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, int32_t v, int64_t* off_host,
+                        int32_t* ids_host, int32_t* counts_host, int64_t cap, int64_t* total);
 int32_t knn_merge_dev(rpt_ctx* ctx, const int32_t* ids_dev, const double* dist_dev,
                       const int32_t* count_dev, int64_t shard_stride, int32_t G, int64_t nq,
                       int32_t k, int32_t flags, int32_t* out_ids, double* out_dist,

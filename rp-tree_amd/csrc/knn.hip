@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "common.h"
+#include "knn_vote.h"
 
 namespace rpt {
 namespace {
@@ -4798,6 +4800,224 @@ static int32_t knn_general(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
   }
   RPT_HIP(stream_sync(ctx->stream));  // the plan's buffers are released on return
   return RPT_OK;
+}
+
+// ---- the vote threshold over the general kernels (rpt_knn_vote_*, rpt_vote_candidates_host) ----
+// make_plan, then knn_vote.hip's vote-select step turns every query's leaf ranges into ONE range of
+// a scratch id array (the ids at least v trees propose, ascending), then the launcher of the (row
+// layout, dtype, distance) ranks those lists as it ranks any plan: perm := the voted ids, T := 1, no
+// duplicate rule (the ids are distinct, so candidate position order is id order).
+static_assert(sizeof(Range) == sizeof(VoteRange) && offsetof(Range, poff) == offsetof(VoteRange, poff) &&
+                  offsetof(Range, n) == offsetof(VoteRange, n) && offsetof(Range, pos) == offsetof(VoteRange, pos),
+              "knn_vote.h restates Range");
+
+// Words of id and sort slabs one slice may hold (1 GiB; a single query above it is a slice of its
+// own).  Fixed: scratch is sized from the plan and the options, never from the free memory.
+constexpr int64_t kVoteBudgetWords = (int64_t)1 << 28;
+
+struct VoteWork {
+  QueryPlan pl;
+  std::vector<int64_t> starts;    // [nq + 1] cand_off[q * T] on the host
+  std::vector<VoteSlice> slices;
+  DevBuf<int64_t> sort_off;       // [nq]: a large query's first word in the slice's sort slab
+  DevBuf<int32_t> ids, counts, sort;
+  DevBuf<Range> vranges;
+  DevBuf<int64_t> vrng_off;
+  DevBuf<unsigned long long> total;
+  int lds_cap = kVoteLds;
+};
+
+static int64_t vote_pow2(int64_t n) {
+  int64_t p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+// the plan, the slices and their scratch (sized for the largest slice)
+static int32_t vote_prepare(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, bool want_counts, VoteWork& w) {
+  RPT_TRY(make_plan(ctx, f, q, w.pl));
+  const int64_t nq = q->n;
+  RPT_TRY(w.total.alloc(1));
+  RPT_HIP(hipMemsetAsync(w.total.p, 0, 8, ctx->stream));
+  if (nq == 0) return RPT_OK;
+  w.lds_cap = ctx->opt.knn_vote_lds > 0 && ctx->opt.knn_vote_lds < kVoteLds ? (int)ctx->opt.knn_vote_lds : kVoteLds;
+  const int64_t max_q = ctx->opt.knn_vote_slice > 0 ? ctx->opt.knn_vote_slice : 0x7fffffff;
+  DevBuf<int64_t> starts_dev;
+  RPT_TRY(starts_dev.alloc((size_t)nq + 1));
+  RPT_TRY(vote_query_starts(ctx, w.pl.cand_off.p, f->T, nq, starts_dev.p));
+  w.starts.resize((size_t)nq + 1);
+  RPT_HIP(hipMemcpyAsync(w.starts.data(), starts_dev.p, (size_t)(nq + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  RPT_HIP(stream_sync(ctx->stream));
+  std::vector<int64_t> so((size_t)nq, 0);
+  VoteSlice cur;
+  int64_t max_cand = 1, max_sort = 1, max_ns = 1;
+  auto close = [&]() {
+    if (cur.ns == 0) return;
+    w.slices.push_back(cur);
+    max_cand = std::max(max_cand, cur.cand_words);
+    max_sort = std::max(max_sort, cur.sort_words);
+    max_ns = std::max(max_ns, cur.ns);
+  };
+  for (int64_t i = 0; i < nq; ++i) {
+    const int64_t nc = w.starts[i + 1] - w.starts[i];
+    RPT_ARG(nc <= 0x7fffffff, "a query has more candidates than an int32 holds");
+    const int64_t sw = nc > w.lds_cap ? vote_pow2(nc) : 0;
+    if (cur.ns > 0 && (cur.ns >= max_q || cur.cand_words + cur.sort_words + nc + sw > kVoteBudgetWords)) {
+      close();
+      cur = VoteSlice();
+    }
+    if (cur.ns == 0) cur.q0 = i;
+    so[i] = cur.sort_words;
+    cur.ns += 1;
+    cur.cand_words += nc;
+    cur.sort_words += sw;
+    if (sw == 0 && nc > 0) cur.lds_words = std::max(cur.lds_words, (int)vote_pow2(nc));
+  }
+  close();
+  RPT_TRY(w.sort_off.alloc((size_t)nq));
+  RPT_HIP(hipMemcpyAsync(w.sort_off.p, so.data(), (size_t)nq * 8, hipMemcpyHostToDevice, ctx->stream));
+  RPT_HIP(stream_sync(ctx->stream));  // (so is a local)
+  RPT_TRY(w.ids.alloc((size_t)max_cand));
+  if (want_counts) RPT_TRY(w.counts.alloc((size_t)max_cand));
+  RPT_TRY(w.sort.alloc((size_t)max_sort));
+  RPT_TRY(w.vranges.alloc((size_t)max_ns));
+  RPT_TRY(w.vrng_off.alloc((size_t)max_ns + 1));
+  return RPT_OK;
+}
+
+static int32_t vote_slice_select(rpt_ctx* ctx, rpt_forest* f, VoteWork& w, const VoteSlice& sl, int v,
+                                 bool want_counts) {
+  ProfScope ps(ctx, RPT_PROF_KNN_VOTE);
+  return vote_select(ctx, f->perm.p, reinterpret_cast<const VoteRange*>(w.pl.ranges.p), w.pl.rng_off.p,
+                     w.pl.cand_off.p, f->T, sl, v, w.lds_cap, w.sort_off.p, w.sort.p, w.ids.p,
+                     want_counts ? w.counts.p : nullptr, reinterpret_cast<VoteRange*>(w.vranges.p), w.vrng_off.p,
+                     w.total.p);
+}
+
+static int32_t vote_read_total(rpt_ctx* ctx, VoteWork& w) {
+  unsigned long long t = 0;
+  RPT_HIP(hipMemcpyAsync(&t, w.total.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  RPT_HIP(stream_sync(ctx->stream));
+  ctx->last_voted = (int64_t)t;
+  return RPT_OK;
+}
+
+int32_t knn_vote_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q, int32_t k,
+                     int32_t v, int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  RPT_ARG(k <= kBuf / 2, "k too large for the LDS merge buffer");
+  RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
+  ctx->last_uncertified = 0;
+  ctx->metric_unc_pending = false;
+  ctx->last_retries = 0;
+  ctx->last_tier = 0;
+  ctx->last_voted = 0;
+  VoteWork w;
+  RPT_TRY(vote_prepare(ctx, f, q, false, w));
+  ctx->last_candidates = w.pl.total_cand;
+  if (q->n == 0) return RPT_OK;
+  const int metric = flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER);
+  const int refm = (flags & RPT_KNN_METRIC_REFERENCE) ? 1 : 0;
+  DevBuf<int32_t> unc;  // the queries the exact kernels answer again
+  size_t max_ns = 1;
+  for (const VoteSlice& sl : w.slices) max_ns = std::max(max_ns, (size_t)sl.ns);
+  RPT_TRY(unc.alloc(max_ns));
+  int64_t uncertified = 0;
+  for (size_t si = 0; si < w.slices.size(); ++si) {
+    const VoteSlice& sl = w.slices[si];
+    RPT_TRY(vote_slice_select(ctx, f, w, sl, v, false));
+    // the slice's queries as a dataset of their own (a view: nothing is owned, no cache is read)
+    rpt_dataset qv = *q;
+    qv.owns = false;
+    qv.n = sl.ns;
+    if (q->csr) qv.rowptr = q->rowptr + sl.q0;  // (rowptr holds absolute offsets into col / val)
+    else qv.X = static_cast<char*>(q->X) + (size_t)sl.q0 * q->d * dtype_size(q->dtype);
+    int32_t* ids = ids_dev + sl.q0 * k;
+    double* dist = dist_dev + sl.q0 * k;
+    int32_t* cnt = count_dev + sl.q0;
+    const int32_t* perm = w.ids.p;
+    const Range* rg = w.vranges.p;
+    const int64_t* ro = w.vrng_off.p;
+    ctx->last_uncertified = 0;
+    ctx->metric_unc_pending = false;
+    if (data->csr && metric) {
+      RPT_TRY(launch_metric_csr(ctx, data, &qv, perm, rg, ro, 1, 0, k, 0, metric, unc.p, ids, dist, cnt));
+    } else if (data->csr) {
+      const size_t smem = topk_smem(data->d, 8);
+      ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
+      if (data->dtype == RPT_F64)
+        RPT_HIP(launch_dyn(topk_csr_kernel<double>, dim3((unsigned)qv.n), dim3(256), smem, ctx->stream, data->rowptr,
+                           data->col, (const double*)data->val, data->nnz, data->d, qv.rowptr, qv.col,
+                           (const double*)qv.val, perm, rg, ro, 1, k, 0, refm, ids, dist, cnt));
+      else
+        RPT_HIP(launch_dyn(topk_csr_kernel<float>, dim3((unsigned)qv.n), dim3(256), smem, ctx->stream, data->rowptr,
+                           data->col, (const float*)data->val, data->nnz, data->d, qv.rowptr, qv.col,
+                           (const float*)qv.val, perm, rg, ro, 1, k, 0, refm, ids, dist, cnt));
+    } else if (metric) {
+      RPT_TRY(launch_metric(ctx, data, &qv, perm, rg, ro, 1, 0, k, 0, metric, unc.p, ids, dist, cnt));
+    } else if (data->dtype == RPT_F64) {
+      RPT_TRY(launch_l2_f64(ctx, data, &qv, perm, rg, ro, 1, 0, k, 0, unc.p, ids, dist, cnt));
+    } else if (data->dtype == RPT_F32) {
+      RPT_TRY(launch_topk_dense<float>(ctx, data, &qv, perm, rg, ro, 1, 0, k, 0, ids, dist, cnt));
+    } else {
+      RPT_TRY(launch_topk_dense<__hip_bfloat16>(ctx, data, &qv, perm, rg, ro, 1, 0, k, 0, ids, dist, cnt));
+    }
+    if (w.slices.size() > 1) {  // the launchers count per launch: add the slices up
+      if (ctx->metric_unc_pending) {
+        unsigned long long n = 0;
+        RPT_HIP(hipMemcpyAsync(&n, ctx->metric_unc_dev, 8, hipMemcpyDeviceToHost, ctx->stream));
+        RPT_HIP(stream_sync(ctx->stream));
+        uncertified += (int64_t)n;
+      } else {
+        uncertified += ctx->last_uncertified;
+      }
+    }
+  }
+  if (w.slices.size() > 1) {
+    ctx->last_uncertified = uncertified;
+    ctx->metric_unc_pending = false;
+  }
+  return vote_read_total(ctx, w);  // synchronises: the scratch is released on return
+}
+
+int32_t vote_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, int32_t v, int64_t* off_host,
+                        int32_t* ids_host, int32_t* counts_host, int64_t cap, int64_t* total) {
+  const bool fill = ids_host != nullptr;
+  const bool want_counts = fill && counts_host != nullptr;
+  ctx->last_voted = 0;
+  VoteWork w;
+  RPT_TRY(vote_prepare(ctx, f, q, want_counts, w));
+  ctx->last_candidates = w.pl.total_cand;
+  std::vector<Range> hr;
+  std::vector<int32_t> hids, hcnt;
+  int64_t at = 0;
+  if (off_host) off_host[0] = 0;
+  for (const VoteSlice& sl : w.slices) {
+    RPT_TRY(vote_slice_select(ctx, f, w, sl, v, want_counts));
+    hr.resize((size_t)sl.ns);
+    RPT_HIP(hipMemcpyAsync(hr.data(), w.vranges.p, (size_t)sl.ns * sizeof(Range), hipMemcpyDeviceToHost, ctx->stream));
+    if (fill && sl.cand_words > 0) {
+      hids.resize((size_t)sl.cand_words);
+      RPT_HIP(hipMemcpyAsync(hids.data(), w.ids.p, (size_t)sl.cand_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if (want_counts) {
+        hcnt.resize((size_t)sl.cand_words);
+        RPT_HIP(hipMemcpyAsync(hcnt.data(), w.counts.p, (size_t)sl.cand_words * 4, hipMemcpyDeviceToHost,
+                               ctx->stream));
+      }
+    }
+    RPT_HIP(stream_sync(ctx->stream));
+    for (int64_t i = 0; i < sl.ns; ++i) {
+      const Range& r = hr[(size_t)i];
+      if (fill && r.n > 0) {
+        RPT_ARG(at + r.n <= cap, "ids capacity too small");
+        std::memcpy(ids_host + at, hids.data() + r.poff, (size_t)r.n * 4);
+        if (want_counts) std::memcpy(counts_host + at, hcnt.data() + r.poff, (size_t)r.n * 4);
+      }
+      at += r.n;
+      if (off_host) off_host[sl.q0 + i + 1] = at;
+    }
+  }
+  *total = at;
+  return vote_read_total(ctx, w);
 }
 
 int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,

@@ -349,6 +349,60 @@ inline std::vector<int32_t> candidates(const RPForest& tts, int t, const SVector
   return std::vector<int32_t>(ids.begin() + off[(size_t)t], ids.begin() + off[(size_t)t + 1]);
 }
 
+// ---- the vote threshold (rpt_knn_vote_host, rpt_vote_candidates_host) ----
+// knnVote: only the ids that at least v trees propose are ranked, each once, by (distance, id) ->
+// (distance, point id).  Every row layout and Metric, batch and streamed forests, any number of
+// trees and of candidates, k up to 1024; the distances are knn's for the same data and metric.
+// reference_metric (SVector rows, Metric::L2): the reference's truncating metricSSL2.
+template <class Q>
+inline std::vector<std::pair<double, int32_t>> knnVoteVia(const RPForest& tts, const Q& qs, int k, int v,
+                                                          int32_t flags) {
+  std::vector<int32_t> ids((size_t)k);
+  std::vector<double> dist((size_t)k);
+  int32_t cnt = 0;
+  check(rpt_knn_vote_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(), k, v, flags, ids.data(),
+                          dist.data(), &cnt));
+  std::vector<std::pair<double, int32_t>> out;
+  for (int i = 0; i < cnt; ++i) out.push_back({dist[(size_t)i], ids[(size_t)i]});
+  return out;
+}
+inline std::vector<std::pair<double, int32_t>> knnVote(const RPForest& tts, int k, int v, const DVector& q,
+                                                       Metric metric = Metric::L2) {
+  std::vector<DVector> qv{q};
+  Dataset qs(*tts.ctx, qv);
+  return knnVoteVia(tts, qs, k, v, metric_flags(metric));
+}
+inline std::vector<std::pair<double, int32_t>> knnVote(const RPForest& tts, int k, int v, const SVector& q,
+                                                       Metric metric = Metric::L2, bool reference_metric = false) {
+  std::vector<SVector> qv{q};
+  Dataset qs(*tts.ctx, qv, tts.data->d);
+  return knnVoteVia(tts, qs, k, v, metric_flags(metric) | (reference_metric ? RPT_KNN_METRIC_REFERENCE : 0));
+}
+
+// voteCandidates: (id, number of trees that propose it) of the ids with at least v votes, ascending
+// (the reference's commented-out counts / keepCounts, RPTree.hs:464-478)
+template <class Q>
+inline std::vector<std::pair<int32_t, int32_t>> voteCandidatesVia(const RPForest& tts, const Q& qs, int v) {
+  int64_t off[2] = {0, 0}, total = 0;
+  check(rpt_vote_candidates_host(tts.ctx->get(), tts.get(), qs.get(), v, off, nullptr, nullptr, 0, &total));
+  std::vector<int32_t> ids((size_t)(total > 0 ? total : 1)), counts(ids.size());
+  check(rpt_vote_candidates_host(tts.ctx->get(), tts.get(), qs.get(), v, off, ids.data(), counts.data(), total,
+                                 &total));
+  std::vector<std::pair<int32_t, int32_t>> out;
+  for (int64_t i = 0; i < total; ++i) out.push_back({ids[(size_t)i], counts[(size_t)i]});
+  return out;
+}
+inline std::vector<std::pair<int32_t, int32_t>> voteCandidates(const RPForest& tts, int v, const DVector& q) {
+  std::vector<DVector> qv{q};
+  Dataset qs(*tts.ctx, qv);
+  return voteCandidatesVia(tts, qs, v);
+}
+inline std::vector<std::pair<int32_t, int32_t>> voteCandidates(const RPForest& tts, int v, const SVector& q) {
+  std::vector<SVector> qv{q};
+  Dataset qs(*tts.ctx, qv, tts.data->d);
+  return voteCandidatesVia(tts, qs, v);
+}
+
 // ---- evaluation: exhaustive kNN and recallWith (RPTree.hs:259-282), dense and SVector data ----
 // flags: 0, metric_flags(Metric::Cosine / Inner) on dense data, RPT_KNN_METRIC_REFERENCE (the
 // reference's truncating metricSSL2) on SVector data

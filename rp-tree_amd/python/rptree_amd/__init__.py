@@ -45,6 +45,7 @@ __all__ = [
     "graphSearch", "graphSearchDev", "graphSearchLast", "graphSearchSV", "graphSearchSVDev",
     "graphPrepare", "graphPrepareDev", "graphPrepareLast", "graphPrepareSV", "graphPrepareSVDev",
     "graphSearchMetricSV", "graphSearchMetricSVDev", "graphPrepareMetricSV", "graphPrepareMetricSVDev",
+    "knnVote", "knnVoteDev", "voteCandidates", "knnVoteLast",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -829,6 +830,73 @@ def knnBatch(k, forest, qs, dedup=False, vote=0, reference_metric=False, metric=
     entry = lib().rpt_knn_csr_metric_host if mflag and forest.data.is_csr else lib().rpt_knn_host
     check(entry(ctx._h, forest._h, forest.data._h, qd._h, int(k), flags, _vp(ids), _vp(dist), _vp(cnt)))
     return ids, dist, cnt
+
+
+def _vote_flags(forest, metric, reference_metric):
+    mflag = _metric_flag(metric)
+    if mflag and reference_metric:
+        raise ValueError("reference_metric is an L2 metric: not with metricCosine / metricInner")
+    if reference_metric and not forest.data.is_csr:
+        raise ValueError("reference_metric is the SVector rows' metric")
+    return mflag | (RPT_KNN_METRIC_REFERENCE if reference_metric else 0)
+
+
+def knnVote(k, forest, qs, v, metric=None, reference_metric=False):
+    """Vote-threshold knn for a batch of queries -> (ids[nq][k], dist[nq][k], count[nq])
+    (rpt_knn_vote_host): only the ids that at least v trees propose are ranked, each once, by
+    (distance, id).  Every row layout (dense f64 / f32 / bf16, SVector f64 / f32), every distance
+    (metric: None / metricL2, metricCosine, metricInner; reference_metric: SVector rows by the
+    reference's truncating metricSSL2), batch and streamed forests, any number of trees and of
+    candidates, k up to 1024.  The distances are those of knnBatch for the same data and metric.
+    qs: as knnBatch's (arrays, SVectors, a CSR tuple, a Dataset)."""
+    ctx = forest.ctx
+    flags = _vote_flags(forest, metric, reference_metric)
+    qd, nq = _query_dataset(ctx, forest.data, qs)
+    ids = np.empty((nq, k), dtype=np.int32)
+    dist = np.empty((nq, k), dtype=np.float64)
+    cnt = np.empty(nq, dtype=np.int32)
+    check(lib().rpt_knn_vote_host(ctx._h, forest._h, forest.data._h, qd._h, int(k), int(v), flags,
+                                  _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnVoteDev(k, forest, queries, v, ids_ptr, dist_ptr, count_ptr, metric=None, reference_metric=False):
+    """knnVote on device arrays (rpt_knn_vote_dev): queries is a Dataset, the outputs (int32 [nq][k],
+    float64 [nq][k], int32 [nq]) device addresses.  Returns synchronised; whatever filled the
+    queries must have finished (see Dataset.dense_device)."""
+    ctx = forest.ctx
+    flags = _vote_flags(forest, metric, reference_metric)
+    check(lib().rpt_knn_vote_dev(ctx._h, forest._h, forest.data._h, queries._h, int(k), int(v), flags,
+                                 C.c_void_p(ids_ptr), C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
+
+
+def voteCandidates(forest, qs, v):
+    """-> (off[nq+1], ids, counts): the voted list of query i = ids[off[i]:off[i+1]], the ids that at
+    least v trees propose, ascending, each once; counts: the number of trees that propose each (the
+    reference's commented-out counts / keepCounts, RPTree.hs:464-478; rpt_vote_candidates_host)."""
+    ctx = forest.ctx
+    qd, nq = _query_dataset(ctx, forest.data, qs)
+    total = C.c_int64()
+    off = np.empty(nq + 1, dtype=np.int64)
+    check(lib().rpt_vote_candidates_host(ctx._h, forest._h, qd._h, int(v), _vp(off), None, None, 0,
+                                         C.byref(total)))
+    ids = np.empty(max(total.value, 1), dtype=np.int32)
+    counts = np.empty(max(total.value, 1), dtype=np.int32)
+    check(lib().rpt_vote_candidates_host(ctx._h, forest._h, qd._h, int(v), _vp(off), _vp(ids), _vp(counts),
+                                         total.value, C.byref(total)))
+    return off, ids[:total.value], counts[:total.value]
+
+
+def knnVoteLast(ctx=None):
+    """(candidates, voted, uncertified) of the last knnVote / knnVoteDev call: the candidate entries
+    of all trees, the voted ids (= distances evaluated), the queries answered again by an exact
+    kernel."""
+    ctx = ctx or default_context()
+    c, v, u = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().rpt_knn_last_candidates(ctx._h, C.byref(c)))
+    check(lib().rpt_knn_last_voted(ctx._h, C.byref(v)))
+    check(lib().rpt_knn_last_uncertified(ctx._h, C.byref(u)))
+    return int(c.value), int(v.value), int(u.value)
 
 
 def _graph_flag(accumulate):

@@ -130,6 +130,10 @@ SYMBOLS = {
     "rpt_brute_knn_csr_metric_host": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "rpt_brute_knn_csr_metric_dev": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "rpt_recall_hits_csr_metric_host": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
+    "rpt_knn_vote_host": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rpt_knn_vote_dev": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rpt_vote_candidates_host": (i32, [vp, vp, vp, i32, vp, vp, vp, i64, p_i64]),
+    "rpt_knn_last_voted": (i32, [vp, p_i64]),
 }
 
 
