@@ -7,13 +7,13 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchAllowHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
 import Control.Monad (when)
 import Data.Int (Int8, Int32, Int64)
-import Data.Word (Word64)
+import Data.Word (Word32, Word64)
 import Foreign.C.String (CString, peekCString)
 import Foreign.Marshal.Alloc (alloca)
 import Foreign.Ptr (Ptr, nullPtr)
@@ -58,6 +58,7 @@ foreign import ccall safe "rpt_knn_graph_refine_csr_host" c_knn_graph_refine_csr
 foreign import ccall safe "rpt_knn_graph_csr_metric_host" c_knn_graph_csr_metric_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_graph_refine_csr_metric_host" c_knn_graph_refine_csr_metric_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_host" c_graph_search_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_graph_search_allow_host" c_graph_search_allow_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Ptr Word32 -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_csr_host" c_graph_search_csr_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_host" c_graph_prepare_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_csr_host" c_graph_prepare_csr_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
@@ -406,6 +407,24 @@ graphSearchMetricSVHIP ctx ds qs m nq kg (gids, gcount) s seeds k ef = do
   VS.unsafeWith gids (\pg -> VS.unsafeWith gcount (\pc -> VS.unsafeWith seeds (\ps ->
     VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
       c_graph_search_csr_metric_host ctx ds qs (fromIntegral kg) pg pc (fromIntegral s) ps (fromIntegral k) (fromIntegral ef) (metricFlag m) 0 a b)))))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | 'graphSearchHIP' among SOME of the points (rpt_graph_search_allow_host): @allow@ holds
+-- ceil(n \/ 32) words, id i allowed when bit (i .&. 31) of word (i `shiftR` 5) is set; 'Nothing' allows
+-- every id.  @ds@ and @qs@ are both dense or both CSR, under any 'Metric'.  @ef@ counts ALLOWED beam
+-- entries only; @width@ in [ef, 1024] is the most entries the beam may hold, allowed or not; a beam
+-- with ef allowed entries ends at its ef-th allowed entry and disallowed entries are expanded like any
+-- other.  The answer is the first k allowed entries.  With every id allowed it is 'graphSearchHIP's \/
+-- 'graphSearchMetricSVHIP's bit for bit; with width = ef it is the allowed entries of the unfiltered beam.
+graphSearchAllowHIP :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Metric -> Int -> Int
+                    -> (VS.Vector Int32, VS.Vector Int32) -> Int -> VS.Vector Int32 -> Maybe (VS.Vector Word32)
+                    -> Int -> Int -> Int -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+graphSearchAllowHIP ctx ds qs m nq kg (gids, gcount) s seeds allow k ef width = do
+  ids <- VSM.new (nq * k); dist <- VSM.new (nq * k); cnt <- VSM.new nq
+  let withAllow f = maybe (f nullPtr) (`VS.unsafeWith` f) allow
+  VS.unsafeWith gids (\pg -> VS.unsafeWith gcount (\pc -> VS.unsafeWith seeds (\ps -> withAllow (\pa ->
+    VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
+      c_graph_search_allow_host ctx ds qs (fromIntegral kg) pg pc (fromIntegral s) ps pa (fromIntegral k) (fromIntegral ef) (fromIntegral width) (metricFlag m) 0 a b))))))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | A kNN graph made ready for 'graphSearchHIP' (rpt_graph_prepare_host), PyNNDescent's search graph.

@@ -700,6 +700,73 @@ int32_t rpt_graph_search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_d
                               int32_t* count_host);
 int32_t rpt_graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
 
+/* ---- query the kNN graph over an allow-list of ids ----
+ * rpt_graph_search_allow_* is the beam search of rpt_graph_search_* among SOME of the points: a
+ * tombstone bitmap after deletions, the rows of one tenant.  The parameter list is
+ * rpt_graph_search_*'s with `allow` behind the seeds and `width` behind ef.  One pair of entry
+ * points serves dense data (f64, f32, bf16; dist as rpt_graph_search_*) and CSR data (f64, f32; dist
+ * as rpt_graph_search_csr_metric_*, whose metric 0 is rpt_graph_search_csr_*) under `metric` 0,
+ * RPT_KNN_METRIC_COSINE and RPT_KNN_METRIC_INNER; data and queries are both dense or both CSR.
+ *   allow       a bitmap of n bits in ceil(n / 32) 32-bit words: id i is allowed when bit i & 31 of
+ *               word i >> 5 is set.  Bits at positions >= n are ignored.  A null pointer means every
+ *               id is allowed.  One bitmap serves the whole batch.
+ *   width       in [ef, RPT_GRAPH_SEARCH_MAX_WIDTH]: the most entries the beam may hold, allowed or
+ *               not.
+ *   ef          in [k, RPT_GRAPH_SEARCH_MAX_EF], as before; it now counts ALLOWED entries only.
+ * The distance, the total order ((distance, id), NaN behind every number, NaNs among themselves by
+ * id), the seeds, the offers and "the first unexpanded entry" are word for word those of
+ * rpt_graph_search_*.  Three things change.
+ *   Cut         For a set U of (distance, id) entries sorted in the order, t_a is the ef-th allowed
+ *               entry of U, if it has one, and t_w the width-th entry of U, if it has one.  cut(U)
+ *               is every entry of U that is not after min(t_a, t_w); with neither, cut(U) = U.  So
+ *               a beam with ef allowed entries ENDS at its ef-th allowed entry, disallowed entries
+ *               behind it go too, and a beam with fewer allowed entries holds up to `width`
+ *               entries, mostly disallowed ones: the frontier it walks through.
+ *   Offer       B <- cut(B u {(dist(q, v), v) : v in S}), every id once, new entries unexpanded.
+ *               Disallowed entries are expanded like any other: the traversal walks through them.
+ *               Seeds need not be allowed.
+ *   Answer      the first k allowed entries of B, count = min(k, allowed entries of B); unused slots
+ *               hold id -1 and distance +inf.
+ * Three properties:
+ *   Consistency  cut(cut(A) u S) = cut(A u S): the entry at min(t_a, t_w) is itself in the beam and
+ *               witnesses the limit, and both limits only tighten as entries are added.  Hence B is
+ *               always cut of everything offered so far: an id rejected or evicted once can never
+ *               enter later, a point is expanded at most once, the loop ends after at most n
+ *               expansions, and the visited filter (an exact visited set, a lossy one, or none;
+ *               graph_search_nofilter) changes no answer and not `expansions`.  (The rule "the
+ *               longest sorted prefix with at most width entries and at most ef allowed ones" is
+ *               NOT this one: it forgets a rejected allowed entry and lets later, farther entries
+ *               in, so its answer depends on the visited set.)
+ *   Identity    With every id allowed (a null bitmap or all ones) t_a is the ef-th entry and
+ *               width >= ef, so B is the first ef: the ids, the distance bits, the counts and
+ *               `expansions` are those of rpt_graph_search_* / _csr_* / _csr_metric_* on the same
+ *               inputs, whatever `width` is.  `evaluated` keeps its defined bounds; it is equal too
+ *               under graph_search_nofilter = 1 (the hash is sized by width).
+ *   width = ef  is post-filtering: the answer is the allowed entries of the unfiltered beam.
+ * One wave answers a query and no atomics touch a beam: the same bits whatever the launch shape and
+ * whatever graph_search_nofilter and graph_search_csr_stream are set to.  Every valid combination of
+ * arguments launches: the beam, the filter, the offer's rows and the resident query take up to about
+ * 46 KB of LDS per wave, and a workgroup is 4, 2 or 1 waves, whichever keeps the most waves on a
+ * compute unit.  rpt_graph_search_last reports these calls too.
+ * Errors: those of rpt_graph_search_* (a dense / CSR pair, any other `metric` value, both metric bits
+ * together, RPT_KNN_METRIC_REFERENCE, k, ef, s or kg out of range, flags other than 0: RPT_E_ARG), and
+ * width outside [ef, RPT_GRAPH_SEARCH_MAX_WIDTH]: RPT_E_ARG.  CSR data is NOT refused here.  Always
+ * valid: n = 0, nq = 0, an all-zero bitmap (every count is 0), a null bitmap.  _host validates the
+ * graph and the seeds as rpt_graph_search_host does, reads and uploads ceil(n / 32) words of
+ * allow_host, and synchronises; _dev borrows device arrays, does not synchronise and does NOT
+ * validate.  A refused call leaves the context usable. */
+#define RPT_GRAPH_SEARCH_MAX_WIDTH 1024
+int32_t rpt_graph_search_allow_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                   int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev,
+                                   int32_t s, const int32_t* seeds_dev, const uint32_t* allow_dev,
+                                   int32_t k, int32_t ef, int32_t width, int32_t metric, int32_t flags,
+                                   int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+int32_t rpt_graph_search_allow_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                    int32_t kg, const int32_t* gids_host, const int32_t* gcount_host,
+                                    int32_t s, const int32_t* seeds_host, const uint32_t* allow_host,
+                                    int32_t k, int32_t ef, int32_t width, int32_t metric, int32_t flags,
+                                    int32_t* ids_host, double* dist_host, int32_t* count_host);
+
 /* ---- query the kNN graph on SVector (CSR) rows, under L2 ----
  * rpt_graph_search_csr_* is rpt_graph_search_* for a CSR data set and CSR queries (rpt_dataset_csr_*,
  * f64 or f32 values, the same d and the same dtype); the parameter lists are the dense ones.  With

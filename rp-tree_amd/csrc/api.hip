@@ -1468,9 +1468,12 @@ int32_t rpt_knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* update
 // ---- beam search over a kNN graph -------------------------------------------------------------
 namespace {
 // Rows::Csr: the rpt_graph_search_csr_* entry points (CSR data and queries, L2 only); Rows::CsrMetric:
-// the rpt_graph_search_csr_metric_* ones (the same, under every metric)
+// the rpt_graph_search_csr_metric_* ones (the same, under every metric).  allow: the
+// rpt_graph_search_allow_* ones, which take dense and CSR data alike under every metric (the caller
+// passes the Rows of the data set) and a beam of `width` entries
 int32_t check_search(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
-                     int32_t s, int32_t k, int32_t ef, int32_t metric, int32_t flags, Rows rows) {
+                     int32_t s, int32_t k, int32_t ef, int32_t metric, int32_t flags, Rows rows,
+                     bool allow = false, int32_t width = 0) {
   RPT_ARG(ctx && data && queries, "NULL argument");
   RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
   RPT_TRY(check_graph_metric(metric));
@@ -1494,6 +1497,9 @@ int32_t check_search(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q
   RPT_ARG(ef >= k, "ef must be at least k");
   RPT_ARG(ef <= RPT_GRAPH_SEARCH_MAX_EF, "ef must be at most 256 (RPT_GRAPH_SEARCH_MAX_EF)");
   RPT_ARG(data->n <= 0x7fffffff, "graph too large");
+  if (allow)
+    RPT_ARG(width >= ef && width <= RPT_GRAPH_SEARCH_MAX_WIDTH,
+            "width must be in [ef, 1024] (RPT_GRAPH_SEARCH_MAX_WIDTH)");
   return RPT_OK;
 }
 
@@ -1525,25 +1531,29 @@ int32_t check_search_arrays(int64_t n, int64_t nq, int32_t kg, const int32_t* gi
 int32_t search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
                    const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s, const int32_t* seeds_dev,
                    int32_t k, int32_t ef, int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
-                   int32_t* count_dev, Rows rows) {
+                   int32_t* count_dev, Rows rows, bool allow = false, int32_t width = 0,
+                   const uint32_t* allow_dev = nullptr) {
   if (ctx) dev_set_stream(ctx->stream);
-  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, rows));
+  if (allow && data) rows = data->csr ? Rows::CsrMetric : Rows::Dense;
+  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, rows, allow, width));
   RPT_ARG(data->n == 0 || (gids_dev && gcount_dev), "NULL graph arrays");
   RPT_ARG(queries->n == 0 || (seeds_dev && ids_dev && dist_dev && count_dev), "NULL seeds or output");
   RPT_HIP(hipSetDevice(ctx->device));
   if (rows != Rows::Dense)
     return graph_search_csr_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric,
-                                ids_dev, dist_dev, count_dev);
+                                ids_dev, dist_dev, count_dev, allow ? width : 0, allow_dev);
   return graph_search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric,
-                          ids_dev, dist_dev, count_dev);
+                          ids_dev, dist_dev, count_dev, allow ? width : 0, allow_dev);
 }
 
 int32_t search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
                     const int32_t* gids_host, const int32_t* gcount_host, int32_t s,
                     const int32_t* seeds_host, int32_t k, int32_t ef, int32_t metric, int32_t flags,
-                    int32_t* ids_host, double* dist_host, int32_t* count_host, Rows rows) {
+                    int32_t* ids_host, double* dist_host, int32_t* count_host, Rows rows, bool allow = false,
+                    int32_t width = 0, const uint32_t* allow_host = nullptr) {
   if (ctx) dev_set_stream(ctx->stream);
-  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, rows));
+  if (allow && data) rows = data->csr ? Rows::CsrMetric : Rows::Dense;
+  RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, rows, allow, width));
   const int64_t n = data->n, nq = queries->n;
   RPT_ARG(n == 0 || (gids_host && gcount_host), "NULL graph arrays");
   RPT_ARG(nq == 0 || (seeds_host && ids_host && dist_host && count_host), "NULL seeds or output");
@@ -1560,8 +1570,14 @@ int32_t search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* qu
     RPT_HIP(hipMemcpy(gcnt.p, gcount_host, (size_t)n * 4, hipMemcpyHostToDevice));
   }
   if (nq) RPT_HIP(hipMemcpy(seeds.p, seeds_host, (size_t)nq * s * 4, hipMemcpyHostToDevice));
+  DevBuf<uint32_t> bitmap;  // the allow-list's ceil(n / 32) words
+  const size_t words = allow_host ? (size_t)((n + 31) / 32) : 0;
+  if (words) {
+    RPT_TRY(bitmap.alloc(words));
+    RPT_HIP(hipMemcpy(bitmap.p, allow_host, words * 4, hipMemcpyHostToDevice));
+  }
   RPT_TRY(search_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, metric, flags, out.ids.p,
-                     out.dist.p, out.cnt.p, rows));
+                     out.dist.p, out.cnt.p, rows, allow, width, words ? bitmap.p : nullptr));
   RPT_HIP(stream_sync(ctx->stream));
   return out.download(ids_host, dist_host, count_host);
 }
@@ -1628,6 +1644,28 @@ int32_t rpt_graph_search_csr_metric_host(rpt_ctx* ctx, const rpt_dataset* data, 
   return guarded([&]() -> int32_t {
     return search_host(ctx, data, queries, kg, gids_host, gcount_host, s, seeds_host, k, ef, metric, flags,
                        ids_host, dist_host, count_host, Rows::CsrMetric);
+  });
+}
+
+int32_t rpt_graph_search_allow_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                   int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
+                                   const int32_t* seeds_dev, const uint32_t* allow_dev, int32_t k, int32_t ef,
+                                   int32_t width, int32_t metric, int32_t flags, int32_t* ids_dev,
+                                   double* dist_dev, int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    return search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric, flags,
+                      ids_dev, dist_dev, count_dev, Rows::Dense, true, width, allow_dev);
+  });
+}
+
+int32_t rpt_graph_search_allow_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                    int32_t kg, const int32_t* gids_host, const int32_t* gcount_host,
+                                    int32_t s, const int32_t* seeds_host, const uint32_t* allow_host,
+                                    int32_t k, int32_t ef, int32_t width, int32_t metric, int32_t flags,
+                                    int32_t* ids_host, double* dist_host, int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return search_host(ctx, data, queries, kg, gids_host, gcount_host, s, seeds_host, k, ef, metric, flags,
+                       ids_host, dist_host, count_host, Rows::Dense, true, width, allow_host);
   });
 }
 

@@ -466,18 +466,22 @@ int32_t knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* updates, i
 // ---- beam search over a kNN graph (graph_search.hip) -----------------------------------------
 // arguments checked by the caller (dense data and queries of one shape and dtype, kg, s, k <= 64,
 // k <= ef <= RPT_GRAPH_SEARCH_MAX_EF; metric as knn_graph_dev's); the arrays are not validated:
-// entries out of range are skipped; enqueued on the ctx stream
+// entries out of range are skipped; enqueued on the ctx stream.  width == 0: rpt_graph_search_*.
+// width in [ef, RPT_GRAPH_SEARCH_MAX_WIDTH]: rpt_graph_search_allow_* with the allow-list allow_dev
+// (ceil(n / 32) words, null = every id), which launches whatever the shape
 int32_t graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
                          const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
                          const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
-                         int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+                         int32_t* ids_dev, double* dist_dev, int32_t* count_dev, int32_t width = 0,
+                         const uint32_t* allow_dev = nullptr);
 // the same on CSR rows (graph_search_csr.hip): CSR data and queries of one d and dtype (f64 or f32
 // values); metric as knn_graph_dev's, the cosine / inner-product distances from dotS (rptree_hip.h);
 // the statistics go where graph_search_dev's go
 int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
                              int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
                              const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
-                             int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+                             int32_t* ids_dev, double* dist_dev, int32_t* count_dev, int32_t width = 0,
+                             const uint32_t* allow_dev = nullptr);
 // synchronises the stream
 int32_t graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
 // ---- a kNN graph made ready for the search (graph_prepare.hip) ---------------------------------

@@ -180,10 +180,21 @@ __device__ inline void wave_stage(const TD* __restrict__ X, int d, const int* si
 //                            full neighbourhood is overwritten (lossy)
 //   sid   R ints             the ids of the running offer that are evaluated
 // All 64 lanes of the wave call every function below together.
+//
+// The allow-list searches (rpt_graph_search_allow_*: graph_search_allow_kernel,
+// graph_search_csr_allow_kernel) run the same functions with the compile-time switch F on.  Then
+// the beam holds up to `width` entries (bd/bi of ceil(width / 64) * 64), a third array
+//   ba    bytes, as many      1 where the entry's id is in the allow-list; ids use all 31 bits and
+//                            ~id marks an expanded entry, so bi has no bit to spare
+// stands beside them, `na` counts the allowed entries, and the beam is cut(everything offered) of
+// include/rptree_hip.h: it ends at its ef-th allowed entry or at its width-th entry, whichever
+// comes first.  With F off none of this is compiled and the functions are what they were.  J is
+// the number of beam entries a lane looks after in beam_insert (ceil(width / 64) <= J).
 constexpr int kEmpty = (int)0x80000000;  // free slot of a hash of ids in LDS (never an id): the
                                          // search's filter, the refinement's candidate set
 constexpr int kProbe = 8;                // slots of the filter an id may take
 constexpr int kBeamJ = RPT_GRAPH_SEARCH_MAX_EF / 64;  // beam entries a lane looks after
+constexpr int kBeamJWide = RPT_GRAPH_SEARCH_MAX_WIDTH / 64;  // ... of an allow-list beam beyond 256
 
 struct SearchState {
   unsigned long long expansions, evaluated;
@@ -194,9 +205,11 @@ struct SearchArgs {
   int d, kg, s, k, ef;
   int R, H, qres, vec, nofilter, wave_bytes;
   int qcap, stream;  // CSR rows: entries of a query that stay in LDS, 1 = every query is streamed
+  int width;         // entries the beam may hold, allowed or not (without an allow-list: ef)
   const int32_t* gids;
   const int32_t* gcount;
   const int32_t* seeds;
+  const uint32_t* allow;  // the allow-list: bit i & 31 of word i >> 5; null = every id (F only)
   const double* rn;  // dot(x, x) of the data rows (cosine)
   const double* qn;  // ... of the queries
   int32_t* ids;
@@ -212,7 +225,37 @@ __global__ void search_begin_kernel(SearchState* st) {
   }
 }
 
+// What every search sizes the same way.  An offer holds a graph row whole and seeds come in batches
+// of the same size; the filter has eight slots per beam entry, 1 to 8 KB.
+inline void search_shape(SearchArgs& a) {
+  a.R = std::max<int>(a.kg, std::min<int>(a.s, 16));
+  a.H = 256;
+  while (a.H < 8 * a.width && a.H < 2048) a.H <<= 1;
+}
+
+// Waves per workgroup of an allow-list search, which never refuses a shape: of 4, 2 and 1 the count
+// that keeps the most waves on a CU, floor(lds / (W * wave_bytes)) workgroups of W waves each, the
+// larger count on a tie.  One wave always fits (wave_bytes stays below 64 KB by the entry points'
+// limits on kg, width and the resident query).
+inline int search_waves(int wave_bytes, int lds) {
+  int best = 1, waves = 0;
+  for (int W = 4; W >= 1; W >>= 1) {
+    const int r = (lds / (W * wave_bytes)) * W;
+    if (r > waves) {
+      waves = r;
+      best = W;
+    }
+  }
+  return best;
+}
+
 __device__ inline int beam_id(int v) { return v < 0 ? ~v : v; }
+
+// whether id v (in [0, n), or -1 on an idle lane) is in the allow-list: one 32-bit load
+__device__ inline bool beam_allowed(const SearchArgs& a, int v) {
+  if (v < 0) return false;
+  return a.allow == nullptr || ((a.allow[v >> 5] >> (v & 31)) & 1u) != 0;
+}
 
 // The next offer, a candidate per lane (-1: none): a batch of R seeds, then the graph row of the
 // first unexpanded entry, which is marked expanded.  false: no unexpanded entry is left, the search
@@ -279,59 +322,121 @@ __device__ __forceinline__ int beam_admit(const SearchArgs& a, const int* bi, in
 // The offer's entries (cd, my) of the lanes [0, nrows) into the beam of c entries, one at a time:
 // rank by ballot / popcount over the lanes' entries (lane l looks at positions l, l + 64, ...), the
 // tail shifted by one in LDS.
+// F: al says whether `my` is allowed, ba / na are the beam's allowed bits and their count.  The beam
+// is full when it holds ef allowed entries or `width` entries; either way its last entry is the
+// threshold.  An insertion makes it min(c + 1, width) entries, and when an allowed entry came in and
+// ef or more are allowed now, the beam ends at its ef-th allowed entry, found by ballot / popcount
+// over the blocks of 64 positions: the old last entry and every disallowed one between it and the new
+// ef-th go in one step.
+template <bool F = false, int J = kBeamJ>
 __device__ __forceinline__ void beam_insert(double* bd, int* bi, int& c, int ef, int nj, int lane, int nrows,
-                                            double cd, int my) {
+                                            double cd, int my, unsigned char* ba = nullptr, int width = 0,
+                                            int* na_ = nullptr, bool al = false) {
   bool v = lane < nrows;
+  const int cap = F ? width : ef;
+  int na = 0;
+  if constexpr (F) na = *na_;
   for (;;) {
-    if (c == ef) {  // a full beam: only what comes before its last entry can enter
+    int gone = 0;  // F: the allowed bit of the entry a beam of `width` entries is about to lose
+    if (F ? (na == ef || c == cap) : c == ef) {  // a full beam: only what comes before its last entry can enter
       const double td = bd[c - 1];
       const int ti = beam_id(bi[c - 1]);
       v = v && before(cd, my, td, ti);
+      if constexpr (F) gone = c == cap ? (int)ba[c - 1] : 0;
     }
     const unsigned long long m = __ballot(v);
     if (!m) break;
     const int src = __ffsll((long long)m) - 1;
     const double nd = __shfl(cd, src);
     const int ni = __shfl(my, src);
+    int nal = 0;
+    if constexpr (F) nal = __shfl((int)al, src);
     if (lane == src) v = false;
-    double ed[kBeamJ];
-    int ei[kBeamJ];
+    double ed[J];
+    int ei[J];
+    unsigned char ea[F ? J : 1];
     int p = 0;
     bool dup = false;
 #pragma unroll
-    for (int j = 0; j < kBeamJ; ++j)
+    for (int j = 0; j < J; ++j)
       if (j < nj) {
         const int pos = j * 64 + lane;
         const bool on = pos < c;
         ed[j] = on ? bd[pos] : 0.0;
         ei[j] = on ? bi[pos] : kEmpty;
+        if constexpr (F) ea[j] = on ? ba[pos] : (unsigned char)0;
         dup |= on && beam_id(ei[j]) == ni;
         p += __popcll(__ballot(on && before(ed[j], beam_id(ei[j]), nd, ni)));
       }
     if (__ballot(dup)) continue;  // the same id twice in one offer
-    const int newc = c < ef ? c + 1 : c;
+    const int newc = c < cap ? c + 1 : c;
     wave_sync();  // every entry has been read
 #pragma unroll
-    for (int j = 0; j < kBeamJ; ++j)
+    for (int j = 0; j < J; ++j)
       if (j < nj) {
         const int pos = j * 64 + lane;
         if (pos >= p && pos < c && pos + 1 < newc) {
           bd[pos + 1] = ed[j];
           bi[pos + 1] = ei[j];
+          if constexpr (F) ba[pos + 1] = ea[j];
         }
       }
     if (lane == 0) {
       bd[p] = nd;
       bi[p] = ni;
+      if constexpr (F) ba[p] = (unsigned char)nal;
     }
     wave_sync();
     c = newc;
+    if constexpr (F) {
+      na += nal - gone;
+      if (nal && na >= ef) {  // the beam ends at its ef-th allowed entry
+        int seen = 0;
+        for (int j = 0; j < nj; ++j) {
+          const int pos = j * 64 + lane;
+          const unsigned long long am = __ballot(pos < c && ba[pos] != 0);
+          const int cnt = __popcll(am);
+          if (seen + cnt >= ef) {
+            // the lane that holds the (ef - seen)-th set bit of am
+            const bool hit = ((am >> lane) & 1ULL) && __popcll(am & ((2ULL << lane) - 1)) == ef - seen;
+            c = j * 64 + __ffsll((long long)__ballot(hit));
+            break;
+          }
+          seen += cnt;
+        }
+        na = ef;
+      }
+    }
   }
+  if constexpr (F) *na_ = na;
 }
 
 // the answer of query qi: the first k of the beam, padded with id -1 and distance +inf
+// F: the first k ALLOWED entries, compacted by ballot prefix over the blocks of 64 positions
+template <bool F = false>
 __device__ __forceinline__ void beam_answer(const SearchArgs& a, int64_t qi, const double* bd, const int* bi,
-                                            int c, int lane) {
+                                            int c, int lane, const unsigned char* ba = nullptr, int na = 0) {
+  if constexpr (F) {
+    const int found = na < a.k ? na : a.k;
+    int seen = 0;
+    for (int j = 0; j * 64 < c && seen < found; ++j) {
+      const int pos = j * 64 + lane;
+      const bool on = pos < c && ba[pos] != 0;
+      const unsigned long long am = __ballot(on);
+      const int r = seen + __popcll(am & ((1ULL << lane) - 1));
+      if (on && r < found) {
+        a.ids[qi * a.k + r] = beam_id(bi[pos]);
+        a.dist[qi * a.k + r] = bd[pos];
+      }
+      seen += __popcll(am);
+    }
+    if (lane >= found && lane < a.k) {
+      a.ids[qi * a.k + lane] = -1;
+      a.dist[qi * a.k + lane] = pos_inf();
+    }
+    if (lane == 0) a.count[qi] = found;
+    return;
+  }
   const int found = c < a.k ? c : a.k;
   if (lane < a.k) {
     const bool on = lane < found;

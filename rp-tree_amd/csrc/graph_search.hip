@@ -19,6 +19,12 @@
 // the tail shifted by one in LDS.  No atomics touch the beam; the filter's atomics only decide what is
 // evaluated twice.  The loops are bounded by the definition: ceil(s / R) seed offers, at most n
 // expansions.
+//
+// graph_search_allow_kernel (rpt_graph_search_allow_*): the same search among the ids of an allow-list.
+// The body of both kernels is graph_search_body; with its switch F on, the beam is the cut of
+// graph_dev.h (up to `width` entries, ending at its ef-th allowed entry), the answer the first k allowed
+// entries, and the workgroup 4, 2 or 1 waves, whichever keeps the most waves on a CU (search_waves), so
+// that every valid shape launches.
 #include <algorithm>
 
 #include "graph_dev.h"
@@ -29,12 +35,14 @@ namespace {
 constexpr int kLdsMax = 160 * 1024;
 constexpr int kQMax = 1024;  // columns up to which the query stays in LDS whole
 
-template <class TD, int M>
-__global__ __launch_bounds__(256) void graph_search_kernel(const TD* __restrict__ X,
-                                                           const TD* __restrict__ Q, SearchArgs a) {
-  extern __shared__ double smem[];
+// The search of one workgroup; F and J are the beam's switches of graph_dev.h.  F off: the beam of
+// rpt_graph_search_*.  F on: the beam of rpt_graph_search_allow_*, up to a.width entries with their
+// allowed bytes `ba` behind the offer's ids.
+template <class TD, int M, bool F, int J>
+__device__ __forceinline__ void graph_search_body(const TD* __restrict__ X, const TD* __restrict__ Q,
+                                                  const SearchArgs& a, double* smem) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
-  const int nj = (a.ef + 63) >> 6, efp = nj * 64;
+  const int nj = ((F ? a.width : a.ef) + 63) >> 6, efp = nj * 64;
   const int d = a.d, ef = a.ef, R = a.R;
   double* buf = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + (size_t)wave * a.wave_bytes);
   double* qv = buf + R * kLS;
@@ -42,6 +50,7 @@ __global__ __launch_bounds__(256) void graph_search_kernel(const TD* __restrict_
   int* bi = reinterpret_cast<int*>(bd + efp);
   int* tab = bi + efp;
   int* sid = tab + a.H;
+  unsigned char* ba = reinterpret_cast<unsigned char*>(sid + R);  // F only
   const bool filter = a.nofilter == 0;
   unsigned long long n_exp = 0, n_eval = 0;
 
@@ -56,7 +65,8 @@ __global__ __launch_bounds__(256) void graph_search_kernel(const TD* __restrict_
     double qnorm = 0.0;
     if constexpr (M == kGraphCosine) qnorm = a.qn[qi];
 
-    int c = 0;  // entries of the beam
+    int c = 0;   // entries of the beam
+    int na = 0;  // F: the allowed ones among them
     int s0 = 0;
     int64_t expanded = 0;
     for (;;) {
@@ -89,10 +99,16 @@ __global__ __launch_bounds__(256) void graph_search_kernel(const TD* __restrict_
       const double cd = fold_finish<M>(acc, qnorm, nrm);
 
       // ---- into the beam, one at a time, by the order of before()
-      beam_insert(bd, bi, c, ef, nj, lane, nrows, cd, my);
+      if constexpr (F)
+        beam_insert<true, J>(bd, bi, c, ef, nj, lane, nrows, cd, my, ba, a.width, &na, beam_allowed(a, my));
+      else
+        beam_insert(bd, bi, c, ef, nj, lane, nrows, cd, my);
     }
     n_exp += (unsigned long long)expanded;
-    beam_answer(a, qi, bd, bi, c, lane);
+    if constexpr (F)
+      beam_answer<true>(a, qi, bd, bi, c, lane, ba, na);
+    else
+      beam_answer(a, qi, bd, bi, c, lane);
   }
   if (lane == 0 && (n_exp | n_eval)) {
     atomicAdd(&a.st->expansions, n_exp);
@@ -101,31 +117,57 @@ __global__ __launch_bounds__(256) void graph_search_kernel(const TD* __restrict_
 }
 
 template <class TD, int M>
+__global__ __launch_bounds__(256) void graph_search_kernel(const TD* __restrict__ X,
+                                                           const TD* __restrict__ Q, SearchArgs a) {
+  extern __shared__ double smem[];
+  graph_search_body<TD, M, false, kBeamJ>(X, Q, a, smem);
+}
+
+// rpt_graph_search_allow_*: J = kBeamJ for a width up to 256, kBeamJWide beyond
+template <class TD, int M, int J>
+__global__ __launch_bounds__(256) void graph_search_allow_kernel(const TD* __restrict__ X,
+                                                                 const TD* __restrict__ Q, SearchArgs a) {
+  extern __shared__ double smem[];
+  graph_search_body<TD, M, true, J>(X, Q, a, smem);
+}
+
+// J == 0: graph_search_kernel, four waves per workgroup; else graph_search_allow_kernel<J>, as many
+// of 4, 2 or 1 as search_waves picks
+template <class TD, int M, int J>
 int32_t launch_search(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, SearchArgs a) {
   const TD* X = static_cast<const TD*>(data->X);
   const TD* Q = static_cast<const TD*>(queries->X);
   a.vec = ((reinterpret_cast<uintptr_t>(X) & 15) == 0 && ((size_t)a.d * sizeof(TD)) % 16 == 0) ? 1 : 0;
+  void (*kern)(const TD*, const TD*, SearchArgs);
+  if constexpr (J == 0) kern = graph_search_kernel<TD, M>;
+  else kern = graph_search_allow_kernel<TD, M, J>;
   static DeviceOnce attr_once;
   RPT_TRY(attr_once.run(ctx->device, [&]() -> int32_t {
-    RPT_HIP(hipFuncSetAttribute((const void*)graph_search_kernel<TD, M>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
+    RPT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
     return RPT_OK;
   }));
-  const int W = 4;
+  const int W = J == 0 ? 4 : search_waves(a.wave_bytes, kLdsMax);
   const int64_t want = (a.nq + W - 1) / W;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)ctx->n_cu * 64));
-  hipLaunchKernelGGL((graph_search_kernel<TD, M>), dim3(grid), dim3(64 * W), (size_t)a.wave_bytes * W,
-                     ctx->stream, X, Q, a);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * W), (size_t)a.wave_bytes * W, ctx->stream, X, Q, a);
   RPT_HIP(hipGetLastError());
   return RPT_OK;
 }
 
-template <class TD>
+template <class TD, int J>
 int32_t launch_search_metric(int m, rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
                              const SearchArgs& a) {
-  if (m == kGraphCosine) return launch_search<TD, kGraphCosine>(ctx, data, queries, a);
-  if (m == kGraphInner) return launch_search<TD, kGraphInner>(ctx, data, queries, a);
-  return launch_search<TD, kGraphL2>(ctx, data, queries, a);
+  if (m == kGraphCosine) return launch_search<TD, kGraphCosine, J>(ctx, data, queries, a);
+  if (m == kGraphInner) return launch_search<TD, kGraphInner, J>(ctx, data, queries, a);
+  return launch_search<TD, kGraphL2, J>(ctx, data, queries, a);
+}
+
+template <class TD>
+int32_t launch_search_beam(int m, rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                           const SearchArgs& a, bool allow) {
+  if (!allow) return launch_search_metric<TD, 0>(m, ctx, data, queries, a);
+  if (a.width <= 64 * kBeamJ) return launch_search_metric<TD, kBeamJ>(m, ctx, data, queries, a);
+  return launch_search_metric<TD, kBeamJWide>(m, ctx, data, queries, a);
 }
 
 }  // namespace
@@ -133,7 +175,9 @@ int32_t launch_search_metric(int m, rpt_ctx* ctx, const rpt_dataset* data, const
 int32_t graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
                          const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
                          const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
-                         int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+                         int32_t* ids_dev, double* dist_dev, int32_t* count_dev, int32_t width,
+                         const uint32_t* allow_dev) {
+  const bool allow = width != 0;  // rpt_graph_search_allow_*
   const int m = graph_metric_of(metric);
   if (m == kGraphCosine) {  // the rows' dot(x, x), cached on the two datasets
     RPT_TRY(ensure_sqnorm(ctx, data));
@@ -144,7 +188,7 @@ int32_t graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
     if (e != hipSuccess)
       return fail(RPT_E_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
   }
-  SearchArgs a;
+  SearchArgs a = {};
   a.n = data->n;
   a.nq = queries->n;
   a.d = data->d;
@@ -152,21 +196,21 @@ int32_t graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
   a.s = s;
   a.k = k;
   a.ef = ef;
-  // an offer holds a graph row whole; seeds come in batches of the same size
-  a.R = std::max<int>(kg, std::min<int>(s, 16));
-  // the filter: eight slots per beam entry, 1 to 8 KB
-  a.H = 256;
-  while (a.H < 8 * ef && a.H < 2048) a.H <<= 1;
+  a.width = allow ? width : ef;
+  search_shape(a);
   a.qres = a.d <= kQMax ? 1 : 0;
   a.vec = 0;
   a.nofilter = ctx->opt.graph_search_nofilter != 0 ? 1 : 0;
-  const int efp = ((ef + 63) / 64) * 64;
+  const int efp = ((a.width + 63) / 64) * 64;
+  // an allow-list beam keeps a byte per entry behind the offer's ids
   a.wave_bytes = (int)(((size_t)(a.R * kLS + (a.qres ? a.d : kCW) + efp) * 8 +
-                        (size_t)(efp + a.H + a.R) * 4 + 7) & ~(size_t)7);
-  if (4 * a.wave_bytes > kLdsMax) return fail(RPT_E_INTERNAL, "graph search: the beam does not fit LDS");
+                        (size_t)(efp + a.H + a.R) * 4 + (allow ? efp : 0) + 7) & ~(size_t)7);
+  if (!allow && 4 * a.wave_bytes > kLdsMax)
+    return fail(RPT_E_INTERNAL, "graph search: the beam does not fit LDS");
   a.gids = gids_dev;
   a.gcount = gcount_dev;
   a.seeds = seeds_dev;
+  a.allow = allow_dev;
   a.rn = m == kGraphCosine ? data->sqnorm : nullptr;
   a.qn = m == kGraphCosine ? queries->sqnorm : nullptr;
   a.ids = ids_dev;
@@ -180,11 +224,11 @@ int32_t graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
   if (a.nq == 0) return RPT_OK;
   switch (data->dtype) {
     case RPT_F64:
-      return launch_search_metric<double>(m, ctx, data, queries, a);
+      return launch_search_beam<double>(m, ctx, data, queries, a, allow);
     case RPT_F32:
-      return launch_search_metric<float>(m, ctx, data, queries, a);
+      return launch_search_beam<float>(m, ctx, data, queries, a, allow);
     default:
-      return launch_search_metric<uint16_t>(m, ctx, data, queries, a);
+      return launch_search_beam<uint16_t>(m, ctx, data, queries, a, allow);
   }
 }
 

@@ -32,6 +32,10 @@
 // tail.  No zero stands in for an absent entry: a stored inf or NaN meets only what the other row
 // stores.  Cosine reads dotS(q, q) once per query and dotS(x_v, x_v) in the epilogue, both from
 // rpt_dataset::sqnorm (the same fold), as graph_search.hip does; LDS is what the L2 kernel takes.
+//
+// graph_search_csr_allow_kernel (rpt_graph_search_allow_* on CSR rows): the same search among the ids of
+// an allow-list, as graph_search_allow_kernel is to graph_search_kernel: one body (graph_search_csr_body),
+// the beam's switch F on, 4, 2 or 1 waves per workgroup by search_waves.
 #include <algorithm>
 
 #include "graph_dev.h"
@@ -94,14 +98,15 @@ __device__ __forceinline__ double merge_piece(double acc, const int* pc, const d
   return acc;
 }
 
-template <class TV, int M>
-__global__ __launch_bounds__(256) void graph_search_csr_kernel(
+// The search of one workgroup; F and J are the beam's switches of graph_dev.h, as in graph_search.hip:
+// F on is the beam of rpt_graph_search_allow_*, with its allowed bytes `ba` behind the offer's ids.
+template <class TV, int M, bool F, int J>
+__device__ __forceinline__ void graph_search_csr_body(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const TV* __restrict__ val,
     const int64_t* __restrict__ qrowptr, const int32_t* __restrict__ qcol, const TV* __restrict__ qval,
-    SearchArgs a) {
-  extern __shared__ double smem[];
+    const SearchArgs& a, double* smem) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
-  const int nj = (a.ef + 63) >> 6, efp = nj * 64;
+  const int nj = ((F ? a.width : a.ef) + 63) >> 6, efp = nj * 64;
   const int ef = a.ef;
   double* qv = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + (size_t)wave * a.wave_bytes);
   double* bd = qv + a.qcap;
@@ -109,6 +114,7 @@ __global__ __launch_bounds__(256) void graph_search_csr_kernel(
   int* bi = qc + a.qcap;
   int* tab = bi + efp;
   int* sid = tab + a.H;
+  unsigned char* ba = reinterpret_cast<unsigned char*>(sid + a.R);  // F only
   const bool filter = a.nofilter == 0;
   unsigned long long n_exp = 0, n_eval = 0;
 
@@ -127,7 +133,8 @@ __global__ __launch_bounds__(256) void graph_search_csr_kernel(
     double qnorm = 0.0;
     if constexpr (M == kGraphCosine) qnorm = a.qn[qi];
 
-    int c = 0;  // entries of the beam
+    int c = 0;   // entries of the beam
+    int na = 0;  // F: the allowed ones among them
     int s0 = 0;
     int64_t expanded = 0;
     for (;;) {
@@ -180,10 +187,16 @@ __global__ __launch_bounds__(256) void graph_search_csr_kernel(
       const double cd = fold_finish<M>(acc, qnorm, nrm);
 
       // ---- into the beam, one at a time, by the order of before()
-      beam_insert(bd, bi, c, ef, nj, lane, nrows, cd, my);
+      if constexpr (F)
+        beam_insert<true, J>(bd, bi, c, ef, nj, lane, nrows, cd, my, ba, a.width, &na, beam_allowed(a, my));
+      else
+        beam_insert(bd, bi, c, ef, nj, lane, nrows, cd, my);
     }
     n_exp += (unsigned long long)expanded;
-    beam_answer(a, qi, bd, bi, c, lane);
+    if constexpr (F)
+      beam_answer<true>(a, qi, bd, bi, c, lane, ba, na);
+    else
+      beam_answer(a, qi, bd, bi, c, lane);
   }
   if (lane == 0 && (n_exp | n_eval)) {
     atomicAdd(&a.st->expansions, n_exp);
@@ -192,30 +205,61 @@ __global__ __launch_bounds__(256) void graph_search_csr_kernel(
 }
 
 template <class TV, int M>
+__global__ __launch_bounds__(256) void graph_search_csr_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const TV* __restrict__ val,
+    const int64_t* __restrict__ qrowptr, const int32_t* __restrict__ qcol, const TV* __restrict__ qval,
+    SearchArgs a) {
+  extern __shared__ double smem[];
+  graph_search_csr_body<TV, M, false, kBeamJ>(rowptr, col, val, qrowptr, qcol, qval, a, smem);
+}
+
+// rpt_graph_search_allow_* on CSR rows: J = kBeamJ for a width up to 256, kBeamJWide beyond
+template <class TV, int M, int J>
+__global__ __launch_bounds__(256) void graph_search_csr_allow_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const TV* __restrict__ val,
+    const int64_t* __restrict__ qrowptr, const int32_t* __restrict__ qcol, const TV* __restrict__ qval,
+    SearchArgs a) {
+  extern __shared__ double smem[];
+  graph_search_csr_body<TV, M, true, J>(rowptr, col, val, qrowptr, qcol, qval, a, smem);
+}
+
+// J == 0: graph_search_csr_kernel, four waves per workgroup; else graph_search_csr_allow_kernel<J>, as
+// many of 4, 2 or 1 as search_waves picks
+template <class TV, int M, int J>
 int32_t launch_search_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
                           const SearchArgs& a) {
+  void (*kern)(const int64_t*, const int32_t*, const TV*, const int64_t*, const int32_t*, const TV*, SearchArgs);
+  if constexpr (J == 0) kern = graph_search_csr_kernel<TV, M>;
+  else kern = graph_search_csr_allow_kernel<TV, M, J>;
   static DeviceOnce attr_once;
   RPT_TRY(attr_once.run(ctx->device, [&]() -> int32_t {
-    RPT_HIP(hipFuncSetAttribute((const void*)graph_search_csr_kernel<TV, M>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
+    RPT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax));
     return RPT_OK;
   }));
-  const int W = 4;
+  const int W = J == 0 ? 4 : search_waves(a.wave_bytes, kLdsMax);
   const int64_t want = (a.nq + W - 1) / W;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)ctx->n_cu * 64));
-  hipLaunchKernelGGL((graph_search_csr_kernel<TV, M>), dim3(grid), dim3(64 * W), (size_t)a.wave_bytes * W,
-                     ctx->stream, data->rowptr, data->col, static_cast<const TV*>(data->val),
-                     queries->rowptr, queries->col, static_cast<const TV*>(queries->val), a);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * W), (size_t)a.wave_bytes * W, ctx->stream, data->rowptr,
+                     data->col, static_cast<const TV*>(data->val), queries->rowptr, queries->col,
+                     static_cast<const TV*>(queries->val), a);
   RPT_HIP(hipGetLastError());
   return RPT_OK;
 }
 
-template <class TV>
+template <class TV, int J>
 int32_t launch_search_csr_metric(int m, rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
                                  const SearchArgs& a) {
-  if (m == kGraphCosine) return launch_search_csr<TV, kGraphCosine>(ctx, data, queries, a);
-  if (m == kGraphInner) return launch_search_csr<TV, kGraphInner>(ctx, data, queries, a);
-  return launch_search_csr<TV, kGraphL2>(ctx, data, queries, a);
+  if (m == kGraphCosine) return launch_search_csr<TV, kGraphCosine, J>(ctx, data, queries, a);
+  if (m == kGraphInner) return launch_search_csr<TV, kGraphInner, J>(ctx, data, queries, a);
+  return launch_search_csr<TV, kGraphL2, J>(ctx, data, queries, a);
+}
+
+template <class TV>
+int32_t launch_search_csr_beam(int m, rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                               const SearchArgs& a, bool allow) {
+  if (!allow) return launch_search_csr_metric<TV, 0>(m, ctx, data, queries, a);
+  if (a.width <= 64 * kBeamJ) return launch_search_csr_metric<TV, kBeamJ>(m, ctx, data, queries, a);
+  return launch_search_csr_metric<TV, kBeamJWide>(m, ctx, data, queries, a);
 }
 
 }  // namespace
@@ -223,7 +267,9 @@ int32_t launch_search_csr_metric(int m, rpt_ctx* ctx, const rpt_dataset* data, c
 int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
                              int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
                              const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
-                             int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+                             int32_t* ids_dev, double* dist_dev, int32_t* count_dev, int32_t width,
+                             const uint32_t* allow_dev) {
+  const bool allow = width != 0;  // rpt_graph_search_allow_*
   const int m = graph_metric_of(metric);
   if (m == kGraphCosine) {  // the rows' dotS(x, x), cached on the two datasets
     RPT_TRY(ensure_sqnorm(ctx, data));
@@ -237,18 +283,17 @@ int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_da
   a.s = s;
   a.k = k;
   a.ef = ef;
-  // an offer holds a graph row whole; seeds come in batches of the same size
-  a.R = std::max<int>(kg, std::min<int>(s, 16));
-  // the filter: eight slots per beam entry, 1 to 8 KB
-  a.H = 256;
-  while (a.H < 8 * ef && a.H < 2048) a.H <<= 1;
+  a.width = allow ? width : ef;
+  search_shape(a);
   a.nofilter = ctx->opt.graph_search_nofilter != 0 ? 1 : 0;
   a.stream = ctx->opt.graph_search_csr_stream != 0 ? 1 : 0;
   // a row of ascending columns holds at most d entries: no more LDS than any query can fill
   a.qcap = std::max<int>(kPiece, std::min<int>(kQCap, a.d));
-  const int efp = ((ef + 63) / 64) * 64;
-  a.wave_bytes = (int)(((size_t)(a.qcap + efp) * 12 + (size_t)(a.H + a.R) * 4 + 7) & ~(size_t)7);
-  if (4 * a.wave_bytes > kLdsMax) return fail(RPT_E_INTERNAL, "graph search: the beam does not fit LDS");
+  const int efp = ((a.width + 63) / 64) * 64;
+  // an allow-list beam keeps a byte per entry behind the offer's ids
+  a.wave_bytes = (int)(((size_t)(a.qcap + efp) * 12 + (size_t)(a.H + a.R) * 4 + (allow ? efp : 0) + 7) &
+                       ~(size_t)7);
+  if (!allow && 4 * a.wave_bytes > kLdsMax) return fail(RPT_E_INTERNAL, "graph search: the beam does not fit LDS");
   if (!ctx->search_state_dev) {
     hipError_t e = dev_alloc(&ctx->search_state_dev, sizeof(SearchState));
     if (e != hipSuccess)
@@ -257,6 +302,7 @@ int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_da
   a.gids = gids_dev;
   a.gcount = gcount_dev;
   a.seeds = seeds_dev;
+  a.allow = allow_dev;
   a.rn = m == kGraphCosine ? data->sqnorm : nullptr;
   a.qn = m == kGraphCosine ? queries->sqnorm : nullptr;
   a.ids = ids_dev;
@@ -268,8 +314,8 @@ int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_da
   hipLaunchKernelGGL(search_begin_kernel, dim3(1), dim3(64), 0, ctx->stream, a.st);
   RPT_HIP(hipGetLastError());
   if (a.nq == 0) return RPT_OK;
-  if (data->dtype == RPT_F64) return launch_search_csr_metric<double>(m, ctx, data, queries, a);
-  return launch_search_csr_metric<float>(m, ctx, data, queries, a);
+  if (data->dtype == RPT_F64) return launch_search_csr_beam<double>(m, ctx, data, queries, a, allow);
+  return launch_search_csr_beam<float>(m, ctx, data, queries, a, allow);
 }
 
 }  // namespace rpt

@@ -11,6 +11,7 @@
 //   (SplitMix64 + Box-Muller restated from the published algorithm: self-consistent, not
 //   verified against Hackage's splitmix-distributions — a Haskell host keeps its own generator).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -763,6 +764,48 @@ inline KnnResult graphSearchSV(const RPForest& tts, const GraphResult& g, const 
                        forestSeeds(tts, qs, seed_k, metric == Metric::L2 ? rpt_knn_host : rpt_knn_csr_metric_host,
                                    RPT_KNN_DEDUP | metric_flags(metric), "graphSearchSV"),
                        seed_k, stats);
+}
+
+// graphSearch among SOME of the points (rpt_graph_search_allow_host): `allow` holds ceil(n / 32)
+// words, id i allowed when bit i & 31 of word i >> 5 is set (allowBitmap packs a mask); an empty
+// vector allows every id.  data and qs are both dense or both CSR, under any Metric.  ef counts
+// ALLOWED beam entries only; width in [ef, 1024] is the most entries the beam may hold, allowed or
+// not (0 = min(1024, 8 * ef)); a beam with ef allowed entries ends at its ef-th allowed entry, and
+// disallowed entries are expanded like any other.  The answer is the first k allowed entries.  With
+// every id allowed it is graphSearch's / graphSearchSV's bit for bit; with width = ef it is the allowed
+// entries of the unfiltered beam.
+inline std::vector<uint32_t> allowBitmap(const std::vector<bool>& mask) {
+  std::vector<uint32_t> words((mask.size() + 31) / 32, 0u);
+  for (size_t i = 0; i < mask.size(); ++i)
+    if (mask[i]) words[i >> 5] |= 1u << (i & 31);
+  return words;
+}
+inline KnnResult graphSearchAllow(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs,
+                                  const std::vector<uint32_t>& allow, int k, int ef, int width,
+                                  const std::vector<int32_t>& seeds, int s, Metric metric = Metric::L2,
+                                  SearchStats* stats = nullptr) {
+  if (!allow.empty() && allow.size() != ((size_t)data.n + 31) / 32)
+    throw RPTError(RPT_E_ARG, "graphSearchAllow: allow must hold ceil(n / 32) words (or none)");
+  if (width == 0) width = std::min(RPT_GRAPH_SEARCH_MAX_WIDTH, 8 * ef);
+  return graphSearchVia(
+      [&](const int32_t* gids, const int32_t* gcount, const int32_t* sd, int32_t flags, int32_t* ids, double* dist,
+          int32_t* count) {
+        return rpt_graph_search_allow_host(ctx.get(), data.get(), qs.get(), g.k, gids, gcount, s, sd,
+                                           allow.empty() ? nullptr : allow.data(), k, ef, width,
+                                           metric_flags(metric), flags, ids, dist, count);
+      },
+      "graphSearchAllow", ctx, data, g, qs, k, seeds, s, stats);
+}
+// ... the seeds taken from a forest under the same metric, as graphSearch / graphSearchSV take them;
+// seeds need not be allowed
+inline KnnResult graphSearchAllow(const RPForest& tts, const GraphResult& g, const Dataset& qs,
+                                  const std::vector<uint32_t>& allow, int k, int ef, int width = 0,
+                                  Metric metric = Metric::L2, int seed_k = 8, SearchStats* stats = nullptr) {
+  const bool csr_metric = tts.data->csr && metric != Metric::L2;
+  return graphSearchAllow(*tts.ctx, *tts.data, g, qs, allow, k, ef, width,
+                          forestSeeds(tts, qs, seed_k, csr_metric ? rpt_knn_csr_metric_host : rpt_knn_host,
+                                      RPT_KNN_DEDUP | metric_flags(metric), "graphSearchAllow"),
+                          seed_k, metric, stats);
 }
 
 struct BruteResult {

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import gen
 from ._lib import (RPT_BF16, RPT_F32, RPT_F64, RPT_GRAPH_ACCUMULATE, RPT_GRAPH_MAX_K, RPT_GRAPH_SEARCH_MAX_EF,
-                   RPT_GRAPH_PREP_DIVERSIFY, RPT_GRAPH_PREP_REVERSE,
+                   RPT_GRAPH_SEARCH_MAX_WIDTH, RPT_GRAPH_PREP_DIVERSIFY, RPT_GRAPH_PREP_REVERSE,
                    RPT_KNN_DEDUP, RPT_KNN_DEDUP_DISTANCE,
                    RPT_KNN_KEEP_DUPLICATES, RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER,
                    RPT_KNN_METRIC_REFERENCE,
@@ -43,6 +43,7 @@ __all__ = [
     "knnGraphSV", "knnGraphSVDev", "knnGraphRefineSV", "knnGraphRefineSVDev",
     "knnGraphMetricSV", "knnGraphMetricSVDev", "knnGraphRefineMetricSV", "knnGraphRefineMetricSVDev",
     "graphSearch", "graphSearchDev", "graphSearchLast", "graphSearchSV", "graphSearchSVDev",
+    "graphSearchAllow", "graphSearchAllowDev", "allowBitmap",
     "graphPrepare", "graphPrepareDev", "graphPrepareLast", "graphPrepareSV", "graphPrepareSVDev",
     "graphSearchMetricSV", "graphSearchMetricSVDev", "graphPrepareMetricSV", "graphPrepareMetricSVDev",
     "knnVote", "knnVoteDev", "voteCandidates", "knnVoteLast",
@@ -1122,9 +1123,11 @@ def knnGraphRefineLast(ctx=None):
     return int(a.value), int(b.value), int(c.value)
 
 
-def _graph_search(entry, who, graph, data, qs, k, ef, seeds, forest, seed_k, metric_flag, seed_metric, ctx):
-    """graphSearch / graphSearchSV / graphSearchMetricSV around their _host entry point; seed_metric:
-    the metric of the knnBatch that takes seeds from `forest`"""
+def _graph_search(entry, who, graph, data, qs, k, ef, seeds, forest, seed_k, metric_flag, seed_metric, ctx,
+                  allow=None, width=None, filtered=False):
+    """graphSearch / graphSearchSV / graphSearchMetricSV / graphSearchAllow around their _host entry
+    point; seed_metric: the metric of the knnBatch that takes seeds from `forest`; filtered: the entry
+    point takes the allow-list's words behind the seeds and `width` behind ef"""
     ds = _refine_data(data)
     ctx = ctx or ds.ctx
     gids = np.ascontiguousarray(graph[0], dtype=np.int32)
@@ -1145,8 +1148,13 @@ def _graph_search(entry, who, graph, data, qs, k, ef, seeds, forest, seed_k, met
     ids = np.empty((nq, k), dtype=np.int32)
     dist = np.empty((nq, k), dtype=np.float64)
     cnt = np.empty(nq, dtype=np.int32)
-    check(entry(ctx._h, ds._h, qd._h, int(gids.shape[1]), _vp(gids), _vp(gcnt), int(seeds.shape[1]),
-                _vp(seeds), int(k), int(ef), metric_flag, 0, _vp(ids), _vp(dist), _vp(cnt)))
+    head = (ctx._h, ds._h, qd._h, int(gids.shape[1]), _vp(gids), _vp(gcnt), int(seeds.shape[1]), _vp(seeds))
+    beam = (int(k), int(ef))
+    if filtered:
+        words = None if allow is None else allowBitmap(allow, ds.n)
+        head += (None if words is None else _vp(words),)
+        beam += (min(RPT_GRAPH_SEARCH_MAX_WIDTH, 8 * int(ef)) if width is None else int(width),)
+    check(entry(*head, *beam, metric_flag, 0, _vp(ids), _vp(dist), _vp(cnt)))
     return ids, dist, cnt
 
 
@@ -1229,9 +1237,70 @@ def graphSearchMetricSVDev(distf, data, queries, kg, gids_ptr, gcount_ptr, s, se
                                                 C.c_void_p(count_ptr)))
 
 
+def allowBitmap(mask_or_ids, n):
+    """The allow-list of graphSearchAllow as ceil(n / 32) uint32 words: id i is allowed when bit i & 31
+    of word i >> 5 is set.  mask_or_ids: a bool array of n (True = allowed), an integer array of the
+    allowed ids (each in [0, n)), or the uint32 words themselves (returned as they are)."""
+    n = int(n)
+    nw = (n + 31) // 32
+    a = np.asarray(mask_or_ids)
+    if a.dtype == np.uint32:
+        if a.shape != (nw,):
+            raise ValueError("the allow-list's words must be ceil(n / 32) = %d uint32" % nw)
+        return np.ascontiguousarray(a)
+    if a.dtype == np.bool_:
+        if a.shape != (n,):
+            raise ValueError("the allow mask must hold n = %d bools" % n)
+        mask = a
+    else:
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("allow must be a bool mask of n, integer ids or uint32 words")
+        ids = a.astype(np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() >= n):
+            raise ValueError("an allowed id lies outside [0, n)")
+        mask = np.zeros(n, dtype=bool)
+        mask[ids] = True
+    bits = np.zeros(nw * 32, dtype=np.uint8)
+    bits[:n] = mask
+    return np.ascontiguousarray(np.packbits(bits, bitorder="little").view("<u4").astype(np.uint32))
+
+
+def graphSearchAllow(allow, graph, data, qs, k, ef=None, width=None, seeds=None, forest=None, seed_k=8, metric=None,
+                     ctx=None):
+    """graphSearch among SOME of the points (rpt_graph_search_allow_host) -> (ids[nq][k], dist[nq][k],
+    count[nq]): the rows a tombstone bitmap has not deleted, the rows of one tenant.  allow: a bool
+    array of n (True = allowed), the uint32 words of allowBitmap, or None (every id); one list serves
+    the whole batch.  data: a dense or an SVector (CSR) Dataset, or a forest over one; qs as graphSearch
+    / graphSearchSV take them; metric: None / metricL2, metricCosine or metricInner on either layout.
+    ef (None = max(k, 32), at most 256) counts ALLOWED beam entries only; width (None = min(1024,
+    8 * ef), in [ef, 1024]) is the most entries the beam may hold, allowed or not: the frontier the
+    search walks through, disallowed entries being expanded like any other.  A beam with ef allowed
+    entries ends at its ef-th allowed entry.  The answer is the first k allowed entries by (distance,
+    id).  With every id allowed it is graphSearch's / graphSearchSV's / graphSearchMetricSV's bit for
+    bit, whatever the width; with width = ef it is the allowed entries of the unfiltered beam.  With
+    `forest` the seeds are the ids of knnBatch(seed_k, forest, qs, dedup=True, metric=metric); seeds
+    need not be allowed."""
+    return _graph_search(lib().rpt_graph_search_allow_host, "graphSearchAllow", graph, data, qs, k, ef, seeds,
+                         forest, seed_k, _metric_flag(metric), metric, ctx, allow, width, True)
+
+
+def graphSearchAllowDev(data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, allow_ptr, k, ef, width, ids_ptr,
+                        dist_ptr, count_ptr, metric=None):
+    """graphSearchAllow on device arrays (rpt_graph_search_allow_dev): data and queries are Datasets
+    (both dense or both CSR), allow_ptr the device address of the ceil(n / 32) uint32 words (0 = every
+    id); the other arrays and the synchronisation as graphSearchDev's."""
+    metric_flag = _metric_flag(metric)
+    ds = _refine_data(data)
+    check(lib().rpt_graph_search_allow_dev(ds.ctx._h, ds._h, queries._h, int(kg), C.c_void_p(gids_ptr),
+                                           C.c_void_p(gcount_ptr), int(s), C.c_void_p(seeds_ptr),
+                                           C.c_void_p(allow_ptr), int(k), int(ef), int(width), metric_flag, 0,
+                                           C.c_void_p(ids_ptr), C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
+
+
 def graphSearchLast(ctx=None):
-    """(expansions, evaluated) of the last graphSearch / graphSearchSV call on ctx (rpt_graph_search_last;
-    synchronises): beam entries expanded and distances computed, summed over the queries."""
+    """(expansions, evaluated) of the last graphSearch / graphSearchSV / graphSearchAllow call on ctx
+    (rpt_graph_search_last; synchronises): beam entries expanded and distances computed, summed over
+    the queries."""
     ctx = ctx or default_context()
     a, b = C.c_int64(), C.c_int64()
     check(lib().rpt_graph_search_last(ctx._h, C.byref(a), C.byref(b)))

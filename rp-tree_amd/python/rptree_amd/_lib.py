@@ -19,6 +19,7 @@ RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER = 1 << 25, 1 << 26
 RPT_GRAPH_ACCUMULATE = 1
 RPT_GRAPH_MAX_K = 64
 RPT_GRAPH_SEARCH_MAX_EF = 256
+RPT_GRAPH_SEARCH_MAX_WIDTH = 1024
 RPT_GRAPH_PREP_DIVERSIFY = 1
 RPT_GRAPH_PREP_REVERSE = 2
 RPT_COMM_UID_BYTES = 128
@@ -98,6 +99,8 @@ SYMBOLS = {
     "rpt_graph_search_csr_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_csr_metric_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_csr_metric_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "rpt_graph_search_allow_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "rpt_graph_search_allow_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_last": (i32, [vp, p_i64, p_i64]),
     "rpt_graph_prepare_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_prepare_host": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
