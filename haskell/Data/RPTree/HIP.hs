@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchAllowHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchAllowHIP, graphInsertHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -59,6 +59,7 @@ foreign import ccall safe "rpt_knn_graph_csr_metric_host" c_knn_graph_csr_metric
 foreign import ccall safe "rpt_knn_graph_refine_csr_metric_host" c_knn_graph_refine_csr_metric_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_host" c_graph_search_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_allow_host" c_graph_search_allow_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Ptr Word32 -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_graph_insert_host" c_graph_insert_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int64 -> Int32 -> Ptr Int32 -> Int32 -> Int64 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_csr_host" c_graph_search_csr_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_host" c_graph_prepare_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_csr_host" c_graph_prepare_csr_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
@@ -425,6 +426,25 @@ graphSearchAllowHIP ctx ds qs m nq kg (gids, gcount) s seeds allow k ef width = 
   VS.unsafeWith gids (\pg -> VS.unsafeWith gcount (\pc -> VS.unsafeWith seeds (\ps -> withAllow (\pa ->
     VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
       c_graph_search_allow_host ctx ds qs (fromIntegral kg) pg pc (fromIntegral s) ps pa (fromIntegral k) (fromIntegral ef) (fromIntegral width) (metricFlag m) 0 a b))))))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | New rows into a kNN graph (rpt_graph_insert_host): @ds@ holds N = n + m rows whose LAST m are the
+-- new ones (dense or CSR, under any 'Metric'), the graph is over the first n and its distances ARE
+-- read.  The new rows are taken in chunks of @batch@; every row of a chunk is answered by
+-- 'graphSearchHIP' with k = kg and this @ef@ over the rows visible so far (the first n and the chunks
+-- before it, not its own chunk), the answer becomes the new row, and every row it names takes the new
+-- id at the same distance when that is among its first kg by (distance, id).  @seeds@ is [m][s], -1
+-- an unused slot; a seed may name a row of an earlier chunk.  The result (ids[N][kg], dist[N][kg],
+-- count[N]) is a pure function of its inputs, bit for bit; m = 0 copies the graph.
+graphInsertHIP :: Ptr Ctx -> Ptr Dataset -> Metric -> Int -> Int -> Int
+               -> (VS.Vector Int32, VS.Vector Double, VS.Vector Int32) -> Int -> VS.Vector Int32 -> Int -> Int
+               -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+graphInsertHIP ctx ds metric n m kg (gids, gdist, gcount) s seeds ef batch = do
+  let total = n + m
+  ids <- VSM.new (total * kg); dist <- VSM.new (total * kg); cnt <- VSM.new total
+  VS.unsafeWith gids (\pg -> VS.unsafeWith gdist (\pd -> VS.unsafeWith gcount (\pc -> VS.unsafeWith seeds (\ps ->
+    VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
+      c_graph_insert_host ctx ds (fromIntegral kg) pg pd pc (fromIntegral m) (fromIntegral s) ps (fromIntegral ef) (fromIntegral batch) (metricFlag metric) 0 a b))))))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
 
 -- | A kNN graph made ready for 'graphSearchHIP' (rpt_graph_prepare_host), PyNNDescent's search graph.

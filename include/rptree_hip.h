@@ -186,7 +186,8 @@ int32_t rpt_ctx_get_option(rpt_ctx* ctx, const char* name, int64_t* value);
  * one pass over the whole point set for up to 96 hyperplanes), 1 = split work,
  * 2 = query plan (query projections + traversal), 3 = distance/top-k kernel, 4 = the wide
  * (> 32 hyperplanes per pass) MFMA projection launches alone (they are also part of class 0),
- * 5 = the vote-select kernel of rpt_knn_vote_* / rpt_vote_candidates_host.
+ * 5 = the vote-select kernel of rpt_knn_vote_* / rpt_vote_candidates_host, 6 = the link kernels of
+ * rpt_graph_insert_* (one launch = the link of one chunk; its searches are class 3).
  * rpt_prof_get synchronises the stream and returns the accumulated ms and launch count. */
 int32_t rpt_prof_enable(rpt_ctx* ctx, int32_t on);
 int32_t rpt_prof_reset(rpt_ctx* ctx);
@@ -766,6 +767,75 @@ int32_t rpt_graph_search_allow_host(rpt_ctx* ctx, const rpt_dataset* data, const
                                     int32_t s, const int32_t* seeds_host, const uint32_t* allow_host,
                                     int32_t k, int32_t ef, int32_t width, int32_t metric, int32_t flags,
                                     int32_t* ids_host, double* dist_host, int32_t* count_host);
+
+/* ---- insert new rows into a kNN graph ----
+ * rpt_graph_insert_* grows a graph: the rows that were added to a data set find their neighbours
+ * with the beam search and are linked in both directions, and nothing is rebuilt.  With the allow-list
+ * (deletions) this makes the graph a dynamic index.  One pair of entry points serves dense data (f64,
+ * f32, bf16) and CSR data (f64, f32) under `metric` 0, RPT_KNN_METRIC_COSINE and RPT_KNN_METRIC_INNER.
+ * Inputs:
+ *   data        a data set of N = n + m rows; its LAST m rows are the new ones.
+ *   gids, gdist, gcount   a graph over the first n rows in rpt_knn_graph_*'s layout: ids[n][kg],
+ *               dist[n][kg], count[n], kg in [1, RPT_GRAPH_MAX_K].  The stored distances ARE read
+ *               here.  The caller's graph is read only.
+ *   m           >= 0, at most data.n.
+ *   seeds       seeds[m][s], s in [1, 64], -1 an unused slot: where the search of new row n + i starts.
+ *   ef          in [kg, RPT_GRAPH_SEARCH_MAX_EF].
+ *   batch       >= 1: new rows per chunk.
+ *   flags       0.
+ * Output: oids[N][kg], odist[N][kg], ocount[N].
+ * State.  G_0 is the input graph followed by m empty rows; v_0 = n rows are visible.  Chunk c is the
+ * rows P_c = [v_c, min(v_c + batch, N)).
+ *   Search      For every p in P_c, A_p is the answer of rpt_graph_search_*'s definition, word for word,
+ *               with the query = row p of data, the graph = G_c, n replaced by v_c (seeds and graph
+ *               ids outside [0, v_c) are skipped: a seed naming a row of an EARLIER chunk is valid, a
+ *               seed naming a row of this or a later chunk is not), k = kg, this ef and this metric.
+ *               The distance is the one the graph code uses for this layout and metric: the dense
+ *               folds, the union fold for CSR rows under L2, dotS for CSR rows under cosine / inner
+ *               product, with the cached norms for cosine.  All of them are symmetric bit for bit, so
+ *               the distance found with p as the query is the distance a graph row of the other
+ *               endpoint would store for p.
+ *   Link        Row p of G_{c+1} is A_p: sorted by (distance, id), count = |A_p|, unused slots hold id
+ *               -1 and distance +inf.  For every o < v_c named by at least one A_p of this chunk, row
+ *               o of G_{c+1} is the first kg by (distance, id) (the order of the search: NaN behind
+ *               every number, NaNs among themselves by id) of
+ *                 (valid entries of row o of G_c) u {(d, p) : p in P_c, (d, o) in A_p}.
+ *               Rows that no A_p names are carried over unchanged.  v_{c+1} = v_c + |P_c|.
+ * The result is G after the last chunk: a pure function of (data, graph, m, seeds, ef, batch, metric).
+ * The order in which reverse offers arrive plays no part: the row is the first kg of a set under a
+ * total order.  Stated properties:
+ *   Rows of one chunk do not see each other: the price of searching a chunk in parallel; `batch` is
+ *               the knob, and a rpt_knn_graph_refine_* round afterwards links them.
+ *   m = 0 copies the graph.
+ *   A new row whose seeds are all invalid gets count 0 and links nothing.
+ *   Untouched rows are copied verbatim by _dev, whatever they hold.
+ *   Touched rows come out sorted with invalid entries dropped: slots at or beyond the count clamped to
+ *               [0, kg], ids outside [0, N), and an id the row holds twice counts once, at its first
+ *               slot (an offer whose id the row holds already is dropped too; neither happens in a
+ *               graph over the first n rows).
+ * No atomics touch a row and one wave writes it: the same bits whatever the launch shape and whatever
+ * graph_search_nofilter and graph_search_csr_stream are set to.  The link of a chunk costs O(|P_c| kg)
+ * whatever n is.  Scratch is sized by (N, batch, kg): 12 N + 24 min(batch, m) kg bytes.
+ * rpt_graph_insert_last: chunks = the number of chunks; evaluated = the distances the searches
+ * computed (bounds as rpt_graph_search_last's, summed); offered = reverse entries offered (the sum of
+ * |A_p|); accepted = reverse entries that are in their target's row when that row is written.
+ * rpt_graph_search_last then reports the last chunk's search.
+ * Errors: kg, s or ef out of range, batch < 1, m < 0 or m > data.n, flags other than 0, any other
+ * `metric` value, both metric bits together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG; no room for the
+ * scratch: RPT_E_NOMEM.  _host validates the counts, ids in [0, n) and seeds in {-1} u [0, N) before
+ * anything is uploaded, as rpt_graph_search_host does, names the offending row, and synchronises;
+ * _dev borrows device arrays, does NOT validate and does not synchronise.  A refused call leaves the
+ * context usable. */
+int32_t rpt_graph_insert_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_dev,
+                             const double* gdist_dev, const int32_t* gcount_dev, int64_t m, int32_t s,
+                             const int32_t* seeds_dev, int32_t ef, int64_t batch, int32_t metric,
+                             int32_t flags, int32_t* oids_dev, double* odist_dev, int32_t* ocount_dev);
+int32_t rpt_graph_insert_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_host,
+                              const double* gdist_host, const int32_t* gcount_host, int64_t m, int32_t s,
+                              const int32_t* seeds_host, int32_t ef, int64_t batch, int32_t metric,
+                              int32_t flags, int32_t* oids_host, double* odist_host, int32_t* ocount_host);
+int32_t rpt_graph_insert_last(rpt_ctx* ctx, int64_t* chunks, int64_t* evaluated, int64_t* offered,
+                              int64_t* accepted);
 
 /* ---- query the kNN graph on SVector (CSR) rows, under L2 ----
  * rpt_graph_search_csr_* is rpt_graph_search_* for a CSR data set and CSR queries (rpt_dataset_csr_*,

@@ -381,6 +381,7 @@ int32_t rpt_ctx_destroy(rpt_ctx* ctx) {
     if (ctx->refine_state_dev) dev_free(ctx->refine_state_dev);
     if (ctx->search_state_dev) dev_free(ctx->search_state_dev);
     if (ctx->prepare_state_dev) dev_free(ctx->prepare_state_dev);
+    if (ctx->insert_state_dev) dev_free(ctx->insert_state_dev);
     dev_trim();
     delete ctx;
     return RPT_OK;
@@ -1809,6 +1810,104 @@ int32_t rpt_graph_prepare_last(rpt_ctx* ctx, int64_t* pairs, int64_t* occluded, 
     RPT_ARG(ctx && pairs && occluded && capped, "NULL argument");
     RPT_HIP(hipSetDevice(ctx->device));
     return graph_prepare_last(ctx, pairs, occluded, capped);
+  });
+}
+
+// ---- new rows into a kNN graph -------------------------------------------------------------------
+namespace {
+// one pair of entry points for dense and CSR data under every metric
+int32_t check_insert(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, int64_t m, int32_t s, int32_t ef,
+                     int64_t batch, int32_t metric, int32_t flags) {
+  RPT_ARG(ctx && data, "NULL argument");
+  RPT_ARG(data->ctx == ctx, "handles belong to another context");
+  RPT_TRY(check_graph_metric(metric));
+  RPT_ARG(flags == 0, "flags must be 0");
+  RPT_ARG(kg >= 1 && kg <= RPT_GRAPH_MAX_K, "kg must be in [1,64] (RPT_GRAPH_MAX_K)");
+  RPT_ARG(s >= 1 && s <= 64, "s (seeds per new row) must be in [1,64]");
+  RPT_ARG(ef >= kg, "ef must be at least kg");
+  RPT_ARG(ef <= RPT_GRAPH_SEARCH_MAX_EF, "ef must be at most 256 (RPT_GRAPH_SEARCH_MAX_EF)");
+  RPT_ARG(batch >= 1, "batch must be at least 1");
+  RPT_ARG(m >= 0 && m <= data->n, "m must be in [0, data.n]: the new rows are the data set's last m");
+  RPT_ARG(data->n <= 0x7fffffff, "graph too large");
+  RPT_ARG(std::min<int64_t>(batch, m) * kg <= 0x7fffffff, "a chunk of min(batch, m) rows holds 2^31 or more entries");
+  return RPT_OK;
+}
+
+int32_t insert_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_dev,
+                   const double* gdist_dev, const int32_t* gcount_dev, int64_t m, int32_t s,
+                   const int32_t* seeds_dev, int32_t ef, int64_t batch, int32_t metric, int32_t flags,
+                   int32_t* oids_dev, double* odist_dev, int32_t* ocount_dev) {
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_TRY(check_insert(ctx, data, kg, m, s, ef, batch, metric, flags));
+  RPT_ARG(data->n == m || (gids_dev && gdist_dev && gcount_dev), "NULL graph arrays");
+  RPT_ARG(m == 0 || seeds_dev, "NULL seeds");
+  RPT_ARG(data->n == 0 || (oids_dev && odist_dev && ocount_dev), "NULL output");
+  RPT_HIP(hipSetDevice(ctx->device));
+  return graph_insert_dev(ctx, data, kg, gids_dev, gdist_dev, gcount_dev, m, s, seeds_dev, ef, batch, metric,
+                          oids_dev, odist_dev, ocount_dev);
+}
+
+int32_t insert_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_host,
+                    const double* gdist_host, const int32_t* gcount_host, int64_t m, int32_t s,
+                    const int32_t* seeds_host, int32_t ef, int64_t batch, int32_t metric, int32_t flags,
+                    int32_t* oids_host, double* odist_host, int32_t* ocount_host) {
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_TRY(check_insert(ctx, data, kg, m, s, ef, batch, metric, flags));
+  const int64_t N = data->n, n = N - m;
+  RPT_ARG(n == 0 || (gids_host && gdist_host && gcount_host), "NULL graph arrays");
+  RPT_ARG(m == 0 || seeds_host, "NULL seeds");
+  RPT_ARG(N == 0 || (oids_host && odist_host && ocount_host), "NULL output");
+  // before anything is uploaded: the graph's counts and ids, then the seeds, which may name new rows
+  RPT_TRY(check_search_arrays(n, 0, kg, gids_host, gcount_host, s, nullptr));
+  for (int64_t q = 0; q < m; ++q)
+    for (int32_t e = 0; e < s; ++e) {
+      const int32_t id = seeds_host[q * s + e];
+      if (id != -1 && (id < 0 || id >= N))
+        return fail(RPT_E_ARG, "seeds row " + std::to_string(q) + ": id " + std::to_string(id) +
+                                   " is neither -1 nor in [0, N)");
+    }
+  RPT_HIP(hipSetDevice(ctx->device));
+  Triple g, out;
+  DevBuf<int32_t> seeds;
+  RPT_TRY(g.alloc(n, kg));
+  RPT_TRY(out.alloc(N, kg));
+  RPT_TRY(seeds.alloc((size_t)m * s));
+  RPT_TRY(g.upload(gids_host, gdist_host, gcount_host));
+  if (m) RPT_HIP(hipMemcpy(seeds.p, seeds_host, (size_t)m * s * 4, hipMemcpyHostToDevice));
+  RPT_TRY(insert_dev(ctx, data, kg, g.ids.p, g.dist.p, g.cnt.p, m, s, seeds.p, ef, batch, metric, flags,
+                     out.ids.p, out.dist.p, out.cnt.p));
+  RPT_HIP(stream_sync(ctx->stream));
+  return out.download(oids_host, odist_host, ocount_host);
+}
+}  // namespace
+
+int32_t rpt_graph_insert_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_dev,
+                             const double* gdist_dev, const int32_t* gcount_dev, int64_t m, int32_t s,
+                             const int32_t* seeds_dev, int32_t ef, int64_t batch, int32_t metric,
+                             int32_t flags, int32_t* oids_dev, double* odist_dev, int32_t* ocount_dev) {
+  return guarded([&]() -> int32_t {
+    return insert_dev(ctx, data, kg, gids_dev, gdist_dev, gcount_dev, m, s, seeds_dev, ef, batch, metric, flags,
+                      oids_dev, odist_dev, ocount_dev);
+  });
+}
+
+int32_t rpt_graph_insert_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_host,
+                              const double* gdist_host, const int32_t* gcount_host, int64_t m, int32_t s,
+                              const int32_t* seeds_host, int32_t ef, int64_t batch, int32_t metric,
+                              int32_t flags, int32_t* oids_host, double* odist_host, int32_t* ocount_host) {
+  return guarded([&]() -> int32_t {
+    return insert_host(ctx, data, kg, gids_host, gdist_host, gcount_host, m, s, seeds_host, ef, batch, metric,
+                       flags, oids_host, odist_host, ocount_host);
+  });
+}
+
+int32_t rpt_graph_insert_last(rpt_ctx* ctx, int64_t* chunks, int64_t* evaluated, int64_t* offered,
+                              int64_t* accepted) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ctx && chunks && evaluated && offered && accepted, "NULL argument");
+    RPT_HIP(hipSetDevice(ctx->device));
+    return graph_insert_last(ctx, chunks, evaluated, offered, accepted);
   });
 }
 

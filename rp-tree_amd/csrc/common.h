@@ -139,7 +139,7 @@ struct DevBuf {
 
 // kernel classes timed by rpt_prof_* (HIP events on the ctx stream)
 enum { RPT_PROF_PROJECT = 0, RPT_PROF_SPLIT = 1, RPT_PROF_KNN_PLAN = 2, RPT_PROF_KNN_TOPK = 3,
-       RPT_PROF_PROJECT_WIDE = 4, RPT_PROF_KNN_VOTE = 5, RPT_PROF_CLASSES = 6 };
+       RPT_PROF_PROJECT_WIDE = 4, RPT_PROF_KNN_VOTE = 5, RPT_PROF_GRAPH_LINK = 6, RPT_PROF_CLASSES = 7 };
 
 struct rpt_prof_span {
   hipEvent_t a, b;
@@ -236,6 +236,7 @@ struct rpt_ctx {
   void* refine_state_dev = nullptr;  // graph_refine.hip: the last rpt_knn_graph_refine_* call's flag and counters
   void* search_state_dev = nullptr;  // graph_search.hip: the last rpt_graph_search_* call's counters
   void* prepare_state_dev = nullptr;  // graph_prepare.hip: the last rpt_graph_prepare_* call's counters
+  void* insert_state_dev = nullptr;  // graph_insert.hip: the last rpt_graph_insert_* call's counters
   int32_t last_tier = 0;  // ranking tier of the last fused kNN call: 0 exact, 1 f32 shadow, 2 half, 3 int8
   // last build: nodes csub_kernel handed back to the general kernels (pivot codes shared by more
   // points than its pool), and how many of those for a histogram that contradicted the node
@@ -246,8 +247,8 @@ struct rpt_ctx {
   std::vector<rpt_prof_span> spans;
   std::vector<hipEvent_t> prof_events;  // resolved spans' events, reused (creating a pair per span
                                         // cost ~5 us: 0.07 ms of a profiled C2 build)
-  double prof_ms[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0, 0};
-  int64_t prof_n[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0, 0};
+  double prof_ms[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0, 0, 0};
+  int64_t prof_n[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace rpt {
@@ -495,6 +496,17 @@ int32_t graph_prepare_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t k, cons
                           int32_t* out_count_dev);
 // synchronises the stream
 int32_t graph_prepare_last(rpt_ctx* ctx, int64_t* pairs, int64_t* occluded, int64_t* capped);
+// ---- new rows into a kNN graph (graph_insert.hip) -----------------------------------------------
+// arguments checked by the caller (data of N = n + m rows, dense or CSR; kg, s <= 64, kg <= ef <=
+// RPT_GRAPH_SEARCH_MAX_EF, batch >= 1, 0 <= m <= N; metric as knn_graph_dev's); the input graph of
+// n rows is read only and not validated; the output arrays hold N rows; enqueued on the ctx stream
+int32_t graph_insert_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_dev,
+                         const double* gdist_dev, const int32_t* gcount_dev, int64_t m, int32_t s,
+                         const int32_t* seeds_dev, int32_t ef, int64_t batch, int32_t metric,
+                         int32_t* oids_dev, double* odist_dev, int32_t* ocount_dev);
+// synchronises the stream
+int32_t graph_insert_last(rpt_ctx* ctx, int64_t* chunks, int64_t* evaluated, int64_t* offered,
+                          int64_t* accepted);
 int32_t knn_h(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
               int32_t k, int64_t* off_host, int32_t* ids_host, double* dist_host, int64_t cap,
               int64_t* total);

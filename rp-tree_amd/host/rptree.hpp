@@ -808,6 +808,57 @@ inline KnnResult graphSearchAllow(const RPForest& tts, const GraphResult& g, con
                           seed_k, metric, stats);
 }
 
+// New rows into a kNN graph (rpt_graph_insert_host): `data` holds N = n + m rows whose LAST m are the
+// new ones, g is a graph over the first n (its distances ARE read), dense or CSR rows under any Metric
+// (the one g was built under).  The new rows are taken in chunks of `batch`; every row of a chunk is
+// answered by graphSearch with k = g.k and this ef over the rows visible so far (the first n and the
+// chunks before it, not its own chunk), the answer becomes the new row, and every row it names takes
+// the new id at the same distance when that is among its first g.k by (distance, id).  seeds[m][s]
+// (-1 = unused; a seed may name a row of an earlier chunk).  The result is a pure function of its
+// inputs, bit for bit; m = 0 copies the graph.  A smaller batch links more (rows of one chunk do not
+// see each other; knnGraphRefine afterwards links them), a larger one fills the device.
+struct InsertStats {
+  int64_t chunks = 0, evaluated = 0, offered = 0, accepted = 0;
+};
+inline GraphResult graphInsert(Context& ctx, const Dataset& data, const GraphResult& g, int64_t m, int ef,
+                               int64_t batch, const std::vector<int32_t>& seeds, int s, Metric metric = Metric::L2,
+                               InsertStats* stats = nullptr) {
+  const size_t N = (size_t)data.n, n = N - (size_t)m;
+  if (m < 0 || (size_t)m > N || g.count.size() != n || g.ids.size() != n * (size_t)(g.k > 0 ? g.k : 0) ||
+      g.dist.size() != g.ids.size())
+    throw RPTError(RPT_E_ARG, "graphInsert: the graph must be over the first n = N - m rows of data");
+  if (s < 1 || seeds.size() != (size_t)m * (size_t)s) throw RPTError(RPT_E_ARG, "graphInsert: seeds must be [m][s]");
+  const int32_t none = -1;  // non-NULL pointers for empty inputs
+  const double nod = 0.0;
+  const size_t k = (size_t)(g.k > 0 ? g.k : 0);
+  GraphResult r;
+  r.k = g.k;
+  r.ids.resize(N * k + 1);
+  r.dist.resize(N * k + 1);
+  r.count.resize(N + 1);
+  check(rpt_graph_insert_host(ctx.get(), data.get(), g.k, n ? g.ids.data() : &none, n ? g.dist.data() : &nod,
+                              n ? g.count.data() : &none, m, s, m ? seeds.data() : &none, ef, batch,
+                              metric_flags(metric), 0, r.ids.data(), r.dist.data(), r.count.data()));
+  r.ids.resize(N * k);
+  r.dist.resize(N * k);
+  r.count.resize(N);
+  if (stats)
+    check(rpt_graph_insert_last(ctx.get(), &stats->chunks, &stats->evaluated, &stats->offered, &stats->accepted));
+  return r;
+}
+// ... the seeds taken from a forest over the OLD n rows: `fresh` holds the m new rows alone (the last
+// m rows of data once more), batch 0 = min(m, 4096) (kept after tools/graph_insert_times.py's sweep)
+inline GraphResult graphInsert(const RPForest& old, const Dataset& data, const Dataset& fresh, const GraphResult& g,
+                               int ef, int64_t batch = 0, Metric metric = Metric::L2, int seed_k = 8,
+                               InsertStats* stats = nullptr) {
+  const bool csr_metric = old.data->csr && metric != Metric::L2;
+  if (batch == 0) batch = std::max<int64_t>(1, std::min<int64_t>(fresh.n, 4096));
+  return graphInsert(*old.ctx, data, g, fresh.n, ef, batch,
+                     forestSeeds(old, fresh, seed_k, csr_metric ? rpt_knn_csr_metric_host : rpt_knn_host,
+                                 RPT_KNN_DEDUP | metric_flags(metric), "graphInsert"),
+                     seed_k, metric, stats);
+}
+
 struct BruteResult {
   std::vector<int32_t> ids;  // [nq][k], -1 = unused slot
   std::vector<double> dist;  // [nq][k]

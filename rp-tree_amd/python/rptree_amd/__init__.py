@@ -44,6 +44,7 @@ __all__ = [
     "knnGraphMetricSV", "knnGraphMetricSVDev", "knnGraphRefineMetricSV", "knnGraphRefineMetricSVDev",
     "graphSearch", "graphSearchDev", "graphSearchLast", "graphSearchSV", "graphSearchSVDev",
     "graphSearchAllow", "graphSearchAllowDev", "allowBitmap",
+    "graphInsert", "graphInsertDev", "graphInsertLast",
     "graphPrepare", "graphPrepareDev", "graphPrepareLast", "graphPrepareSV", "graphPrepareSVDev",
     "graphSearchMetricSV", "graphSearchMetricSVDev", "graphPrepareMetricSV", "graphPrepareMetricSVDev",
     "knnVote", "knnVoteDev", "voteCandidates", "knnVoteLast",
@@ -1305,6 +1306,102 @@ def graphSearchLast(ctx=None):
     a, b = C.c_int64(), C.c_int64()
     check(lib().rpt_graph_search_last(ctx._h, C.byref(a), C.byref(b)))
     return int(a.value), int(b.value)
+
+
+def _insert_rows(data, n):
+    """the new rows of graphInsert's `data` as knnBatch takes queries: the rows from n on"""
+    if isinstance(data, Dataset):
+        if data._host is None:
+            raise ValueError("graphInsert takes seeds from a forest only when it is handed the rows themselves "
+                             "(an array or a CSR tuple, or a Dataset made from float64 rows): pass seeds")
+        return data._host[n:]
+    if isinstance(data, tuple):
+        rowptr = np.asarray(data[0], dtype=np.int64)
+        lo, hi = int(rowptr[n]), int(rowptr[-1])
+        return rowptr[n:] - lo, np.asarray(data[1])[lo:hi], np.asarray(data[2])[lo:hi], data[3]
+    return np.asarray(data)[n:]
+
+
+def graphInsert(graph, data, m, ef=None, batch=None, seeds=None, forest=None, seed_k=8, metric=None, ctx=None):
+    """New rows into a kNN graph (rpt_graph_insert_host) -> (ids[N][kg], dist[N][kg], count[N]): the
+    graph grows, nothing is rebuilt.  data: the data set of N = n + m rows whose LAST m rows are the new
+    ones, as a 2-D array (float64, float32, or uint16 bf16 patterns), a CSR tuple (rowptr, col, val, d)
+    or a dense or CSR Dataset; graph: (ids[n][kg], dist[n][kg], count[n]) over the first n rows
+    (knnGraph's, knnGraphRefine's; the distances ARE read); metric: None / metricL2, metricCosine or
+    metricInner, the one the graph was built under, on either layout.  The new rows are taken in
+    chunks of `batch`.  Every row of a chunk is answered by graphSearch with k = kg and this ef (None
+    = max(kg, 32)) over the rows visible so far: the first n and the chunks before it, not its own
+    chunk.  The answer becomes the new row, and every row it names takes the new id at the same
+    distance when that is among its first kg by (distance, id).  Rows of one chunk do not see each
+    other (knnGraphRefine afterwards links them): a smaller batch links more, a larger one fills the
+    device.  batch None = min(m, 4096): kept after the sweep of tools/graph_insert_times.py at 1 M x 128
+    (74 / 25 / 19 / 14 ms at batch 1024 / 4096 / 16384 / m = 100 000: one chunk is the fastest, and its
+    rows are linked to old rows only).  seeds[m][s] (s <= 64, -1 = unused; a seed may name a row of an earlier chunk)
+    or, with `forest`, a forest over the OLD n rows, the ids of knnBatch(seed_k, forest, new rows,
+    dedup=True, metric=metric).  The result is a pure function of its inputs, bit for bit; m = 0
+    copies the graph."""
+    metric_flag = _metric_flag(metric)
+    ctx = ctx or (data.ctx if isinstance(data, Dataset) else default_context())
+    if isinstance(data, np.ndarray) and data.dtype == np.uint16:
+        ds = Dataset.dense(ctx, data, dtype=RPT_BF16)
+    else:
+        ds = Dataset.of(ctx, data)
+    m = int(m)
+    N, n = ds.n, ds.n - m
+    gids = np.ascontiguousarray(graph[0], dtype=np.int32)
+    gdist = np.ascontiguousarray(graph[1], dtype=np.float64)
+    gcnt = np.ascontiguousarray(graph[2], dtype=np.int32)
+    if m < 0 or n < 0 or gids.ndim != 2 or gids.shape[0] != n or gdist.shape != gids.shape or gcnt.shape != (n,):
+        raise ValueError("graph must be (ids[n][kg], dist[n][kg], count[n]) over the first n = N - m rows of data")
+    kg = int(gids.shape[1])
+    if ef is None:
+        ef = max(kg, 32)
+    if batch is None:
+        batch = max(1, min(m, 4096))
+    if seeds is None:
+        if forest is None:
+            raise ValueError("graphInsert needs seeds or a forest over the old rows to take them from")
+        if m:
+            sid, _, scnt = knnBatch(int(seed_k), forest, _insert_rows(data, n), dedup=True, metric=metric)
+            seeds = np.where(np.arange(sid.shape[1])[None, :] < scnt[:, None], sid, -1)
+        else:
+            seeds = np.zeros((0, int(seed_k)), dtype=np.int32)
+    seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+    if seeds.ndim != 2 or seeds.shape[0] != m:
+        raise ValueError("seeds must be [m][s]")
+    ids = np.empty((N, kg), dtype=np.int32)
+    dist = np.empty((N, kg), dtype=np.float64)
+    cnt = np.empty(N, dtype=np.int32)
+    check(lib().rpt_graph_insert_host(ctx._h, ds._h, kg, _vp(gids), _vp(gdist), _vp(gcnt), m, int(seeds.shape[1]),
+                                      _vp(seeds), int(ef), int(batch), metric_flag, 0, _vp(ids), _vp(dist),
+                                      _vp(cnt)))
+    return ids, dist, cnt
+
+
+def graphInsertDev(data, kg, gids_ptr, gdist_ptr, gcount_ptr, m, s, seeds_ptr, ef, batch, oids_ptr, odist_ptr,
+                   ocount_ptr, metric=None):
+    """graphInsert on device arrays (rpt_graph_insert_dev): data is the Dataset of N = n + m rows, the
+    graph (int32 [n][kg], float64 [n][kg], int32 [n]), the seeds (int32 [m][s]) and the outputs (int32
+    [N][kg], float64 [N][kg], int32 [N]) device addresses.  The input graph is read only and NOT
+    validated: rows nothing links to are copied as they are, touched rows come out sorted without
+    their invalid entries.  Enqueued on the ctx stream, not synchronised (ctx.sync() before reading);
+    whatever filled the arrays must have finished (see Dataset.dense_device)."""
+    metric_flag = _metric_flag(metric)
+    ds = _refine_data(data)
+    check(lib().rpt_graph_insert_dev(ds.ctx._h, ds._h, int(kg), C.c_void_p(gids_ptr), C.c_void_p(gdist_ptr),
+                                     C.c_void_p(gcount_ptr), int(m), int(s), C.c_void_p(seeds_ptr), int(ef),
+                                     int(batch), metric_flag, 0, C.c_void_p(oids_ptr), C.c_void_p(odist_ptr),
+                                     C.c_void_p(ocount_ptr)))
+
+
+def graphInsertLast(ctx=None):
+    """(chunks, evaluated, offered, accepted) of the last graphInsert call on ctx (rpt_graph_insert_last;
+    synchronises): chunks searched and linked, distances the searches computed, reverse entries offered
+    to the rows the answers name, and those that were in their row when it was written."""
+    ctx = ctx or default_context()
+    a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().rpt_graph_insert_last(ctx._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return int(a.value), int(b.value), int(c.value), int(d.value)
 
 
 def _prepare_flags(diversify, reverse):

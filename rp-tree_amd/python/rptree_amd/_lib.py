@@ -102,6 +102,9 @@ SYMBOLS = {
     "rpt_graph_search_allow_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_allow_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_search_last": (i32, [vp, p_i64, p_i64]),
+    "rpt_graph_insert_dev": (i32, [vp, vp, i32, vp, vp, vp, i64, i32, vp, i32, i64, i32, i32, vp, vp, vp]),
+    "rpt_graph_insert_host": (i32, [vp, vp, i32, vp, vp, vp, i64, i32, vp, i32, i64, i32, i32, vp, vp, vp]),
+    "rpt_graph_insert_last": (i32, [vp, p_i64, p_i64, p_i64, p_i64]),
     "rpt_graph_prepare_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_prepare_host": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_prepare_csr_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
