@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchAllowHIP, graphInsertHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchAllowHIP, graphInsertHIP, graphDeleteHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -60,6 +60,7 @@ foreign import ccall safe "rpt_knn_graph_refine_csr_metric_host" c_knn_graph_ref
 foreign import ccall safe "rpt_graph_search_host" c_graph_search_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_allow_host" c_graph_search_allow_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Ptr Word32 -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_insert_host" c_graph_insert_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int64 -> Int32 -> Ptr Int32 -> Int32 -> Int64 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_graph_delete_host" c_graph_delete_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Ptr Word32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_search_csr_host" c_graph_search_csr_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_host" c_graph_prepare_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_graph_prepare_csr_host" c_graph_prepare_csr_host :: Ptr Ctx -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
@@ -446,6 +447,29 @@ graphInsertHIP ctx ds metric n m kg (gids, gdist, gcount) s seeds ef batch = do
     VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
       c_graph_insert_host ctx ds (fromIntegral kg) pg pd pc (fromIntegral m) (fromIntegral s) ps (fromIntegral ef) (fromIntegral batch) (metricFlag metric) 0 a b))))))) >>= check
   (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | Rows out of a kNN graph (rpt_graph_delete_host): @keep@ holds the ceil(n / 32) words of the tombstone
+-- bitmap 'graphSearchAllowHIP' takes, unchanged (a set bit = the row STAYS; 'Nothing' = every row
+-- stays); the graph is over the n rows of @ds@ (dense or CSR, under any 'Metric') and its distances ARE
+-- read.  The deleted rows are dropped; a kept row that named one becomes the first kg by (distance, id)
+-- of its kept entries, at their stored distances, and the kept neighbours of its deleted neighbours,
+-- at their distance to the row (one hop; 'knnGraphRefineHIP' afterwards repairs rows that end short).
+-- @compact@: the survivors are renumbered densely and the result has popcount rows; otherwise n rows
+-- in old ids with the deleted rows empty.  Returns the graph and newid[n] (the new id, or -1).  A pure
+-- function of its inputs, bit for bit.
+graphDeleteHIP :: Ptr Ctx -> Ptr Dataset -> Metric -> Int -> Int
+               -> (VS.Vector Int32, VS.Vector Double, VS.Vector Int32) -> Maybe (VS.Vector Word32) -> Bool
+               -> IO ((VS.Vector Int32, VS.Vector Double, VS.Vector Int32), VS.Vector Int32)
+graphDeleteHIP ctx ds metric n kg (gids, gdist, gcount) keep compact = do
+  ids <- VSM.new (n * kg); dist <- VSM.new (n * kg); cnt <- VSM.new n; newid <- VSM.new n
+  let withKeep f = maybe (f nullPtr) (\w -> VS.unsafeWith w f) keep
+  VS.unsafeWith gids (\pg -> VS.unsafeWith gdist (\pd -> VS.unsafeWith gcount (\pc -> withKeep (\pk ->
+    VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (\c -> VSM.unsafeWith newid (
+      c_graph_delete_host ctx ds (fromIntegral kg) pg pd pc pk (metricFlag metric) (if compact then 1 else 0) a b c)))))))) >>= check
+  nid <- VS.freeze newid
+  let rows = if compact then VS.length (VS.filter (>= 0) nid) else n
+  i <- VS.freeze ids; d <- VS.freeze dist; c <- VS.freeze cnt
+  pure ((VS.take (rows * kg) i, VS.take (rows * kg) d, VS.take rows c), nid)
 
 -- | A kNN graph made ready for 'graphSearchHIP' (rpt_graph_prepare_host), PyNNDescent's search graph.
 -- @diversify@: walking a row in stored order, a neighbour is dropped when an already kept neighbour

@@ -151,6 +151,7 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *   graph_general (0 / 1)          kNN graph: every leaf on the tiled kernel (rpt_knn_graph_*)
  *   graph_refine_general (0 / 1)   kNN graph refinement: one point per workgroup for every k and
  *                                  reverse (rpt_knn_graph_refine_*)
+ *   graph_delete_general (0 / 1)   rpt_graph_delete_*: one touched row per workgroup for every kg
  *   graph_csr_masked (0 / 1)       kNN graph on CSR rows under cosine / inner product: the
  *                                  presence-masked fold for every call, not only for data that stores
  *                                  an inf or NaN (rpt_knn_graph_csr_metric_*)
@@ -187,7 +188,9 @@ int32_t rpt_ctx_get_option(rpt_ctx* ctx, const char* name, int64_t* value);
  * 2 = query plan (query projections + traversal), 3 = distance/top-k kernel, 4 = the wide
  * (> 32 hyperplanes per pass) MFMA projection launches alone (they are also part of class 0),
  * 5 = the vote-select kernel of rpt_knn_vote_* / rpt_vote_candidates_host, 6 = the link kernels of
- * rpt_graph_insert_* (one launch = the link of one chunk; its searches are class 3).
+ * rpt_graph_insert_* (one launch = the link of one chunk; its searches are class 3), 8 = the mark,
+ * scan, copy and repair kernels of rpt_graph_delete_* (one launch = one call).  7 is not a class:
+ * rpt_prof_get answers RPT_E_ARG for it.
  * rpt_prof_get synchronises the stream and returns the accumulated ms and launch count. */
 int32_t rpt_prof_enable(rpt_ctx* ctx, int32_t on);
 int32_t rpt_prof_reset(rpt_ctx* ctx);
@@ -836,6 +839,84 @@ int32_t rpt_graph_insert_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg,
                               int32_t flags, int32_t* oids_host, double* odist_host, int32_t* ocount_host);
 int32_t rpt_graph_insert_last(rpt_ctx* ctx, int64_t* chunks, int64_t* evaluated, int64_t* offered,
                               int64_t* accepted);
+
+/* ---- delete rows from a kNN graph ----
+ * rpt_graph_delete_* is the other half of a dynamic index: rows leave the graph without a rebuild.  A
+ * tombstone bitmap (rpt_graph_search_allow_*) only hides rows; here the deleted rows are dropped,
+ * every list that named one is repaired from the deleted row's own neighbours (the delete
+ * consolidation of FreshDiskANN, adapted to graphs that store distances, order rows by (distance, id)
+ * and answer bit for bit), and the survivors are optionally renumbered densely.  One pair of entry
+ * points serves dense data (f64, f32, bf16) and CSR data (f64, f32) under `metric` 0,
+ * RPT_KNN_METRIC_COSINE and RPT_KNN_METRIC_INNER.
+ * Inputs:
+ *   data        a data set of n rows.
+ *   gids, gdist, gcount   a graph in rpt_knn_graph_*'s layout: ids[n][kg], dist[n][kg], count[n], kg in
+ *               [1, RPT_GRAPH_MAX_K].  The stored distances ARE read.  The caller's graph is read
+ *               only; the output arrays overlap none of the inputs.
+ *   keep        the bitmap format of rpt_graph_search_allow_*: ceil(n / 32) uint32_t words, id i = bit
+ *               i & 31 of word i >> 5, bits at positions >= n ignored, NULL = every row stays.  A set
+ *               bit means the row STAYS: a tombstone bitmap a caller searches with is passed
+ *               unchanged.
+ *   flags       0 or RPT_GRAPH_DELETE_COMPACT.
+ * Outputs: oids[n][kg], odist[n][kg], ocount[n] (sized for n rows) and newid[n] (int32; may be NULL).
+ * Definition.  Ids are old ids throughout.  The VALID entries of row j are, as rpt_graph_insert_*
+ * states for touched rows: the slots below the count clamped to [0, kg], whose id is in [0, n) and is
+ * not j; an id the row holds twice counts once, at its first slot.  For a kept row p, K(p) is the
+ * valid entries of row p whose id is kept, with their STORED distances, and D(p) is the ids of the
+ * valid entries of row p that are deleted.
+ *   Untouched row (D(p) is empty): copied slot for slot, whatever it holds, the distance bits verbatim;
+ *               an id in [0, n) is replaced by newid of it, any other id is left as it is; the count
+ *               is verbatim.
+ *   Touched row (D(p) is not empty): with
+ *                 C(p) = { e : e is the id of a valid entry of row j for some j in D(p), e is kept,
+ *                          e != p, e is not an id of K(p) }, each id once,
+ *               row p becomes the first kg, by the order of the search ((distance, id); NaN behind
+ *               every number, NaNs among themselves by id; -0.0 ties with +0.0), of
+ *                 K(p) u { (dist(p, e), e) : e in C(p) }.
+ *               It is written sorted, the count is the size of the result, unused slots hold id -1 and
+ *               distance +inf.  dist is the graph code's distance for the layout and metric: the dense
+ *               folds, the union fold for CSR rows under L2, dotS for CSR rows under cosine / inner
+ *               product, with the cached norms for cosine.  Those distances are symmetric bit for
+ *               bit, so a new entry holds exactly the bits rpt_knn_graph_* or a refinement round would
+ *               store for that pair.
+ *   One hop only  A deleted neighbour's deleted neighbours are not followed: a row whose neighbours and
+ *               all their neighbours are gone ends with fewer than kg entries, or none.  A
+ *               rpt_knn_graph_refine_* round afterwards repairs such rows.
+ *   Without RPT_GRAPH_DELETE_COMPACT  the output has n rows in old ids; a deleted row has count 0, ids
+ *               -1 and distances +inf; newid[i] is i, or -1 for a deleted row.  The result is
+ *               searchable with the unchanged data set: no kept row names a deleted one, so only
+ *               seeds can reach one.
+ *   With RPT_GRAPH_DELETE_COMPACT  newid[i] is the number of kept rows below i, or -1; the output has
+ *               n' = popcount rows; row newid[p] is row p of the other form with every id mapped
+ *               through newid; rows n' .. n of the output arrays are not written.  Compacting the
+ *               data set is the caller's business.
+ * The result is a pure function of (data, graph, keep, metric, flags): the same bits on every call and
+ * every launch shape.  No atomics touch a row and one wave writes it.  Touched rows are repaired four
+ * to a workgroup while four waves' shares of LDS fit, one to a workgroup beyond (dense rows at kg =
+ * 64); the context option graph_delete_general sends every row there; the answer does not depend on
+ * it.  Scratch is sized by n alone: 8 n bytes, 12 n when newid is NULL.
+ * rpt_graph_delete_last: kept = the kept rows; touched = the touched rows; evaluated = the sum of
+ * |C(p)|, the distances evaluated; dropped = the sum of |D(p)|, the valid entries of kept rows that
+ * named a deleted row.  All four are sums.
+ * Errors: kg out of range, flag bits other than RPT_GRAPH_DELETE_COMPACT, any other `metric` value,
+ * both metric bits together, RPT_KNN_METRIC_REFERENCE: RPT_E_ARG; no room for the scratch:
+ * RPT_E_NOMEM.  _host validates the counts and ids in [0, n) before anything is uploaded, as
+ * rpt_graph_insert_host does, names the offending row, and synchronises; with COMPACT it writes the n'
+ * rows of the answer and leaves the rest of the caller's arrays as they were.  _dev borrows device
+ * arrays, does NOT validate and does not synchronise: with junk rows it stays in bounds and
+ * terminates, untouched rows verbatim and touched rows cleaned.  n = 0, keep = nothing and keep =
+ * everything are valid.  A refused call leaves the context usable. */
+#define RPT_GRAPH_DELETE_COMPACT 1
+int32_t rpt_graph_delete_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_dev,
+                             const double* gdist_dev, const int32_t* gcount_dev, const uint32_t* keep_dev,
+                             int32_t metric, int32_t flags, int32_t* oids_dev, double* odist_dev,
+                             int32_t* ocount_dev, int32_t* newid_dev);
+int32_t rpt_graph_delete_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_host,
+                              const double* gdist_host, const int32_t* gcount_host, const uint32_t* keep_host,
+                              int32_t metric, int32_t flags, int32_t* oids_host, double* odist_host,
+                              int32_t* ocount_host, int32_t* newid_host);
+int32_t rpt_graph_delete_last(rpt_ctx* ctx, int64_t* kept, int64_t* touched, int64_t* evaluated,
+                              int64_t* dropped);
 
 /* ---- query the kNN graph on SVector (CSR) rows, under L2 ----
  * rpt_graph_search_csr_* is rpt_graph_search_* for a CSR data set and CSR queries (rpt_dataset_csr_*,

@@ -254,6 +254,7 @@ const OptDesc kOptions[] = {
     {"knn_vote_slice", &rpt_options::knn_vote_slice},
     {"graph_general", &rpt_options::graph_general},
     {"graph_refine_general", &rpt_options::graph_refine_general},
+    {"graph_delete_general", &rpt_options::graph_delete_general},
     {"graph_csr_masked", &rpt_options::graph_csr_masked},
     {"graph_search_nofilter", &rpt_options::graph_search_nofilter},
     {"graph_search_csr_stream", &rpt_options::graph_search_csr_stream},
@@ -382,6 +383,7 @@ int32_t rpt_ctx_destroy(rpt_ctx* ctx) {
     if (ctx->search_state_dev) dev_free(ctx->search_state_dev);
     if (ctx->prepare_state_dev) dev_free(ctx->prepare_state_dev);
     if (ctx->insert_state_dev) dev_free(ctx->insert_state_dev);
+    if (ctx->delete_state_dev) dev_free(ctx->delete_state_dev);
     dev_trim();
     delete ctx;
     return RPT_OK;
@@ -507,7 +509,7 @@ int32_t rpt_prof_get(rpt_ctx* ctx, int32_t which, double* total_ms, int64_t* lau
   return guarded([&]() -> int32_t {
     if (ctx) dev_set_stream(ctx->stream);
     RPT_ARG(ctx && total_ms && launches, "NULL argument");
-    RPT_ARG(which >= 0 && which < RPT_PROF_CLASSES, "unknown kernel class");
+    RPT_ARG(which >= 0 && which < RPT_PROF_CLASSES && which != 7, "unknown kernel class");
     RPT_HIP(hipSetDevice(ctx->device));
     RPT_HIP(stream_sync(ctx->stream));
     prof_resolve(ctx);
@@ -1908,6 +1910,98 @@ int32_t rpt_graph_insert_last(rpt_ctx* ctx, int64_t* chunks, int64_t* evaluated,
     RPT_ARG(ctx && chunks && evaluated && offered && accepted, "NULL argument");
     RPT_HIP(hipSetDevice(ctx->device));
     return graph_insert_last(ctx, chunks, evaluated, offered, accepted);
+  });
+}
+
+// ---- rows out of a kNN graph ---------------------------------------------------------------------
+namespace {
+// one pair of entry points for dense and CSR data under every metric
+int32_t check_delete(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, int32_t metric, int32_t flags) {
+  RPT_ARG(ctx && data, "NULL argument");
+  RPT_ARG(data->ctx == ctx, "handles belong to another context");
+  RPT_TRY(check_graph_metric(metric));
+  RPT_ARG((flags & ~RPT_GRAPH_DELETE_COMPACT) == 0, "flags must be 0 or RPT_GRAPH_DELETE_COMPACT");
+  RPT_ARG(kg >= 1 && kg <= RPT_GRAPH_MAX_K, "kg must be in [1,64] (RPT_GRAPH_MAX_K)");
+  RPT_ARG(data->n <= 0x7fffffff, "graph too large");
+  return RPT_OK;
+}
+
+int32_t delete_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_dev,
+                   const double* gdist_dev, const int32_t* gcount_dev, const uint32_t* keep_dev, int32_t metric,
+                   int32_t flags, int32_t* oids_dev, double* odist_dev, int32_t* ocount_dev, int32_t* newid_dev) {
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_TRY(check_delete(ctx, data, kg, metric, flags));
+  RPT_ARG(data->n == 0 || (gids_dev && gdist_dev && gcount_dev), "NULL graph arrays");
+  RPT_ARG(data->n == 0 || (oids_dev && odist_dev && ocount_dev), "NULL output");
+  RPT_HIP(hipSetDevice(ctx->device));
+  return graph_delete_dev(ctx, data, kg, gids_dev, gdist_dev, gcount_dev, keep_dev, metric, flags, oids_dev,
+                          odist_dev, ocount_dev, newid_dev);
+}
+
+int32_t delete_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_host,
+                    const double* gdist_host, const int32_t* gcount_host, const uint32_t* keep_host,
+                    int32_t metric, int32_t flags, int32_t* oids_host, double* odist_host, int32_t* ocount_host,
+                    int32_t* newid_host) {
+  if (ctx) dev_set_stream(ctx->stream);
+  RPT_TRY(check_delete(ctx, data, kg, metric, flags));
+  const int64_t n = data->n;
+  RPT_ARG(n == 0 || (gids_host && gdist_host && gcount_host), "NULL graph arrays");
+  RPT_ARG(n == 0 || (oids_host && odist_host && ocount_host), "NULL output");
+  RPT_TRY(check_search_arrays(n, 0, kg, gids_host, gcount_host, 0, nullptr));  // before anything is uploaded
+  RPT_HIP(hipSetDevice(ctx->device));
+  Triple g, out;
+  DevBuf<uint32_t> bitmap;
+  DevBuf<int32_t> newid;
+  RPT_TRY(g.alloc(n, kg));
+  RPT_TRY(out.alloc(n, kg));
+  RPT_TRY(newid.alloc((size_t)n));
+  const size_t words = keep_host ? (size_t)((n + 31) / 32) : 0;
+  RPT_TRY(bitmap.alloc(words));
+  RPT_TRY(g.upload(gids_host, gdist_host, gcount_host));
+  if (words) RPT_HIP(hipMemcpy(bitmap.p, keep_host, words * 4, hipMemcpyHostToDevice));
+  RPT_TRY(delete_dev(ctx, data, kg, g.ids.p, g.dist.p, g.cnt.p, words ? bitmap.p : nullptr, metric, flags,
+                     out.ids.p, out.dist.p, out.cnt.p, newid.p));
+  int64_t kept = 0, touched = 0, evaluated = 0, dropped = 0;
+  RPT_TRY(graph_delete_last(ctx, &kept, &touched, &evaluated, &dropped));  // synchronises
+  // the compact form has `kept` rows; what lies behind them in the caller's arrays is left as it was
+  const size_t rows = (size_t)((flags & RPT_GRAPH_DELETE_COMPACT) ? kept : n);
+  if (rows) {
+    RPT_HIP(hipMemcpy(oids_host, out.ids.p, rows * kg * 4, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(odist_host, out.dist.p, rows * kg * 8, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(ocount_host, out.cnt.p, rows * 4, hipMemcpyDeviceToHost));
+  }
+  if (newid_host && n) RPT_HIP(hipMemcpy(newid_host, newid.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RPT_OK;
+}
+}  // namespace
+
+int32_t rpt_graph_delete_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_dev,
+                             const double* gdist_dev, const int32_t* gcount_dev, const uint32_t* keep_dev,
+                             int32_t metric, int32_t flags, int32_t* oids_dev, double* odist_dev,
+                             int32_t* ocount_dev, int32_t* newid_dev) {
+  return guarded([&]() -> int32_t {
+    return delete_dev(ctx, data, kg, gids_dev, gdist_dev, gcount_dev, keep_dev, metric, flags, oids_dev, odist_dev,
+                      ocount_dev, newid_dev);
+  });
+}
+
+int32_t rpt_graph_delete_host(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_host,
+                              const double* gdist_host, const int32_t* gcount_host, const uint32_t* keep_host,
+                              int32_t metric, int32_t flags, int32_t* oids_host, double* odist_host,
+                              int32_t* ocount_host, int32_t* newid_host) {
+  return guarded([&]() -> int32_t {
+    return delete_host(ctx, data, kg, gids_host, gdist_host, gcount_host, keep_host, metric, flags, oids_host,
+                       odist_host, ocount_host, newid_host);
+  });
+}
+
+int32_t rpt_graph_delete_last(rpt_ctx* ctx, int64_t* kept, int64_t* touched, int64_t* evaluated,
+                              int64_t* dropped) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ctx && kept && touched && evaluated && dropped, "NULL argument");
+    RPT_HIP(hipSetDevice(ctx->device));
+    return graph_delete_last(ctx, kept, touched, evaluated, dropped);
   });
 }
 

@@ -139,7 +139,9 @@ struct DevBuf {
 
 // kernel classes timed by rpt_prof_* (HIP events on the ctx stream)
 enum { RPT_PROF_PROJECT = 0, RPT_PROF_SPLIT = 1, RPT_PROF_KNN_PLAN = 2, RPT_PROF_KNN_TOPK = 3,
-       RPT_PROF_PROJECT_WIDE = 4, RPT_PROF_KNN_VOTE = 5, RPT_PROF_GRAPH_LINK = 6, RPT_PROF_CLASSES = 7 };
+       RPT_PROF_PROJECT_WIDE = 4, RPT_PROF_KNN_VOTE = 5, RPT_PROF_GRAPH_LINK = 6,
+       RPT_PROF_GRAPH_DELETE = 8,  // 7 is not a class: rpt_prof_get answers RPT_E_ARG for it
+       RPT_PROF_CLASSES = 9 };
 
 struct rpt_prof_span {
   hipEvent_t a, b;
@@ -187,6 +189,7 @@ struct rpt_options {
   int64_t knn_vote_slice = 0;   // rpt_knn_vote_*: at most this many queries per vote-select slice (0 = by the budget)
   int64_t graph_general = 0;    // kNN graph: every leaf on the tiled kernel (64-row blocks), not the one-workgroup leaf kernel
   int64_t graph_refine_general = 0;  // kNN graph refinement: one point per workgroup for every k and reverse
+  int64_t graph_delete_general = 0;  // rpt_graph_delete_*: one touched row per workgroup for every kg
   int64_t graph_csr_masked = 0;  // kNN graph on CSR rows under cosine / inner: the presence-masked fold for every call
   int64_t graph_search_nofilter = 0;  // graph search: no visited filter (only the beam itself is checked before a distance)
   int64_t graph_search_csr_stream = 0;  // graph search on CSR rows: every query passes through LDS in pieces (none stays resident)
@@ -237,6 +240,7 @@ struct rpt_ctx {
   void* search_state_dev = nullptr;  // graph_search.hip: the last rpt_graph_search_* call's counters
   void* prepare_state_dev = nullptr;  // graph_prepare.hip: the last rpt_graph_prepare_* call's counters
   void* insert_state_dev = nullptr;  // graph_insert.hip: the last rpt_graph_insert_* call's counters
+  void* delete_state_dev = nullptr;  // graph_delete.hip: the last rpt_graph_delete_* call's counters
   int32_t last_tier = 0;  // ranking tier of the last fused kNN call: 0 exact, 1 f32 shadow, 2 half, 3 int8
   // last build: nodes csub_kernel handed back to the general kernels (pivot codes shared by more
   // points than its pool), and how many of those for a histogram that contradicted the node
@@ -247,8 +251,8 @@ struct rpt_ctx {
   std::vector<rpt_prof_span> spans;
   std::vector<hipEvent_t> prof_events;  // resolved spans' events, reused (creating a pair per span
                                         // cost ~5 us: 0.07 ms of a profiled C2 build)
-  double prof_ms[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0, 0, 0};
-  int64_t prof_n[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0, 0, 0};
+  double prof_ms[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t prof_n[RPT_PROF_CLASSES] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace rpt {
@@ -507,6 +511,18 @@ int32_t graph_insert_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, cons
 // synchronises the stream
 int32_t graph_insert_last(rpt_ctx* ctx, int64_t* chunks, int64_t* evaluated, int64_t* offered,
                           int64_t* accepted);
+// ---- rows out of a kNN graph (graph_delete.hip) -------------------------------------------------
+// arguments checked by the caller (data of n rows, dense or CSR; kg <= 64; metric as knn_graph_dev's;
+// flags 0 or RPT_GRAPH_DELETE_COMPACT); the graph is read only and not validated; keep_dev: ceil(n / 32)
+// words or null (every row stays); the output arrays hold n rows and overlap no input; newid_dev may
+// be null; enqueued on the ctx stream
+int32_t graph_delete_dev(rpt_ctx* ctx, const rpt_dataset* data, int32_t kg, const int32_t* gids_dev,
+                         const double* gdist_dev, const int32_t* gcount_dev, const uint32_t* keep_dev,
+                         int32_t metric, int32_t flags, int32_t* oids_dev, double* odist_dev,
+                         int32_t* ocount_dev, int32_t* newid_dev);
+// synchronises the stream
+int32_t graph_delete_last(rpt_ctx* ctx, int64_t* kept, int64_t* touched, int64_t* evaluated,
+                          int64_t* dropped);
 int32_t knn_h(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
               int32_t k, int64_t* off_host, int32_t* ids_host, double* dist_host, int64_t cap,
               int64_t* total);

@@ -859,6 +859,60 @@ inline GraphResult graphInsert(const RPForest& old, const Dataset& data, const D
                      seed_k, metric, stats);
 }
 
+// Rows out of a kNN graph (rpt_graph_delete_host): `keep` holds the ceil(n / 32) words of allowBitmap (a
+// set bit = the row STAYS; the tombstone bitmap graphSearchAllow takes, unchanged; empty = every row
+// stays), g is a graph over data's n rows (its distances ARE read), dense or CSR rows under any Metric
+// (the one g was built under).  The deleted rows are dropped; a kept row that named one becomes the
+// first g.k by (distance, id) of its kept entries, at their stored distances, and the kept neighbours of
+// its deleted neighbours, at their distance to the row (one hop: a row whose neighbours and all their
+// neighbours are gone ends short, and knnGraphRefine afterwards repairs it).  compact: the survivors are
+// renumbered densely, newid[i] = the number of kept rows below i or -1, and the result has popcount(keep)
+// rows; otherwise it has n rows in old ids, deleted rows empty, newid[i] = i or -1, and is searchable
+// with the unchanged data set.  A pure function of its inputs, bit for bit.
+struct DeleteStats {
+  int64_t kept = 0, touched = 0, evaluated = 0, dropped = 0;
+};
+struct DeleteResult {
+  GraphResult graph;
+  std::vector<int32_t> newid;  // [n]
+};
+inline DeleteResult graphDelete(Context& ctx, const Dataset& data, const GraphResult& g,
+                                const std::vector<uint32_t>& keep, bool compact, Metric metric,
+                                DeleteStats* stats = nullptr) {
+  const size_t n = (size_t)data.n, k = (size_t)(g.k > 0 ? g.k : 0);
+  if (g.count.size() != n || g.ids.size() != n * k || g.dist.size() != g.ids.size())
+    throw RPTError(RPT_E_ARG, "graphDelete: the graph must be over the n rows of data");
+  if (!keep.empty() && keep.size() != (n + 31) / 32)
+    throw RPTError(RPT_E_ARG, "graphDelete: keep must hold ceil(n / 32) words (or none)");
+  DeleteResult r;
+  r.graph.k = g.k;
+  r.graph.ids.resize(n * k + 1);
+  r.graph.dist.resize(n * k + 1);
+  r.graph.count.resize(n + 1);
+  r.newid.resize(n + 1);
+  check(rpt_graph_delete_host(ctx.get(), data.get(), g.k, g.ids.data(), g.dist.data(), g.count.data(),
+                              keep.empty() ? nullptr : keep.data(), metric_flags(metric),
+                              compact ? RPT_GRAPH_DELETE_COMPACT : 0, r.graph.ids.data(), r.graph.dist.data(),
+                              r.graph.count.data(), r.newid.data()));
+  r.newid.resize(n);
+  size_t rows = n;
+  if (compact) {
+    rows = 0;
+    for (int32_t v : r.newid) rows += v >= 0;
+  }
+  r.graph.ids.resize(rows * k);
+  r.graph.dist.resize(rows * k);
+  r.graph.count.resize(rows);
+  if (stats)
+    check(rpt_graph_delete_last(ctx.get(), &stats->kept, &stats->touched, &stats->evaluated, &stats->dropped));
+  return r;
+}
+inline DeleteResult graphDelete(Context& ctx, const Dataset& data, const GraphResult& g,
+                                const std::vector<uint32_t>& keep, bool compact = true,
+                                DeleteStats* stats = nullptr) {
+  return graphDelete(ctx, data, g, keep, compact, Metric::L2, stats);
+}
+
 struct BruteResult {
   std::vector<int32_t> ids;  // [nq][k], -1 = unused slot
   std::vector<double> dist;  // [nq][k]

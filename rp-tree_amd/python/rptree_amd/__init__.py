@@ -23,7 +23,7 @@ import numpy as np
 
 from . import gen
 from ._lib import (RPT_BF16, RPT_F32, RPT_F64, RPT_GRAPH_ACCUMULATE, RPT_GRAPH_MAX_K, RPT_GRAPH_SEARCH_MAX_EF,
-                   RPT_GRAPH_SEARCH_MAX_WIDTH, RPT_GRAPH_PREP_DIVERSIFY, RPT_GRAPH_PREP_REVERSE,
+                   RPT_GRAPH_SEARCH_MAX_WIDTH, RPT_GRAPH_DELETE_COMPACT, RPT_GRAPH_PREP_DIVERSIFY, RPT_GRAPH_PREP_REVERSE,
                    RPT_KNN_DEDUP, RPT_KNN_DEDUP_DISTANCE,
                    RPT_KNN_KEEP_DUPLICATES, RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER,
                    RPT_KNN_METRIC_REFERENCE,
@@ -45,6 +45,7 @@ __all__ = [
     "graphSearch", "graphSearchDev", "graphSearchLast", "graphSearchSV", "graphSearchSVDev",
     "graphSearchAllow", "graphSearchAllowDev", "allowBitmap",
     "graphInsert", "graphInsertDev", "graphInsertLast",
+    "graphDelete", "graphDeleteDev", "graphDeleteLast", "compactRows",
     "graphPrepare", "graphPrepareDev", "graphPrepareLast", "graphPrepareSV", "graphPrepareSVDev",
     "graphSearchMetricSV", "graphSearchMetricSVDev", "graphPrepareMetricSV", "graphPrepareMetricSVDev",
     "knnVote", "knnVoteDev", "voteCandidates", "knnVoteLast",
@@ -1401,6 +1402,102 @@ def graphInsertLast(ctx=None):
     ctx = ctx or default_context()
     a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
     check(lib().rpt_graph_insert_last(ctx._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return int(a.value), int(b.value), int(c.value), int(d.value)
+
+
+def compactRows(data, keep):
+    """The kept rows of a host data set, for graphDelete's compact form: data is a 2-D array or a CSR
+    tuple (rowptr, col, val, d), keep a bool array of n (True = the row stays) or the uint32 words of
+    allowBitmap.  Row newid[p] of the result is row p of data."""
+    n = (len(data[0]) - 1) if isinstance(data, tuple) else len(data)
+    k = np.asarray(keep)
+    if k.dtype == np.uint32:
+        k = np.unpackbits(allowBitmap(k, n).view(np.uint8), bitorder="little")[:n].astype(bool)
+    if k.dtype != np.bool_ or k.shape != (n,):
+        raise ValueError("keep must be a bool mask of n = %d or its uint32 words" % n)
+    if not isinstance(data, tuple):
+        return np.ascontiguousarray(np.asarray(data)[k])
+    rowptr = np.asarray(data[0], dtype=np.int64)
+    length = (rowptr[1:] - rowptr[:-1])[k]
+    out = np.zeros(length.size + 1, dtype=np.int64)
+    out[1:] = np.cumsum(length)
+    take = np.repeat(k, rowptr[1:] - rowptr[:-1])
+    return out, np.asarray(data[1])[take], np.asarray(data[2])[take], data[3]
+
+
+def graphDelete(keep, graph, data, compact=True, metric=None, ctx=None):
+    """Rows out of a kNN graph (rpt_graph_delete_host) -> ((ids, dist, count), newid): the deleted rows
+    are dropped and every list that named one is repaired from the deleted row's own neighbours, one
+    hop; nothing is rebuilt.  keep: a bool array of n (True = the row STAYS), the uint32 words of
+    allowBitmap (the tombstone bitmap graphSearchAllow takes, unchanged) or None (every row stays).
+    graph: (ids[n][kg], dist[n][kg], count[n]) over data's n rows (the distances ARE read); data: a 2-D
+    array (float64, float32, or uint16 bf16 patterns), a CSR tuple (rowptr, col, val, d), a dense or CSR
+    Dataset, or a forest over one; metric: None / metricL2, metricCosine or metricInner, the one the
+    graph was built under.  A kept row that named no deleted row is copied; a row that did becomes the
+    first kg by (distance, id) of its kept entries, at their stored distances, and the kept neighbours
+    of its deleted neighbours, at their distance to the row.  compact=True: the survivors are
+    renumbered densely, newid[i] = the number of kept rows below i or -1, the graph has popcount(keep)
+    rows and belongs to compactRows(data, keep).  compact=False: n rows in old ids, deleted rows empty,
+    newid[i] = i or -1; searchable with the unchanged data.  A row whose neighbours and all their
+    neighbours are gone ends short: knnGraphRefine afterwards repairs it.  A pure function of its inputs,
+    bit for bit."""
+    metric_flag = _metric_flag(metric)
+    if not isinstance(data, (Dataset, np.ndarray, tuple)) and hasattr(data, "data"):
+        data = data.data                                  # a forest
+    ctx = ctx or (data.ctx if isinstance(data, Dataset) else default_context())
+    if isinstance(data, np.ndarray) and data.dtype == np.uint16:
+        ds = Dataset.dense(ctx, data, dtype=RPT_BF16)
+    else:
+        ds = Dataset.of(ctx, data)
+    n = ds.n
+    gids = np.ascontiguousarray(graph[0], dtype=np.int32)
+    gdist = np.ascontiguousarray(graph[1], dtype=np.float64)
+    gcnt = np.ascontiguousarray(graph[2], dtype=np.int32)
+    if gids.ndim != 2 or gids.shape[0] != n or gdist.shape != gids.shape or gcnt.shape != (n,):
+        raise ValueError("graph must be (ids[n][kg], dist[n][kg], count[n]) over the data set's n rows")
+    kg = int(gids.shape[1])
+    words = None
+    if keep is not None:
+        k = np.asarray(keep)
+        if k.dtype != np.uint32 and k.dtype != np.bool_:
+            raise ValueError("keep must be a bool mask of n, its uint32 words or None")
+        words = allowBitmap(k, n)
+    ids = np.empty((n, kg), dtype=np.int32)
+    dist = np.empty((n, kg), dtype=np.float64)
+    cnt = np.empty(n, dtype=np.int32)
+    newid = np.empty(n, dtype=np.int32)
+    check(lib().rpt_graph_delete_host(ctx._h, ds._h, kg, _vp(gids), _vp(gdist), _vp(gcnt),
+                                      None if words is None else _vp(words), metric_flag,
+                                      RPT_GRAPH_DELETE_COMPACT if compact else 0, _vp(ids), _vp(dist), _vp(cnt),
+                                      _vp(newid)))
+    rows = int(np.count_nonzero(newid >= 0)) if compact else n
+    return (ids[:rows], dist[:rows], cnt[:rows]), newid
+
+
+def graphDeleteDev(data, kg, gids_ptr, gdist_ptr, gcount_ptr, keep_ptr, oids_ptr, odist_ptr, ocount_ptr,
+                   newid_ptr=0, compact=True, metric=None):
+    """graphDelete on device arrays (rpt_graph_delete_dev): data is the Dataset (or a forest over it),
+    the graph (int32 [n][kg], float64 [n][kg], int32 [n]), keep (ceil(n / 32) uint32 words, 0 = every
+    row stays), the outputs (sized for n rows; with compact only the first popcount rows are written)
+    and newid (int32 [n], 0 = not wanted) device addresses; the outputs overlap no input.  The graph is
+    read only and NOT validated: untouched rows are copied as they are, touched rows come out sorted
+    without their invalid entries.  Enqueued on the ctx stream, not synchronised (ctx.sync() before
+    reading); whatever filled the arrays must have finished (see Dataset.dense_device)."""
+    metric_flag = _metric_flag(metric)
+    ds = _refine_data(data)
+    check(lib().rpt_graph_delete_dev(ds.ctx._h, ds._h, int(kg), C.c_void_p(gids_ptr), C.c_void_p(gdist_ptr),
+                                     C.c_void_p(gcount_ptr), C.c_void_p(keep_ptr), metric_flag,
+                                     RPT_GRAPH_DELETE_COMPACT if compact else 0, C.c_void_p(oids_ptr),
+                                     C.c_void_p(odist_ptr), C.c_void_p(ocount_ptr), C.c_void_p(newid_ptr)))
+
+
+def graphDeleteLast(ctx=None):
+    """(kept, touched, evaluated, dropped) of the last graphDelete call on ctx (rpt_graph_delete_last;
+    synchronises): kept rows, kept rows that named a deleted row, distances evaluated for them, and the
+    valid entries of kept rows that named a deleted row."""
+    ctx = ctx or default_context()
+    a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().rpt_graph_delete_last(ctx._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
     return int(a.value), int(b.value), int(c.value), int(d.value)
 
 

@@ -21,6 +21,7 @@ RPT_GRAPH_MAX_K = 64
 RPT_GRAPH_SEARCH_MAX_EF = 256
 RPT_GRAPH_SEARCH_MAX_WIDTH = 1024
 RPT_GRAPH_PREP_DIVERSIFY = 1
+RPT_GRAPH_DELETE_COMPACT = 1
 RPT_GRAPH_PREP_REVERSE = 2
 RPT_COMM_UID_BYTES = 128
 
@@ -105,6 +106,9 @@ SYMBOLS = {
     "rpt_graph_insert_dev": (i32, [vp, vp, i32, vp, vp, vp, i64, i32, vp, i32, i64, i32, i32, vp, vp, vp]),
     "rpt_graph_insert_host": (i32, [vp, vp, i32, vp, vp, vp, i64, i32, vp, i32, i64, i32, i32, vp, vp, vp]),
     "rpt_graph_insert_last": (i32, [vp, p_i64, p_i64, p_i64, p_i64]),
+    "rpt_graph_delete_dev": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "rpt_graph_delete_host": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "rpt_graph_delete_last": (i32, [vp, p_i64, p_i64, p_i64, p_i64]),
     "rpt_graph_prepare_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_prepare_host": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_graph_prepare_csr_dev": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
