@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchAllowHIP, graphInsertHIP, graphDeleteHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchAllowHIP, graphInsertHIP, graphDeleteHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, knnAllowHIP, bruteKnnAllowHIP, recallWithAllowHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -69,6 +69,9 @@ foreign import ccall safe "rpt_graph_prepare_csr_metric_host" c_graph_prepare_cs
 foreign import ccall safe "rpt_knn_csr_metric_host" c_knn_csr_metric_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_recall_hits_csr_metric_host" c_recall_hits_csr_metric :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_knn_vote_host" c_knn_vote_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_allow_host" c_knn_allow_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_brute_knn_allow_host" c_brute_knn_allow_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> IO Int32
+foreign import ccall safe "rpt_recall_hits_allow_host" c_recall_hits_allow_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
 -- two calls, the first with null outputs returns the total
 foreign import ccall safe "rpt_vote_candidates_host" c_vote_candidates_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Ptr Int64 -> Ptr Int32 -> Ptr Int32 -> Int64 -> Ptr Int64 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
@@ -622,3 +625,50 @@ voteCandidatesHIP ctx f qd nq v = do
     c_vote_candidates_host ctx f qd (fromIntegral v) po a b total pt))) >>= check
   (,,) <$> VS.freeze off <*> (VS.take (fromIntegral total) <$> VS.freeze ids)
        <*> (VS.take (fromIntegral total) <$> VS.freeze cnt)
+
+-- | 'knnHIP' / 'knnMetricHIP' / 'knnMetricSVHIP' among SOME of the points (rpt_knn_allow_host): @allow@ is
+-- the bitmap 'graphSearchAllowHIP' takes, unchanged (ceil(n / 32) words, id i = bit @i .&. 31@ of word
+-- @i `shiftR` 5@; 'Nothing' = every id).  A query's candidate list loses its disallowed entries, order
+-- and duplicates kept, and is ranked by (distance, position) under the duplicate rule @dedup@ (0
+-- duplicates kept, 1 each id once, 2 one entry per distance), which sees allowed entries only.  With
+-- every id allowed the answer is the unfiltered one bit for bit.  @refMetric@ (SVector rows, 'MetricL2'):
+-- the reference's truncating metricSSL2.  @ds@ is the forest's point set, @qd@ the @nq@ queries in the
+-- same layout.  The ids seed 'graphSearchAllowHIP' under the same bitmap (@dedup@ = 1).
+knnAllowHIP :: Metric -> Bool -> Int -> Maybe (VS.Vector Word32) -> Ptr Ctx -> Ptr Forest -> Ptr Dataset
+            -> Ptr Dataset -> Int -> Int -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnAllowHIP m refMetric dedup allow ctx f ds qd nq k = do
+  let flags = fromIntegral dedup + metricFlag m + (if refMetric then 16777216 else 0)   -- RPT_KNN_METRIC_REFERENCE
+      withAllow g = maybe (g nullPtr) (`VS.unsafeWith` g) allow
+  ids <- VSM.new (max 1 (nq * k)); dist <- VSM.new (max 1 (nq * k)); cnt <- VSM.new (max 1 nq)
+  withAllow (\pa -> VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt
+    (c_knn_allow_host ctx f ds qd pa (fromIntegral k) flags a b)))) >>= check
+  (,,) <$> (VS.take (nq * k) <$> VS.freeze ids) <*> (VS.take (nq * k) <$> VS.freeze dist)
+       <*> (VS.take nq <$> VS.freeze cnt)
+
+-- | The exhaustive kNN among the allowed rows (rpt_brute_knn_allow_host): the k best allowed rows by
+-- (distance, id), NaN last, unused slots id -1 and distance +Infinity.
+bruteKnnAllowHIP :: Metric -> Bool -> Maybe (VS.Vector Word32) -> Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int -> Int
+                 -> IO (VS.Vector Int32, VS.Vector Double)
+bruteKnnAllowHIP m refMetric allow ctx ds qd nq k = do
+  let flags = metricFlag m + (if refMetric then 16777216 else 0)
+      withAllow g = maybe (g nullPtr) (`VS.unsafeWith` g) allow
+  ids <- VSM.new (max 1 (nq * k)); dist <- VSM.new (max 1 (nq * k))
+  withAllow (\pa -> VSM.unsafeWith ids (\a -> VSM.unsafeWith dist
+    (c_brute_knn_allow_host ctx ds qd pa (fromIntegral k) flags a))) >>= check
+  (,) <$> (VS.take (nq * k) <$> VS.freeze ids) <*> (VS.take (nq * k) <$> VS.freeze dist)
+
+-- | 'recallWith' (RPTree.hs:259-282) with the truth taken among the allowed rows
+-- (rpt_recall_hits_allow_host): per query the mean over the trees of
+-- |candidates(tree, q) `intersect` the k nearest allowed rows| / k.
+recallWithAllowHIP :: Metric -> Bool -> Maybe (VS.Vector Word32) -> Ptr Ctx -> Ptr Forest -> Ptr Dataset
+                   -> Ptr Dataset -> Int -> Int -> Int -> IO (V.Vector Double)
+recallWithAllowHIP m refMetric allow ctx f ds qd nq ntrees k = do
+  let flags = metricFlag m + (if refMetric then 16777216 else 0)
+      withAllow g = maybe (g nullPtr) (`VS.unsafeWith` g) allow
+  hits <- VSM.new (max 1 (nq * ntrees)); truth <- VSM.new (max 1 (nq * k))
+  withAllow (\pa -> VSM.unsafeWith hits (\a -> VSM.unsafeWith truth
+    (c_recall_hits_allow_host ctx f ds qd pa (fromIntegral k) flags a))) >>= check
+  hs <- VS.freeze hits
+  let rec i = sum [ fromIntegral (hs VS.! (i * ntrees + t)) / fromIntegral k | t <- [0 .. ntrees - 1] ]
+              / fromIntegral ntrees
+  pure (V.generate nq rec)

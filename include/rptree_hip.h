@@ -173,7 +173,10 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *                                  the answer does not depend on it
  *   knn_vote_slice (0 auto, n)     rpt_knn_vote_*: at most n queries per vote-select slice (auto: by a
  *                                  fixed scratch budget); the answer does not depend on it
- *   comm_force_exchange            sharded kNN on a ONE-rank communicator still runs record ->
+ *   knn_allow_slice (0 auto, n)    rpt_knn_allow_* / rpt_allow_candidates_host: at most n queries per
+ *                                  compaction slice (auto: by the same fixed scratch budget); the answer
+ *                                  does not depend on it
+ *   comm_force_exchange           sharded kNN on a ONE-rank communicator still runs record ->
  *                                  ncclAllGather -> merge (set on the communicator's first ctx)
  *   comm_inject_failure            test hook: the device's shard reports a failure (see "Failures"
  *                                  under the multi-GPU entry points)
@@ -187,7 +190,8 @@ int32_t rpt_ctx_get_option(rpt_ctx* ctx, const char* name, int64_t* value);
  * one pass over the whole point set for up to 96 hyperplanes), 1 = split work,
  * 2 = query plan (query projections + traversal), 3 = distance/top-k kernel, 4 = the wide
  * (> 32 hyperplanes per pass) MFMA projection launches alone (they are also part of class 0),
- * 5 = the vote-select kernel of rpt_knn_vote_* / rpt_vote_candidates_host, 6 = the link kernels of
+ * 5 = the candidate-list step: the vote-select kernel of rpt_knn_vote_* / rpt_vote_candidates_host and
+ * the compaction and list kernels of rpt_knn_allow_* / rpt_brute_knn_allow_*, 6 = the link kernels of
  * rpt_graph_insert_* (one launch = the link of one chunk; its searches are class 3), 8 = the mark,
  * scan, copy and repair kernels of rpt_graph_delete_* (one launch = one call).  7 is not a class:
  * rpt_prof_get answers RPT_E_ARG for it.
@@ -1366,6 +1370,77 @@ int32_t rpt_vote_candidates_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset*
                                  int64_t* off_host /*[nq+1], may be NULL*/, int32_t* ids_host,
                                  int32_t* counts_host /*may be NULL*/, int64_t cap, int64_t* total);
 int32_t rpt_knn_last_voted(rpt_ctx* ctx, int64_t* total);
+
+/* ---- an allow-list on the forest query and on the exhaustive kNN ----
+ * `allow` is the bitmap of rpt_graph_search_allow_*, unchanged: ceil(n / 32) uint32 words; id i is bit
+ * i & 31 of word i >> 5; bits at positions >= n are ignored; NULL means every id; one bitmap serves
+ * the batch.
+ * The forest query (rpt_knn_allow_*).  The candidate list of a query is rpt_candidates' list: trees
+ * ascending, leaves left to right, duplicates kept.  The allowed list is that list with every entry
+ * whose id is not allowed removed, in the same order.  The answer is what rpt_knn_* would answer if
+ * the allowed list were the candidate list: the k best by (distance, position in the allowed list)
+ * under the duplicate rule; NaN ranks last; count = min(k, entries the rule leaves); unused slots are
+ * id -1, distance +inf.  The duplicate rule applies after the filter (RPT_KNN_DEDUP_DISTANCE before
+ * the filter could keep a disallowed row and lose the allowed row at the same distance).  The
+ * distances, fold orders, certificates and exact reruns are those of the existing general kernels of
+ * the (row layout, dtype, distance) cell: with every id allowed the answer is rpt_knn_*'s, bit for
+ * bit (ids, distance bits, counts); with any bitmap it equals "rank the whole candidate list, then
+ * drop disallowed entries, then apply the rule and cut to k".
+ * The exhaustive kNN (rpt_brute_knn_allow_*).  The answer is the k best allowed rows by (distance,
+ * id), NaN last, unused slots -1 / +inf.  Distances are rpt_brute_knn_*'s for the cell: in every cell
+ * except true L2 on CSR rows the answer is bit-equal to the brute force over the allowed rows alone
+ * with ids mapped back through the ascending allowed ids; true L2 on CSR rows (flags 0) is the
+ * tolerance-mode distance of rpt_brute_knn_* there (rtol 1e-9, atol 1e-12; a stored row is at exactly
+ * 0 from itself), from the same tiled kernel behind a compile-time allow switch.
+ * Recall (rpt_recall_hits_allow_host): hits[i][t] = the number of ids of truth_i among the candidates of
+ * (tree t, query i), as rpt_recall_hits_host counts them, truth_i being the exhaustive answer among the allowed rows (unused slots -1).
+ * One entry point routes every cell: dense f64 / f32 / bf16 and CSR f64 / f32 rows with queries of
+ * the same layout and dtype; L2 (no metric bit), RPT_KNN_METRIC_COSINE, RPT_KNN_METRIC_INNER, and
+ * RPT_KNN_METRIC_REFERENCE on CSR rows; batch and streamed forests; k in [1, 1024]; any number of
+ * trees and of candidates.  Flags of rpt_knn_allow_*: the duplicate-rule bits (0, RPT_KNN_DEDUP,
+ * RPT_KNN_DEDUP_DISTANCE) or-ed with at most one metric bit.  Refused with RPT_E_ARG, as rpt_knn_*
+ * refuses them: both duplicate bits, RPT_KNN_METRIC_COSINE with _INNER, a metric with
+ * RPT_KNN_METRIC_REFERENCE, unknown bits; also RPT_KNN_METRIC_REFERENCE on dense rows, k outside
+ * [1, 1024], data and queries of different layout or dtype.  A RPT_KNN_VOTE field is
+ * RPT_E_UNSUPPORTED.  rpt_brute_knn_allow_* / rpt_recall_hits_allow_host take a metric bit only (any
+ * other bit: RPT_E_ARG).  An error leaves the context usable.
+ * How: a compaction kernel writes each query's allowed list into a scratch slab (a workgroup per
+ * query, a ballot and a workgroup prefix: stable), and the cell's general kernel ranks it as one
+ * range; the exhaustive kNN ranks one ascending list of the allowed ids (popcount, scan, scatter),
+ * except the true L2 on CSR rows, whose tiled kernel skips the rows whose bit is clear.
+ * Scratch is sized from the query plan against a fixed 1 GiB budget, never from the free memory; a
+ * batch above it is processed in slices of queries (option knn_allow_slice bounds a slice; the answer
+ * does not depend on it).  The _host variants validate before anything is uploaded and upload the
+ * ceil(n / 32) words; the _dev variants take device pointers (allow_dev too) and return synchronised.
+ * rpt_allow_candidates_host: the allowed lists themselves, with rpt_candidates' two-call protocol:
+ * ids_host NULL returns *total (and off_host[nq + 1], if given); the second call fills
+ * ids_host[cap >= total].
+ * rpt_knn_allow_last: the candidate entries and the allowed entries (= distances evaluated) of the
+ * last rpt_knn_allow_* / rpt_allow_candidates_host call, summed over its queries.
+ * rpt_knn_last_uncertified serves these calls; rpt_knn_last_tier / _retries read 0.
+ * Not built: a bitmap per query; the vote route (rpt_knn_vote_*, RPT_KNN_VOTE) under a filter; the
+ * fused kernels under a filter (this route is the general path, as rpt_knn_vote_* is); sharded /
+ * multi-GPU queries; rpt_knnh_host. */
+int32_t rpt_knn_allow_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                           const rpt_dataset* queries, const uint32_t* allow_host, int32_t k, int32_t flags,
+                           int32_t* ids_host, double* dist_host, int32_t* count_host);
+int32_t rpt_knn_allow_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                          const rpt_dataset* queries, const uint32_t* allow_dev, int32_t k, int32_t flags,
+                          int32_t* ids_dev, double* dist_dev, int32_t* count_dev);
+int32_t rpt_allow_candidates_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* queries,
+                                  const uint32_t* allow_host, int64_t* off_host /*[nq+1], may be NULL*/,
+                                  int32_t* ids_host, int64_t cap, int64_t* total);
+int32_t rpt_brute_knn_allow_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                 const uint32_t* allow_host, int32_t k, int32_t flags, int32_t* ids_host,
+                                 double* dist_host);
+int32_t rpt_brute_knn_allow_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* ids_dev,
+                                double* dist_dev);
+int32_t rpt_recall_hits_allow_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                                   const rpt_dataset* queries, const uint32_t* allow_host, int32_t k,
+                                   int32_t flags, int32_t* hits_host /*[nq][T]*/,
+                                   int32_t* truth_ids_host /*[nq][k], may be NULL*/);
+int32_t rpt_knn_allow_last(rpt_ctx* ctx, int64_t* candidates, int64_t* allowed);
 
 #ifdef __cplusplus
 }

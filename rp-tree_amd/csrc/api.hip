@@ -252,6 +252,7 @@ const OptDesc kOptions[] = {
     {"knn_general", &rpt_options::knn_general},
     {"knn_vote_lds", &rpt_options::knn_vote_lds},
     {"knn_vote_slice", &rpt_options::knn_vote_slice},
+    {"knn_allow_slice", &rpt_options::knn_allow_slice},
     {"graph_general", &rpt_options::graph_general},
     {"graph_refine_general", &rpt_options::graph_refine_general},
     {"graph_delete_general", &rpt_options::graph_delete_general},
@@ -2306,6 +2307,171 @@ int32_t rpt_knn_last_voted(rpt_ctx* ctx, int64_t* total) {
   return guarded([&]() -> int32_t {
     RPT_ARG(ctx && total, "NULL argument");
     *total = ctx->last_voted;
+    return RPT_OK;
+  });
+}
+
+}  // extern "C"
+
+// ---- an allow-list on the forest query and on the exhaustive kNN ----------------------------------
+namespace {
+// the metric part of the rpt_*_allow_* flags: 0 or exactly one of RPT_KNN_METRIC_COSINE / _INNER /
+// _REFERENCE, the last on CSR rows only
+int32_t check_allow_metric(const rpt_dataset* data, int32_t flags) {
+  const int32_t metric = flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER);
+  RPT_ARG(metric != (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER),
+          "RPT_KNN_METRIC_COSINE and RPT_KNN_METRIC_INNER are exclusive");
+  RPT_ARG(!metric || !(flags & RPT_KNN_METRIC_REFERENCE),
+          "RPT_KNN_METRIC_REFERENCE is an L2 metric: not with RPT_KNN_METRIC_COSINE / _INNER");
+  RPT_ARG(!(flags & RPT_KNN_METRIC_REFERENCE) || data->csr, "RPT_KNN_METRIC_REFERENCE is the CSR rows' metric");
+  return RPT_OK;
+}
+
+int32_t check_knn_allow(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* queries, int32_t k,
+                        int32_t flags) {
+  RPT_TRY(check_query(ctx, f, queries));
+  RPT_ARG(data && data->ctx == ctx, "bad data handle");
+  RPT_ARG(data->n == f->n && data->d == f->d, "data shape differs from the forest's");
+  RPT_ARG(data->csr == queries->csr, "data and queries must both be dense or both CSR");
+  RPT_ARG(data->dtype == queries->dtype, "data and query dtype must match");
+  RPT_ARG(proj_dtype(queries->dtype) == f->pdtype,
+          "query dtype must have the forest's projection type (f64 vs f32/bf16)");
+  RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
+  RPT_TRY(check_knn_flags(flags));  // rpt_knn_*'s own refusals, with their codes
+  if ((flags >> 8) & 0xffff)
+    return fail(RPT_E_UNSUPPORTED, "rpt_knn_allow_*: no voting (RPT_KNN_VOTE) under an allow-list");
+  return check_allow_metric(data, flags);
+}
+
+int32_t check_brute_allow(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t k,
+                          int32_t flags) {
+  RPT_ARG(ctx && data && queries, "NULL argument");
+  RPT_ARG(data->ctx == ctx && queries->ctx == ctx, "handles belong to another context");
+  RPT_ARG(data->csr == queries->csr, "data and queries must both be dense or both CSR");
+  RPT_ARG(data->d == queries->d && data->dtype == queries->dtype, "shape/dtype mismatch");
+  RPT_ARG(k >= 1 && k <= 1024, "k must be in [1,1024]");
+  RPT_ARG(flags >= 0 && (flags & ~(RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER | RPT_KNN_METRIC_REFERENCE)) == 0,
+          "rpt_brute_knn_allow_*: flags is 0 or one of RPT_KNN_METRIC_COSINE / _INNER / _REFERENCE");
+  RPT_TRY(check_allow_metric(data, flags));
+  RPT_HIP(hipSetDevice(ctx->device));
+  return RPT_OK;
+}
+
+// the ceil(n / 32) words of a host bitmap on the device (null stays null: every id)
+int32_t upload_allow(const uint32_t* allow_host, int64_t n, DevBuf<uint32_t>& bitmap, const uint32_t** allow_dev) {
+  *allow_dev = nullptr;
+  const size_t words = allow_host ? (size_t)((n + 31) / 32) : 0;
+  if (!words) return RPT_OK;
+  RPT_TRY(bitmap.alloc(words));
+  RPT_HIP(hipMemcpy(bitmap.p, allow_host, words * 4, hipMemcpyHostToDevice));
+  *allow_dev = bitmap.p;
+  return RPT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t rpt_knn_allow_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* queries,
+                          const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                          int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_knn_allow(ctx, f, data, queries, k, flags));
+    RPT_ARG(ids_dev && dist_dev && count_dev, "NULL output");
+    return knn_allow_dev(ctx, f, data, queries, allow_dev, k, flags, ids_dev, dist_dev, count_dev);
+  });
+}
+
+int32_t rpt_knn_allow_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* queries,
+                           const uint32_t* allow_host, int32_t k, int32_t flags, int32_t* ids_host,
+                           double* dist_host, int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_knn_allow(ctx, f, data, queries, k, flags));
+    RPT_ARG(ids_host && dist_host && count_host, "NULL output");
+    DevBuf<uint32_t> bitmap;
+    const uint32_t* allow_dev = nullptr;
+    RPT_TRY(upload_allow(allow_host, data->n, bitmap, &allow_dev));
+    Triple out;
+    RPT_TRY(out.alloc(queries->n, k));
+    RPT_TRY(knn_allow_dev(ctx, f, data, queries, allow_dev, k, flags, out.ids.p, out.dist.p, out.cnt.p));
+    RPT_HIP(stream_sync(ctx->stream));
+    return out.download(ids_host, dist_host, count_host);
+  });
+}
+
+int32_t rpt_allow_candidates_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* queries,
+                                  const uint32_t* allow_host, int64_t* off_host, int32_t* ids_host, int64_t cap,
+                                  int64_t* total) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_query(ctx, f, queries));
+    RPT_ARG(total, "total is NULL");
+    DevBuf<uint32_t> bitmap;
+    const uint32_t* allow_dev = nullptr;
+    RPT_TRY(upload_allow(allow_host, f->n, bitmap, &allow_dev));
+    return allow_candidates(ctx, f, queries, allow_dev, off_host, ids_host, cap, total);
+  });
+}
+
+int32_t rpt_brute_knn_allow_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* ids_dev,
+                                double* dist_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ids_dev && dist_dev, "NULL output");
+    RPT_TRY(check_brute_allow(ctx, data, queries, k, flags));
+    return brute_knn_allow_dev(ctx, data, queries, allow_dev, k, flags, ids_dev, dist_dev);
+  });
+}
+
+int32_t rpt_brute_knn_allow_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                 const uint32_t* allow_host, int32_t k, int32_t flags, int32_t* ids_host,
+                                 double* dist_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ids_host && dist_host, "NULL output");
+    RPT_TRY(check_brute_allow(ctx, data, queries, k, flags));
+    const int64_t nq = queries->n;
+    if (nq == 0) return RPT_OK;
+    DevBuf<uint32_t> bitmap;
+    const uint32_t* allow_dev = nullptr;
+    RPT_TRY(upload_allow(allow_host, data->n, bitmap, &allow_dev));
+    DevBuf<int32_t> ids;
+    DevBuf<double> dist;
+    RPT_TRY(ids.alloc((size_t)nq * k));
+    RPT_TRY(dist.alloc((size_t)nq * k));
+    RPT_TRY(brute_knn_allow_dev(ctx, data, queries, allow_dev, k, flags, ids.p, dist.p));
+    RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    return RPT_OK;
+  });
+}
+
+int32_t rpt_recall_hits_allow_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* queries,
+                                   const uint32_t* allow_host, int32_t k, int32_t flags, int32_t* hits_host,
+                                   int32_t* truth_ids_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_query(ctx, f, queries));
+    RPT_ARG(hits_host, "NULL output");
+    RPT_TRY(check_brute_allow(ctx, data, queries, k, flags));
+    RPT_ARG(data->n == f->n && data->d == f->d, "data shape differs from the forest's");
+    RPT_ARG(proj_dtype(queries->dtype) == f->pdtype,
+            "query dtype must have the forest's projection type (f64 vs f32/bf16)");
+    RPT_ARG(queries->n * (int64_t)f->T <= 0x7fffffff, "too many (query, tree) pairs for one call");
+    DevBuf<uint32_t> bitmap;
+    const uint32_t* allow_dev = nullptr;
+    RPT_TRY(upload_allow(allow_host, data->n, bitmap, &allow_dev));
+    return recall_hits_allow(ctx, f, data, queries, allow_dev, k, flags, hits_host, truth_ids_host);
+  });
+}
+
+int32_t rpt_knn_allow_last(rpt_ctx* ctx, int64_t* candidates, int64_t* allowed) {
+  return guarded([&]() -> int32_t {
+    RPT_ARG(ctx && candidates && allowed, "NULL argument");
+    *candidates = ctx->last_candidates;
+    *allowed = ctx->last_allowed;
     return RPT_OK;
   });
 }

@@ -187,6 +187,7 @@ struct rpt_options {
   int64_t knn_vote_lds = 0;     // rpt_knn_vote_*: ids one workgroup sorts in LDS (0 = 16 384, n = min(n, 16 384));
                                 // queries with more candidates sort in a global slab
   int64_t knn_vote_slice = 0;   // rpt_knn_vote_*: at most this many queries per vote-select slice (0 = by the budget)
+  int64_t knn_allow_slice = 0;  // rpt_knn_allow_*: at most this many queries per compaction slice (0 = by the budget)
   int64_t graph_general = 0;    // kNN graph: every leaf on the tiled kernel (64-row blocks), not the one-workgroup leaf kernel
   int64_t graph_refine_general = 0;  // kNN graph refinement: one point per workgroup for every k and reverse
   int64_t graph_delete_general = 0;  // rpt_graph_delete_*: one touched row per workgroup for every kg
@@ -234,6 +235,8 @@ struct rpt_ctx {
   bool metric_unc_pending = false;
   int64_t last_candidates = 0;
   int64_t last_voted = 0;        // voted ids (= distances evaluated) of the last rpt_knn_vote_* / rpt_vote_candidates_host call
+  int64_t last_allowed = 0;      // allowed candidate entries (= distances evaluated) of the last rpt_knn_allow_* /
+                                 // rpt_allow_candidates_host call
   int64_t last_retries = 0;      // queries of the last fused kNN call that took the in-kernel wider second attempt
   int64_t last_graph_pairs = 0;  // distances the last rpt_knn_graph_* call evaluated
   void* refine_state_dev = nullptr;  // graph_refine.hip: the last rpt_knn_graph_refine_* call's flag and counters
@@ -416,6 +419,22 @@ int32_t knn_vote_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const
 // rpt_candidates' protocol for the voted lists; counts_host may be null
 int32_t vote_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, int32_t v, int64_t* off_host,
                         int32_t* ids_host, int32_t* counts_host, int64_t cap, int64_t* total);
+// an allow-list (bitmap on the device, null = every id) over the general kernels (knn.hip, knn_allow.hip):
+// arguments checked by the caller; flags: the duplicate rule or-ed with 0 or one of
+// RPT_KNN_METRIC_COSINE / _INNER / _REFERENCE.  Returns synchronised.
+int32_t knn_allow_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                      const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                      int32_t* count_dev);
+// rpt_candidates' protocol for the allowed lists
+int32_t allow_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, const uint32_t* allow_dev,
+                         int64_t* off_host, int32_t* ids_host, int64_t cap, int64_t* total);
+// exhaustive kNN among the allowed rows; flags: 0 or one of RPT_KNN_METRIC_COSINE / _INNER (any rows) /
+// _REFERENCE (CSR rows).  Returns synchronised.
+int32_t brute_knn_allow_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, const uint32_t* allow_dev,
+                            int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev);
+int32_t recall_hits_allow(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                          const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* hits_host,
+                          int32_t* truth_ids_host);
 int32_t knn_merge_dev(rpt_ctx* ctx, const int32_t* ids_dev, const double* dist_dev,
                       const int32_t* count_dev, int64_t shard_stride, int32_t G, int64_t nq,
                       int32_t k, int32_t flags, int32_t* out_ids, double* out_dist,

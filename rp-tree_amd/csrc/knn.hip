@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "common.h"
+#include "knn_allow.h"
 #include "knn_vote.h"
 
 namespace rpt {
@@ -4802,6 +4803,59 @@ static int32_t knn_general(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
   return RPT_OK;
 }
 
+// ---- what the list routes (rpt_knn_vote_*, rpt_knn_allow_*, rpt_brute_knn_allow_*) share ----
+// queries q0 .. q0 + ns - 1 as a dataset of their own (a view: nothing is owned, no cache is read)
+static rpt_dataset query_view(const rpt_dataset* q, int64_t q0, int64_t ns) {
+  rpt_dataset qv = *q;
+  qv.owns = false;
+  qv.n = ns;
+  if (q->csr) qv.rowptr = q->rowptr + q0;  // (rowptr holds absolute offsets into col / val)
+  else qv.X = static_cast<char*>(q->X) + (size_t)q0 * q->d * dtype_size(q->dtype);
+  return qv;
+}
+
+// The general launcher of the (row layout, dtype, distance) cell over lists made by a list step:
+// `lists` takes perm's place, every query has one range (T := 1).  dedup: the duplicate rule (0 .. 2);
+// metric: 0 or RPT_KNN_METRIC_COSINE / _INNER; refm: CSR rows under the reference's metricSSL2.
+// unc: [q->n] ints of device scratch.  ctx->last_uncertified / metric_unc_pending follow the launch.
+static int32_t launch_lists(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, const int32_t* lists,
+                            const Range* rg, const int64_t* ro, int k, int dedup, int metric, int refm,
+                            int32_t* unc, int32_t* ids, double* dist, int32_t* cnt) {
+  ctx->last_uncertified = 0;
+  ctx->metric_unc_pending = false;
+  if (data->csr && metric) return launch_metric_csr(ctx, data, q, lists, rg, ro, 1, 0, k, dedup, metric, unc, ids, dist, cnt);
+  if (data->csr) {
+    const size_t smem = topk_smem(data->d, 8);
+    ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
+    if (data->dtype == RPT_F64)
+      RPT_HIP(launch_dyn(topk_csr_kernel<double>, dim3((unsigned)q->n), dim3(256), smem, ctx->stream, data->rowptr,
+                         data->col, (const double*)data->val, data->nnz, data->d, q->rowptr, q->col,
+                         (const double*)q->val, lists, rg, ro, 1, k, dedup, refm, ids, dist, cnt));
+    else
+      RPT_HIP(launch_dyn(topk_csr_kernel<float>, dim3((unsigned)q->n), dim3(256), smem, ctx->stream, data->rowptr,
+                         data->col, (const float*)data->val, data->nnz, data->d, q->rowptr, q->col,
+                         (const float*)q->val, lists, rg, ro, 1, k, dedup, refm, ids, dist, cnt));
+    return RPT_OK;
+  }
+  if (metric) return launch_metric(ctx, data, q, lists, rg, ro, 1, 0, k, dedup, metric, unc, ids, dist, cnt);
+  if (data->dtype == RPT_F64) return launch_l2_f64(ctx, data, q, lists, rg, ro, 1, 0, k, dedup, unc, ids, dist, cnt);
+  if (data->dtype == RPT_F32) return launch_topk_dense<float>(ctx, data, q, lists, rg, ro, 1, 0, k, dedup, ids, dist, cnt);
+  return launch_topk_dense<__hip_bfloat16>(ctx, data, q, lists, rg, ro, 1, 0, k, dedup, ids, dist, cnt);
+}
+
+// the launchers count uncertified queries per launch: a sliced call adds its slices up
+static int32_t add_uncertified(rpt_ctx* ctx, int64_t& uncertified) {
+  if (ctx->metric_unc_pending) {
+    unsigned long long n = 0;
+    RPT_HIP(hipMemcpyAsync(&n, ctx->metric_unc_dev, 8, hipMemcpyDeviceToHost, ctx->stream));
+    RPT_HIP(stream_sync(ctx->stream));
+    uncertified += (int64_t)n;
+  } else {
+    uncertified += ctx->last_uncertified;
+  }
+  return RPT_OK;
+}
+
 // ---- the vote threshold over the general kernels (rpt_knn_vote_*, rpt_vote_candidates_host) ----
 // make_plan, then knn_vote.hip's vote-select step turns every query's leaf ranges into ONE range of
 // a scratch id array (the ids at least v trees propose, ascending), then the launcher of the (row
@@ -4925,52 +4979,10 @@ int32_t knn_vote_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const
   for (size_t si = 0; si < w.slices.size(); ++si) {
     const VoteSlice& sl = w.slices[si];
     RPT_TRY(vote_slice_select(ctx, f, w, sl, v, false));
-    // the slice's queries as a dataset of their own (a view: nothing is owned, no cache is read)
-    rpt_dataset qv = *q;
-    qv.owns = false;
-    qv.n = sl.ns;
-    if (q->csr) qv.rowptr = q->rowptr + sl.q0;  // (rowptr holds absolute offsets into col / val)
-    else qv.X = static_cast<char*>(q->X) + (size_t)sl.q0 * q->d * dtype_size(q->dtype);
-    int32_t* ids = ids_dev + sl.q0 * k;
-    double* dist = dist_dev + sl.q0 * k;
-    int32_t* cnt = count_dev + sl.q0;
-    const int32_t* perm = w.ids.p;
-    const Range* rg = w.vranges.p;
-    const int64_t* ro = w.vrng_off.p;
-    ctx->last_uncertified = 0;
-    ctx->metric_unc_pending = false;
-    if (data->csr && metric) {
-      RPT_TRY(launch_metric_csr(ctx, data, &qv, perm, rg, ro, 1, 0, k, 0, metric, unc.p, ids, dist, cnt));
-    } else if (data->csr) {
-      const size_t smem = topk_smem(data->d, 8);
-      ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
-      if (data->dtype == RPT_F64)
-        RPT_HIP(launch_dyn(topk_csr_kernel<double>, dim3((unsigned)qv.n), dim3(256), smem, ctx->stream, data->rowptr,
-                           data->col, (const double*)data->val, data->nnz, data->d, qv.rowptr, qv.col,
-                           (const double*)qv.val, perm, rg, ro, 1, k, 0, refm, ids, dist, cnt));
-      else
-        RPT_HIP(launch_dyn(topk_csr_kernel<float>, dim3((unsigned)qv.n), dim3(256), smem, ctx->stream, data->rowptr,
-                           data->col, (const float*)data->val, data->nnz, data->d, qv.rowptr, qv.col,
-                           (const float*)qv.val, perm, rg, ro, 1, k, 0, refm, ids, dist, cnt));
-    } else if (metric) {
-      RPT_TRY(launch_metric(ctx, data, &qv, perm, rg, ro, 1, 0, k, 0, metric, unc.p, ids, dist, cnt));
-    } else if (data->dtype == RPT_F64) {
-      RPT_TRY(launch_l2_f64(ctx, data, &qv, perm, rg, ro, 1, 0, k, 0, unc.p, ids, dist, cnt));
-    } else if (data->dtype == RPT_F32) {
-      RPT_TRY(launch_topk_dense<float>(ctx, data, &qv, perm, rg, ro, 1, 0, k, 0, ids, dist, cnt));
-    } else {
-      RPT_TRY(launch_topk_dense<__hip_bfloat16>(ctx, data, &qv, perm, rg, ro, 1, 0, k, 0, ids, dist, cnt));
-    }
-    if (w.slices.size() > 1) {  // the launchers count per launch: add the slices up
-      if (ctx->metric_unc_pending) {
-        unsigned long long n = 0;
-        RPT_HIP(hipMemcpyAsync(&n, ctx->metric_unc_dev, 8, hipMemcpyDeviceToHost, ctx->stream));
-        RPT_HIP(stream_sync(ctx->stream));
-        uncertified += (int64_t)n;
-      } else {
-        uncertified += ctx->last_uncertified;
-      }
-    }
+    const rpt_dataset qv = query_view(q, sl.q0, sl.ns);
+    RPT_TRY(launch_lists(ctx, data, &qv, w.ids.p, w.vranges.p, w.vrng_off.p, k, 0, metric, refm, unc.p,
+                         ids_dev + sl.q0 * k, dist_dev + sl.q0 * k, count_dev + sl.q0));
+    if (w.slices.size() > 1) RPT_TRY(add_uncertified(ctx, uncertified));
   }
   if (w.slices.size() > 1) {
     ctx->last_uncertified = uncertified;
@@ -5018,6 +5030,148 @@ int32_t vote_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, int32
   }
   *total = at;
   return vote_read_total(ctx, w);
+}
+
+// ---- an allow-list on the forest query and on the exhaustive kNN (rpt_knn_allow_*, rpt_brute_knn_allow_*) ----
+// The forest query: make_plan, then knn_allow.hip's compaction turns every query's leaf ranges into
+// ONE range of a scratch id slab (the candidate list without the disallowed entries, order and
+// duplicates kept), then launch_lists ranks it with the call's duplicate rule: the rule sees the
+// allowed list only.  A null bitmap takes the same route with every bit read as set.  Scratch: the
+// vote route's fixed budget (kVoteBudgetWords), queries sliced against it or by knn_allow_slice.
+// The exhaustive kNN: the bitmap as ONE ascending id list that every query ranks; position order is
+// id order, so (distance, position) is (distance, id).
+struct AllowWork {
+  QueryPlan pl;
+  std::vector<int64_t> starts;  // [nq + 1] cand_off[q * T] on the host
+  std::vector<AllowSlice> slices;
+  DevBuf<int32_t> ids, counts;
+  DevBuf<Range> vranges;
+  DevBuf<int64_t> vrng_off;
+  DevBuf<unsigned long long> total;
+  int64_t max_ns = 1;
+};
+
+static int32_t allow_prepare(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, AllowWork& w) {
+  RPT_TRY(make_plan(ctx, f, q, w.pl));
+  const int64_t nq = q->n;
+  RPT_TRY(w.total.alloc(1));
+  RPT_HIP(hipMemsetAsync(w.total.p, 0, 8, ctx->stream));
+  if (nq == 0) return RPT_OK;
+  const int64_t max_q = ctx->opt.knn_allow_slice > 0 ? ctx->opt.knn_allow_slice : 0x7fffffff;
+  DevBuf<int64_t> starts_dev;
+  RPT_TRY(starts_dev.alloc((size_t)nq + 1));
+  RPT_TRY(vote_query_starts(ctx, w.pl.cand_off.p, f->T, nq, starts_dev.p));
+  w.starts.resize((size_t)nq + 1);
+  RPT_HIP(hipMemcpyAsync(w.starts.data(), starts_dev.p, (size_t)(nq + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  RPT_HIP(stream_sync(ctx->stream));
+  AllowSlice cur;
+  int64_t max_cand = 1;
+  auto close = [&]() {
+    if (cur.ns == 0) return;
+    w.slices.push_back(cur);
+    max_cand = std::max(max_cand, cur.cand_words);
+    w.max_ns = std::max(w.max_ns, cur.ns);
+  };
+  for (int64_t i = 0; i < nq; ++i) {
+    const int64_t nc = w.starts[i + 1] - w.starts[i];
+    RPT_ARG(nc <= 0x7fffffff, "a query has more candidates than an int32 holds");
+    if (cur.ns > 0 && (cur.ns >= max_q || cur.cand_words + nc > kVoteBudgetWords)) {
+      close();
+      cur = AllowSlice();
+    }
+    if (cur.ns == 0) cur.q0 = i;
+    cur.ns += 1;
+    cur.cand_words += nc;
+  }
+  close();
+  RPT_TRY(w.ids.alloc((size_t)max_cand));
+  RPT_TRY(w.counts.alloc((size_t)w.max_ns));
+  RPT_TRY(w.vranges.alloc((size_t)w.max_ns));
+  RPT_TRY(w.vrng_off.alloc((size_t)w.max_ns + 1));
+  return RPT_OK;
+}
+
+static int32_t allow_slice_compact(rpt_ctx* ctx, rpt_forest* f, AllowWork& w, const AllowSlice& sl,
+                                   const uint32_t* allow_dev) {
+  ProfScope ps(ctx, RPT_PROF_KNN_VOTE);  // class 5: the candidate-list step
+  return allow_compact(ctx, f->perm.p, reinterpret_cast<const VoteRange*>(w.pl.ranges.p), w.pl.rng_off.p,
+                       w.pl.cand_off.p, f->T, sl, allow_dev, w.ids.p, reinterpret_cast<VoteRange*>(w.vranges.p),
+                       w.vrng_off.p, w.counts.p, w.total.p);
+}
+
+static int32_t allow_read_total(rpt_ctx* ctx, AllowWork& w) {
+  unsigned long long t = 0;
+  RPT_HIP(hipMemcpyAsync(&t, w.total.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  RPT_HIP(stream_sync(ctx->stream));
+  ctx->last_allowed = (int64_t)t;
+  return RPT_OK;
+}
+
+int32_t knn_allow_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                      const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                      int32_t* count_dev) {
+  RPT_ARG(k <= kBuf / 2, "k too large for the LDS merge buffer");
+  RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
+  ctx->last_uncertified = 0;
+  ctx->metric_unc_pending = false;
+  ctx->last_retries = 0;
+  ctx->last_tier = 0;
+  ctx->last_allowed = 0;
+  AllowWork w;
+  RPT_TRY(allow_prepare(ctx, f, q, w));
+  ctx->last_candidates = w.pl.total_cand;
+  if (q->n == 0) return RPT_OK;
+  const int metric = flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER);
+  const int refm = (flags & RPT_KNN_METRIC_REFERENCE) ? 1 : 0;
+  DevBuf<int32_t> unc;  // the queries the exact kernels answer again
+  RPT_TRY(unc.alloc((size_t)w.max_ns));
+  int64_t uncertified = 0;
+  for (const AllowSlice& sl : w.slices) {
+    RPT_TRY(allow_slice_compact(ctx, f, w, sl, allow_dev));
+    const rpt_dataset qv = query_view(q, sl.q0, sl.ns);
+    RPT_TRY(launch_lists(ctx, data, &qv, w.ids.p, w.vranges.p, w.vrng_off.p, k, flags & 3, metric, refm, unc.p,
+                         ids_dev + sl.q0 * k, dist_dev + sl.q0 * k, count_dev + sl.q0));
+    if (w.slices.size() > 1) RPT_TRY(add_uncertified(ctx, uncertified));
+  }
+  if (w.slices.size() > 1) {
+    ctx->last_uncertified = uncertified;
+    ctx->metric_unc_pending = false;
+  }
+  return allow_read_total(ctx, w);  // synchronises: the scratch is released on return
+}
+
+int32_t allow_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, const uint32_t* allow_dev,
+                         int64_t* off_host, int32_t* ids_host, int64_t cap, int64_t* total) {
+  const bool fill = ids_host != nullptr;
+  ctx->last_allowed = 0;
+  AllowWork w;
+  RPT_TRY(allow_prepare(ctx, f, q, w));
+  ctx->last_candidates = w.pl.total_cand;
+  std::vector<Range> hr;
+  std::vector<int32_t> hids;
+  int64_t at = 0;
+  if (off_host) off_host[0] = 0;
+  for (const AllowSlice& sl : w.slices) {
+    RPT_TRY(allow_slice_compact(ctx, f, w, sl, allow_dev));
+    hr.resize((size_t)sl.ns);
+    RPT_HIP(hipMemcpyAsync(hr.data(), w.vranges.p, (size_t)sl.ns * sizeof(Range), hipMemcpyDeviceToHost, ctx->stream));
+    if (fill && sl.cand_words > 0) {
+      hids.resize((size_t)sl.cand_words);
+      RPT_HIP(hipMemcpyAsync(hids.data(), w.ids.p, (size_t)sl.cand_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    RPT_HIP(stream_sync(ctx->stream));
+    for (int64_t i = 0; i < sl.ns; ++i) {
+      const Range& r = hr[(size_t)i];
+      if (fill && r.n > 0) {  // (a piece's first r.n words are the list; the rest was never written)
+        RPT_ARG(at + r.n <= cap, "ids capacity too small");
+        std::memcpy(ids_host + at, hids.data() + r.poff, (size_t)r.n * 4);
+      }
+      at += r.n;
+      if (off_host) off_host[sl.q0 + i + 1] = at;
+    }
+  }
+  *total = at;
+  return allow_read_total(ctx, w);
 }
 
 int32_t knn_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
@@ -5323,13 +5477,16 @@ constexpr int kBcGroups = kBcThreads / 16;
 constexpr int kBcRows = kBcGroups * kBcU;            // rows per batch
 static_assert((kBcRows & (kBcRows - 1)) == 0 && kBcThreads % kBcRows == 0, "batch shape");
 
-template <class TD, int QT>
+// ALLOW: only the rows whose bit of `allow` is set are offered (rpt_brute_knn_allow_*); a compile-time
+// switch, off in the unfiltered instantiation, whose code it leaves as it was.
+template <class TD, int QT, bool ALLOW = false>
 __global__ __launch_bounds__(kBcThreads) void brute_csr_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
     const TD* __restrict__ val, int64_t nnz, int64_t n, int d,
     const int64_t* __restrict__ qrowptr, const int32_t* __restrict__ qcol,
     const TD* __restrict__ qval, int64_t nq, int k, int cap, int64_t rows_per_block, int refm,
-    int32_t* __restrict__ out_ids, double* __restrict__ out_dist, int32_t* __restrict__ out_cnt) {
+    int32_t* __restrict__ out_ids, double* __restrict__ out_dist, int32_t* __restrict__ out_cnt,
+    const uint32_t* __restrict__ allow /* ALLOW only: ceil(n / 32) words */) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* qs = reinterpret_cast<double*>(smem);                                   // [d][QT]
   Entry* bufs = reinterpret_cast<Entry*>(smem + (size_t)d * QT * sizeof(double));  // [QT][cap]
@@ -5372,6 +5529,7 @@ __global__ __launch_bounds__(kBcThreads) void brute_csr_kernel(
     __syncthreads();
   }
   auto push = [&](int i, double dist, int row) {
+    if (ALLOW && !((allow[row >> 5] >> (row & 31)) & 1u)) return;
     if (!s_have[i] || (dist == dist && !(dist >= s_thr[i])))
       bufs[i * cap + atomicAdd(&s_fill[i], 1)] = Entry{dist, row, row};
   };
@@ -5528,26 +5686,27 @@ constexpr size_t kBcLds = 150 * 1024;  // the budget the other query kernels kee
 template <class TD, int QT>
 static int32_t launch_brute_csr_t(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k,
                                   int refm, int64_t rows_per_block, int nblk, int32_t* ids,
-                                  double* dist, int32_t* cnt) {
+                                  double* dist, int32_t* cnt, const uint32_t* allow) {
   const size_t smem = brute_csr_smem(data->d, QT, k);
   const int64_t tiles = (q->n + QT - 1) / QT;
-  RPT_HIP(launch_dyn(brute_csr_kernel<TD, QT>, dim3((unsigned)tiles, (unsigned)nblk),
+  RPT_HIP(launch_dyn(allow ? brute_csr_kernel<TD, QT, true> : brute_csr_kernel<TD, QT, false>,
+                     dim3((unsigned)tiles, (unsigned)nblk),
                      dim3(kBcThreads), smem, ctx->stream, data->rowptr, data->col,
                      (const TD*)data->val, data->nnz, data->n, data->d, q->rowptr, q->col,
                      (const TD*)q->val, q->n, k, brute_csr_cap(k), rows_per_block, refm, ids, dist,
-                     cnt));
+                     cnt, allow));
   return RPT_OK;
 }
 
 template <class TD>
 static int32_t launch_brute_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k,
                                 int refm, int qt, int64_t rows_per_block, int nblk, int32_t* ids,
-                                double* dist, int32_t* cnt) {
+                                double* dist, int32_t* cnt, const uint32_t* allow) {
   switch (qt) {
-    case 8: return launch_brute_csr_t<TD, 8>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt);
-    case 4: return launch_brute_csr_t<TD, 4>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt);
-    case 2: return launch_brute_csr_t<TD, 2>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt);
-    default: return launch_brute_csr_t<TD, 1>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt);
+    case 8: return launch_brute_csr_t<TD, 8>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt, allow);
+    case 4: return launch_brute_csr_t<TD, 4>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt, allow);
+    case 2: return launch_brute_csr_t<TD, 2>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt, allow);
+    default: return launch_brute_csr_t<TD, 1>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt, allow);
   }
 }
 
@@ -5569,9 +5728,10 @@ static int brute_csr_tile(const rpt_ctx* ctx, int d, int k, int64_t nq) {
 }
 
 // exhaustive kNN of CSR queries over CSR rows 0 .. n-1, k best by (distance, id), into device
-// arrays [nq][k]; cnt: [nq] ints of device scratch.  Enqueues only.
+// arrays [nq][k]; cnt: [nq] ints of device scratch.  allow: null, or the bitmap of the rows offered.
+// Enqueues only.
 static int32_t brute_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k, int refm,
-                         int32_t* ids_dev, double* dist_dev, int32_t* cnt_dev) {
+                         int32_t* ids_dev, double* dist_dev, int32_t* cnt_dev, const uint32_t* allow = nullptr) {
   RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
   RPT_ARG(data->n <= 0x7fffffff, "too many rows");
   const int64_t nq = q->n, n = data->n;
@@ -5589,8 +5749,8 @@ static int32_t brute_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
   ProfScope ps(ctx, RPT_PROF_KNN_TOPK);
   if (nblk == 1) {
     if (data->dtype == RPT_F64)
-      return launch_brute_csr<double>(ctx, data, q, k, refm, qt, rows, 1, ids_dev, dist_dev, cnt_dev);
-    return launch_brute_csr<float>(ctx, data, q, k, refm, qt, rows, 1, ids_dev, dist_dev, cnt_dev);
+      return launch_brute_csr<double>(ctx, data, q, k, refm, qt, rows, 1, ids_dev, dist_dev, cnt_dev, allow);
+    return launch_brute_csr<float>(ctx, data, q, k, refm, qt, rows, 1, ids_dev, dist_dev, cnt_dev, allow);
   }
   DevBuf<int32_t> pi, pc;
   DevBuf<double> pd;
@@ -5598,9 +5758,9 @@ static int32_t brute_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_datase
   RPT_TRY(pd.alloc((size_t)nblk * nq * k));
   RPT_TRY(pc.alloc((size_t)nblk * nq));
   if (data->dtype == RPT_F64)
-    RPT_TRY(launch_brute_csr<double>(ctx, data, q, k, refm, qt, rows, (int)nblk, pi.p, pd.p, pc.p));
+    RPT_TRY(launch_brute_csr<double>(ctx, data, q, k, refm, qt, rows, (int)nblk, pi.p, pd.p, pc.p, allow));
   else
-    RPT_TRY(launch_brute_csr<float>(ctx, data, q, k, refm, qt, rows, (int)nblk, pi.p, pd.p, pc.p));
+    RPT_TRY(launch_brute_csr<float>(ctx, data, q, k, refm, qt, rows, (int)nblk, pi.p, pd.p, pc.p, allow));
   // (the partial lists are released on return: the allocator hands a block out again only after
   // the stream it was freed on has been synchronised)
   return knn_merge_dev(ctx, pi.p, pd.p, pc.p, 0, (int32_t)nblk, nq, k, 0, ids_dev, dist_dev, cnt_dev);
@@ -6094,6 +6254,70 @@ int32_t recall_hits(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const 
   RPT_HIP(hipMemcpy(hits_host, hits.p, (size_t)nq * f->T * 4, hipMemcpyDeviceToHost));
   if (truth_ids_host)
     RPT_HIP(hipMemcpy(truth_ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+  return RPT_OK;
+}
+
+// The exhaustive kNN among the allowed rows into device arrays [nq][k] (unused slots -1 / +inf);
+// flags: 0, RPT_KNN_METRIC_COSINE / _INNER, or RPT_KNN_METRIC_REFERENCE (CSR rows).  CSR rows under
+// flags 0 (the true L2) stay on the tiled brute_csr_kernel behind its ALLOW switch: its distance is
+// the brute force's own (a stored row at exactly 0 from itself), which the list route's
+// topk_csr_kernel matches only to 1e-8 |q|.  Every other cell ranks the one list.  Enqueues, then
+// synchronises (the list is scratch of this call).
+int32_t brute_knn_allow_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, const uint32_t* allow_dev,
+                            int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev) {
+  RPT_ARG(k <= kBuf / 2, "k too large");
+  RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
+  RPT_ARG(data->n <= 0x7fffffff, "too many rows");
+  ctx->last_uncertified = 0;
+  ctx->metric_unc_pending = false;
+  const int64_t nq = q->n;
+  if (nq == 0) return RPT_OK;
+  DevBuf<int32_t> list, cnt, unc;
+  DevBuf<int64_t> block_off, ro;
+  DevBuf<Range> rg;
+  if (data->csr && flags == 0) {
+    RPT_TRY(cnt.alloc((size_t)nq));
+    RPT_TRY(brute_csr(ctx, data, q, k, 0, ids_dev, dist_dev, cnt.p, allow_dev));
+    RPT_HIP(stream_sync(ctx->stream));
+    return RPT_OK;
+  }
+  RPT_TRY(list.alloc((size_t)std::max<int64_t>(data->n, 1)));
+  RPT_TRY(block_off.alloc((size_t)allow_list_blocks(data->n) + 1));
+  RPT_TRY(rg.alloc((size_t)nq));
+  RPT_TRY(ro.alloc((size_t)nq + 1));
+  RPT_TRY(cnt.alloc((size_t)nq));
+  RPT_TRY(unc.alloc((size_t)nq));
+  {
+    ProfScope ps(ctx, RPT_PROF_KNN_VOTE);  // class 5: the candidate-list step
+    RPT_TRY(allow_list(ctx, allow_dev, data->n, block_off.p, list.p, nq, reinterpret_cast<VoteRange*>(rg.p), ro.p));
+  }
+  RPT_TRY(launch_lists(ctx, data, q, list.p, rg.p, ro.p, k, 0, flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER),
+                       (flags & RPT_KNN_METRIC_REFERENCE) ? 1 : 0, unc.p, ids_dev, dist_dev, cnt.p));
+  RPT_HIP(stream_sync(ctx->stream));
+  return RPT_OK;
+}
+
+// recall_hits with the truth taken among the allowed rows (brute_knn_allow_dev).  The truth holds
+// allowed rows only, so the trees' unfiltered candidates intersect it as the allowed ones would.
+int32_t recall_hits_allow(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
+                          const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* hits_host,
+                          int32_t* truth_ids_host) {
+  const int64_t nq = q->n;
+  if (nq == 0) return RPT_OK;
+  DevBuf<int32_t> ids, hits;
+  DevBuf<double> dist;
+  RPT_TRY(ids.alloc((size_t)nq * k));
+  RPT_TRY(dist.alloc((size_t)nq * k));
+  RPT_TRY(hits.alloc((size_t)nq * f->T));
+  RPT_TRY(brute_knn_allow_dev(ctx, data, q, allow_dev, k, flags, ids.p, dist.p));
+  QueryPlan pl;
+  RPT_TRY(make_plan(ctx, f, q, pl));
+  hipLaunchKernelGGL(recall_hits_kernel, dim3((unsigned)(nq * f->T)), dim3(256), 0, ctx->stream, ids.p, k,
+                     f->perm.p, pl.ranges.p, pl.rng_off.p, f->T, hits.p);
+  RPT_HIP(hipGetLastError());
+  RPT_HIP(stream_sync(ctx->stream));
+  RPT_HIP(hipMemcpy(hits_host, hits.p, (size_t)nq * f->T * 4, hipMemcpyDeviceToHost));
+  if (truth_ids_host) RPT_HIP(hipMemcpy(truth_ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
   return RPT_OK;
 }
 

@@ -996,4 +996,65 @@ inline double recallWith(const RPForest& tts, int k, const SVector& q, bool refe
   return recallWithBatch(tts, k, qs, reference_metric ? RPT_KNN_METRIC_REFERENCE : 0)[0];
 }
 
+// ---- an allow-list on the forest query and on the exhaustive kNN (rpt_knn_allow_host,
+// rpt_allow_candidates_host, rpt_brute_knn_allow_host, rpt_recall_hits_allow_host) ----
+// `allow`: the ceil(n / 32) words of allowBitmap (an empty vector allows every id); one list serves
+// every query.  A query's candidate list loses its disallowed entries, order and duplicates kept, and
+// is ranked as knn ranks it, the duplicate rule (dedup: RPT_KNN_KEEP_DUPLICATES, RPT_KNN_DEDUP,
+// RPT_KNN_DEDUP_DISTANCE) seeing allowed entries only.  Every row layout and Metric; flags may add
+// RPT_KNN_METRIC_REFERENCE on SVector rows under Metric::L2.
+inline const uint32_t* allowWords(const std::vector<uint32_t>& allow, int64_t n, const char* who) {
+  if (!allow.empty() && allow.size() != ((size_t)n + 31) / 32)
+    throw RPTError(RPT_E_ARG, std::string(who) + ": allow must hold ceil(n / 32) words (or none)");
+  return allow.empty() ? nullptr : allow.data();
+}
+inline KnnResult knnAllow(const RPForest& tts, const std::vector<uint32_t>& allow, int k, const Dataset& qs,
+                          int32_t dedup = RPT_KNN_KEEP_DUPLICATES, Metric metric = Metric::L2, int32_t flags = 0) {
+  KnnResult r{k, std::vector<int32_t>((size_t)qs.n * k + 1), std::vector<double>((size_t)qs.n * k + 1),
+              std::vector<int32_t>((size_t)qs.n + 1)};
+  check(rpt_knn_allow_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(),
+                           allowWords(allow, tts.data->n, "knnAllow"), k, dedup | metric_flags(metric) | flags,
+                           r.ids.data(), r.dist.data(), r.count.data()));
+  r.ids.resize((size_t)qs.n * k);
+  r.dist.resize((size_t)qs.n * k);
+  r.count.resize((size_t)qs.n);
+  return r;
+}
+// the allowed lists themselves: list i = ids[off[i] .. off[i + 1])
+inline std::vector<int32_t> allowCandidates(const RPForest& tts, const std::vector<uint32_t>& allow,
+                                            const Dataset& qs, std::vector<int64_t>* off = nullptr) {
+  const uint32_t* w = allowWords(allow, tts.data->n, "allowCandidates");
+  std::vector<int64_t> o((size_t)qs.n + 1);
+  int64_t total = 0;
+  check(rpt_allow_candidates_host(tts.ctx->get(), tts.get(), qs.get(), w, o.data(), nullptr, 0, &total));
+  std::vector<int32_t> ids((size_t)(total > 0 ? total : 1));
+  check(rpt_allow_candidates_host(tts.ctx->get(), tts.get(), qs.get(), w, o.data(), ids.data(), total, &total));
+  ids.resize((size_t)total);
+  if (off) *off = o;
+  return ids;
+}
+// the k best ALLOWED rows by (distance, id); flags: RPT_KNN_METRIC_REFERENCE on SVector rows, or 0
+inline BruteResult bruteKnnAllow(Context& ctx, const Dataset& data, const std::vector<uint32_t>& allow,
+                                 const Dataset& qs, int k, Metric metric = Metric::L2, int32_t flags = 0) {
+  BruteResult r{std::vector<int32_t>((size_t)qs.n * k + 1), std::vector<double>((size_t)qs.n * k + 1)};
+  check(rpt_brute_knn_allow_host(ctx.get(), data.get(), qs.get(), allowWords(allow, data.n, "bruteKnnAllow"), k,
+                                 metric_flags(metric) | flags, r.ids.data(), r.dist.data()));
+  r.ids.resize((size_t)qs.n * k);
+  r.dist.resize((size_t)qs.n * k);
+  return r;
+}
+// recallHits with the truth taken among the allowed rows (bruteKnnAllow's ids)
+inline std::vector<int32_t> recallHitsAllow(const RPForest& tts, const std::vector<uint32_t>& allow, int k,
+                                            const Dataset& qs, Metric metric = Metric::L2, int32_t flags = 0,
+                                            std::vector<int32_t>* truth = nullptr) {
+  std::vector<int32_t> hits((size_t)qs.n * tts.T + 1);
+  if (truth) truth->assign((size_t)qs.n * k + 1, -1);
+  check(rpt_recall_hits_allow_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(),
+                                   allowWords(allow, tts.data->n, "recallHitsAllow"), k, metric_flags(metric) | flags,
+                                   hits.data(), truth ? truth->data() : nullptr));
+  hits.resize((size_t)qs.n * tts.T);
+  if (truth) truth->resize((size_t)qs.n * k);
+  return hits;
+}
+
 }  // namespace rptree

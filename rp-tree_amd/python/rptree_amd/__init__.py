@@ -49,6 +49,8 @@ __all__ = [
     "graphPrepare", "graphPrepareDev", "graphPrepareLast", "graphPrepareSV", "graphPrepareSVDev",
     "graphSearchMetricSV", "graphSearchMetricSVDev", "graphPrepareMetricSV", "graphPrepareMetricSVDev",
     "knnVote", "knnVoteDev", "voteCandidates", "knnVoteLast",
+    "knnAllow", "knnAllowDev", "allowCandidates", "knnAllowLast", "bruteKnnAllow", "bruteKnnAllowDev",
+    "recallHitsAllow", "recallWithAllowBatch",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -902,6 +904,82 @@ def knnVoteLast(ctx=None):
     return int(c.value), int(v.value), int(u.value)
 
 
+def _allow_words(allow, n):
+    """allow as graphSearchAllow takes it -> (the uint32 words or None, their address or None)"""
+    if allow is None:
+        return None, None
+    words = allowBitmap(allow, n)
+    return words, _vp(words)
+
+
+def _dedup_flag(dedup):
+    return (RPT_KNN_DEDUP_DISTANCE if dedup == RPT_KNN_DEDUP_DISTANCE
+            else RPT_KNN_DEDUP if dedup else RPT_KNN_KEEP_DUPLICATES)
+
+
+def knnAllow(allow, k, forest, qs, dedup=False, metric=None, reference_metric=False):
+    """knnBatch among SOME of the points (rpt_knn_allow_host) -> (ids[nq][k], dist[nq][k], count[nq]).
+    allow: a bool array of n (True = allowed), the uint32 words of allowBitmap, or None (every id);
+    one list serves the batch.  A query's candidate list loses its disallowed entries, order and
+    duplicates kept, and is then ranked as knnBatch ranks: by (distance, position) under the duplicate
+    rule (dedup as knnBatch's), which therefore sees allowed entries only; count = min(k, entries
+    left), unused slots are id -1 and distance +inf.  Every row layout (dense f64 / f32 / bf16,
+    SVector f64 / f32), every distance (metric: None / metricL2, metricCosine, metricInner;
+    reference_metric: SVector rows by the reference's truncating metricSSL2), batch and streamed
+    forests, k up to 1024.  With every id allowed the answer is knnBatch's bit for bit.  The seeds of
+    graphSearchAllow under the same list: knnAllow(allow, seed_k, forest, qs, dedup=True, metric=metric)[0]
+    (unused slots are -1 already)."""
+    ctx = forest.ctx
+    flags = _dedup_flag(dedup) | _vote_flags(forest, metric, reference_metric)
+    qd, nq = _query_dataset(ctx, forest.data, qs)
+    words, wp = _allow_words(allow, forest.data.n)
+    ids = np.empty((nq, k), dtype=np.int32)
+    dist = np.empty((nq, k), dtype=np.float64)
+    cnt = np.empty(nq, dtype=np.int32)
+    check(lib().rpt_knn_allow_host(ctx._h, forest._h, forest.data._h, qd._h, wp, int(k), flags, _vp(ids),
+                                   _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnAllowDev(allow_ptr, k, forest, queries, ids_ptr, dist_ptr, count_ptr, dedup=False, metric=None,
+                reference_metric=False):
+    """knnAllow on device arrays (rpt_knn_allow_dev): allow_ptr is the device address of the
+    ceil(n / 32) uint32 words (0 = every id), queries a Dataset, the outputs (int32 [nq][k], float64
+    [nq][k], int32 [nq]) device addresses.  Returns synchronised; whatever filled the queries and the
+    words must have finished (see Dataset.dense_device)."""
+    ctx = forest.ctx
+    flags = _dedup_flag(dedup) | _vote_flags(forest, metric, reference_metric)
+    check(lib().rpt_knn_allow_dev(ctx._h, forest._h, forest.data._h, queries._h, C.c_void_p(allow_ptr), int(k),
+                                  flags, C.c_void_p(ids_ptr), C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
+
+
+def allowCandidates(allow, forest, qs):
+    """-> (off[nq+1], ids): the allowed list of query i = ids[off[i]:off[i+1]], its candidates of all
+    trees (trees ascending, leaves left to right, duplicates kept) without the entries whose id the
+    allow-list excludes (rpt_allow_candidates_host)."""
+    ctx = forest.ctx
+    qd, nq = _query_dataset(ctx, forest.data, qs)
+    words, wp = _allow_words(allow, forest.data.n)
+    total = C.c_int64()
+    off = np.empty(nq + 1, dtype=np.int64)
+    check(lib().rpt_allow_candidates_host(ctx._h, forest._h, qd._h, wp, _vp(off), None, 0, C.byref(total)))
+    ids = np.empty(max(total.value, 1), dtype=np.int32)
+    check(lib().rpt_allow_candidates_host(ctx._h, forest._h, qd._h, wp, _vp(off), _vp(ids), total.value,
+                                          C.byref(total)))
+    return off, ids[:total.value]
+
+
+def knnAllowLast(ctx=None):
+    """(candidates, allowed, uncertified) of the last knnAllow / knnAllowDev / allowCandidates call:
+    the candidate entries of all trees, the allowed ones among them (= distances evaluated), the
+    queries answered again by an exact kernel."""
+    ctx = ctx or default_context()
+    c, a, u = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().rpt_knn_allow_last(ctx._h, C.byref(c), C.byref(a)))
+    check(lib().rpt_knn_last_uncertified(ctx._h, C.byref(u)))
+    return int(c.value), int(a.value), int(u.value)
+
+
 def _graph_flag(accumulate):
     return RPT_GRAPH_ACCUMULATE if accumulate else 0
 
@@ -1724,6 +1802,69 @@ def recallWithBatch(distf, forest, k, qs, reference_metric=False):
     SVector forests, batch and streamed; reference_metric: the truth of SVector data under the
     reference's own metricSSL2."""
     hits, _ = recallHits(distf, forest, k, qs, reference_metric)
+    out = np.empty(hits.shape[0], dtype=np.float64)
+    for i, row in enumerate(hits.tolist()):
+        out[i] = sum(h / k for h in row) / len(row)
+    return out
+
+
+def _brute_allow_flags(data, metric, reference_metric):
+    flags = _metric_flag(metric)
+    if reference_metric:
+        if flags:
+            raise ValueError("reference_metric is an L2 metric: not with metricCosine / metricInner")
+        if not data.is_csr:
+            raise ValueError("reference_metric is the SVector rows' metric")
+        flags |= RPT_KNN_METRIC_REFERENCE
+    return flags
+
+
+def bruteKnnAllow(allow, forest_or_data, qs, k, ctx=None, metric=None, reference_metric=False):
+    """bruteKnn among SOME of the rows (rpt_brute_knn_allow_host) -> (ids[nq][k], dist[nq][k]): the k
+    best allowed rows by (distance, id), NaN last, unused slots id -1 and distance +inf.  allow as
+    knnAllow's.  Every row layout and distance; the answer is bruteKnn's over compactRows(data, allow)
+    with the ids mapped back, bit for bit; the true Euclidean distance on SVector rows is bruteKnn's
+    tolerance-mode distance (rtol 1e-9, atol 1e-12), from the same tiled kernel."""
+    data = forest_or_data.data if isinstance(forest_or_data, RPForest) else forest_or_data
+    ctx = ctx or data.ctx
+    qd, nq = _query_dataset(ctx, data, qs)
+    words, wp = _allow_words(allow, data.n)
+    ids = np.empty((nq, k), dtype=np.int32)
+    dist = np.empty((nq, k), dtype=np.float64)
+    check(lib().rpt_brute_knn_allow_host(ctx._h, data._h, qd._h, wp, int(k),
+                                         _brute_allow_flags(data, metric, reference_metric), _vp(ids), _vp(dist)))
+    return ids, dist
+
+
+def bruteKnnAllowDev(allow_ptr, data, queries, k, ids_ptr, dist_ptr, metric=None, reference_metric=False):
+    """bruteKnnAllow on device arrays (rpt_brute_knn_allow_dev): allow_ptr the device address of the
+    ceil(n / 32) uint32 words (0 = every id), data and queries Datasets, the outputs (int32 [nq][k],
+    float64 [nq][k]) device addresses.  Returns synchronised."""
+    check(lib().rpt_brute_knn_allow_dev(data.ctx._h, data._h, queries._h, C.c_void_p(allow_ptr), int(k),
+                                        _brute_allow_flags(data, metric, reference_metric),
+                                        C.c_void_p(ids_ptr), C.c_void_p(dist_ptr)))
+
+
+def recallHitsAllow(allow, distf, forest, k, qs, reference_metric=False):
+    """recallHits with the truth taken among the allowed rows (rpt_recall_hits_allow_host) ->
+    (hits[nq][T], truth[nq][k]): truth = bruteKnnAllow's ids (unused slots -1), hits[i][t] =
+    |candidates(tree t, query i) ∩ truth_i|.  The truth holds allowed rows only, so the trees'
+    candidates need no filter."""
+    ctx = forest.ctx
+    qd, nq = _query_dataset(ctx, forest.data, qs)
+    words, wp = _allow_words(allow, forest.data.n)
+    hits = np.empty((nq, forest.T), dtype=np.int32)
+    truth = np.empty((nq, k), dtype=np.int32)
+    check(lib().rpt_recall_hits_allow_host(ctx._h, forest._h, forest.data._h, qd._h, wp, int(k),
+                                           _brute_allow_flags(forest.data, distf, reference_metric), _vp(hits),
+                                           _vp(truth)))
+    return hits, truth
+
+
+def recallWithAllowBatch(allow, distf, forest, k, qs, reference_metric=False):
+    """recallWithBatch among the allowed rows -> recall[nq]: per query the mean over trees of
+    |candidates(tree, q) ∩ the k nearest allowed rows| / k, summed in tree order."""
+    hits, _ = recallHitsAllow(allow, distf, forest, k, qs, reference_metric)
     out = np.empty(hits.shape[0], dtype=np.float64)
     for i, row in enumerate(hits.tolist()):
         out[i] = sum(h / k for h in row) / len(row)

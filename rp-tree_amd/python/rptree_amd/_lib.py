@@ -144,6 +144,13 @@ SYMBOLS = {
     "rpt_knn_vote_dev": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "rpt_vote_candidates_host": (i32, [vp, vp, vp, i32, vp, vp, vp, i64, p_i64]),
     "rpt_knn_last_voted": (i32, [vp, p_i64]),
+    "rpt_knn_allow_host": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "rpt_knn_allow_dev": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "rpt_allow_candidates_host": (i32, [vp, vp, vp, vp, vp, vp, i64, p_i64]),
+    "rpt_brute_knn_allow_host": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
+    "rpt_brute_knn_allow_dev": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
+    "rpt_recall_hits_allow_host": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "rpt_knn_allow_last": (i32, [vp, p_i64, p_i64]),
 }
 
 
