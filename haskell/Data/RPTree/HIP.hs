@@ -7,7 +7,7 @@
 -- mirrors of exactly this call sequence are rp-tree_amd/python/rptree_amd/__init__.py and
 -- rp-tree_amd/host/rptree.hpp.
 module Data.RPTree.HIP (forestBatchHIP, forestBatchHIPWith, forestHIP, withDeviceData, withDeviceForest,
-                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchAllowHIP, graphInsertHIP, graphDeleteHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, knnAllowHIP, bruteKnnAllowHIP, recallWithAllowHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
+                        withDeviceForestOn, knnHIP, knnMetricHIP, knnGraphHIP, knnGraphRefineHIP, knnGraphMetricHIP, knnGraphRefineMetricHIP, knnGraphSVHIP, knnGraphRefineSVHIP, knnGraphMetricSVHIP, knnGraphRefineMetricSVHIP, graphSearchHIP, graphSearchAllowHIP, graphInsertHIP, graphDeleteHIP, graphSearchSVHIP, graphPrepareHIP, graphPrepareSVHIP, graphSearchMetricSVHIP, graphPrepareMetricSVHIP, recallWithHIP, knnMetricSVHIP, recallWithMetricSVHIP, knnVoteHIP, voteCandidatesHIP, knnAllowHIP, bruteKnnAllowHIP, recallWithAllowHIP, graphSearchAllowGroupHIP, graphSearchAllowGroupDevHIP, knnAllowGroupHIP, knnAllowGroupDevHIP, allowGroupCandidatesHIP, bruteKnnAllowGroupHIP, bruteKnnAllowGroupDevHIP, recallWithAllowGroupHIP, withDeviceDataSV, Metric(..), ProjMode(..), FlatForest(..),
                         DeviceForest(..), DeviceData(..)) where
 
 import Control.Exception (Exception, bracket, throwIO)
@@ -72,6 +72,15 @@ foreign import ccall safe "rpt_knn_vote_host" c_knn_vote_host :: Ptr Ctx -> Ptr 
 foreign import ccall safe "rpt_knn_allow_host" c_knn_allow_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
 foreign import ccall safe "rpt_brute_knn_allow_host" c_brute_knn_allow_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> IO Int32
 foreign import ccall safe "rpt_recall_hits_allow_host" c_recall_hits_allow_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
+-- the grouped allow-list: (allow, G, group) where allow stands above
+foreign import ccall safe "rpt_graph_search_allow_group_host" c_graph_search_allow_group_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Ptr Word32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_graph_search_allow_group_dev" c_graph_search_allow_group_dev :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Int32 -> Ptr Int32 -> Ptr Int32 -> Int32 -> Ptr Int32 -> Ptr Word32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_allow_group_host" c_knn_allow_group_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_knn_allow_group_dev" c_knn_allow_group_dev :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO Int32
+foreign import ccall safe "rpt_allow_group_candidates_host" c_allow_group_candidates_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Word32 -> Int32 -> Ptr Int32 -> Ptr Int64 -> Ptr Int32 -> Int64 -> Ptr Int64 -> IO Int32
+foreign import ccall safe "rpt_brute_knn_allow_group_host" c_brute_knn_allow_group_host :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> IO Int32
+foreign import ccall safe "rpt_brute_knn_allow_group_dev" c_brute_knn_allow_group_dev :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Double -> IO Int32
+foreign import ccall safe "rpt_recall_hits_allow_group_host" c_recall_hits_allow_group_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Ptr Dataset -> Ptr Word32 -> Int32 -> Ptr Int32 -> Int32 -> Int32 -> Ptr Int32 -> Ptr Int32 -> IO Int32
 -- two calls, the first with null outputs returns the total
 foreign import ccall safe "rpt_vote_candidates_host" c_vote_candidates_host :: Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int32 -> Ptr Int64 -> Ptr Int32 -> Ptr Int32 -> Int64 -> Ptr Int64 -> IO Int32
 foreign import ccall unsafe "rpt_last_error"        c_last_error     :: IO CString
@@ -668,6 +677,100 @@ recallWithAllowHIP m refMetric allow ctx f ds qd nq ntrees k = do
   hits <- VSM.new (max 1 (nq * ntrees)); truth <- VSM.new (max 1 (nq * k))
   withAllow (\pa -> VSM.unsafeWith hits (\a -> VSM.unsafeWith truth
     (c_recall_hits_allow_host ctx f ds qd pa (fromIntegral k) flags a))) >>= check
+  hs <- VS.freeze hits
+  let rec i = sum [ fromIntegral (hs VS.! (i * ntrees + t)) / fromIntegral k | t <- [0 .. ntrees - 1] ]
+              / fromIntegral ntrees
+  pure (V.generate nq rec)
+
+-- ---- allow-lists per query group (rpt_*_allow_group_*) ----
+-- A grouped allow-list is @(allow, g, group)@: @allow@ holds @g@ bitmaps of ceil(n \/ 32) words each, one
+-- after the other (row stride ceil(n \/ 32)); @group@ holds one entry per query, query q being answered
+-- under bitmap @group ! q@, -1 = every id.  The answer of query q is the single-bitmap function's for that
+-- query under its bitmap, bit for bit.  The host variants refuse a group entry outside [-1, g).
+
+-- | the two arrays of a grouped allow-list as pointers (an empty @allow@ is the null pointer)
+withGroups :: VS.Vector Word32 -> VS.Vector Int32 -> (Ptr Word32 -> Ptr Int32 -> IO a) -> IO a
+withGroups allow group f
+  | VS.null allow = VS.unsafeWith group (f nullPtr)
+  | otherwise = VS.unsafeWith allow (\pa -> VS.unsafeWith group (f pa))
+
+-- | 'graphSearchAllowHIP' with a bitmap per query group (rpt_graph_search_allow_group_host).
+graphSearchAllowGroupHIP :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Metric -> Int -> Int
+                         -> (VS.Vector Int32, VS.Vector Int32) -> Int -> VS.Vector Int32
+                         -> VS.Vector Word32 -> Int -> VS.Vector Int32
+                         -> Int -> Int -> Int -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+graphSearchAllowGroupHIP ctx ds qs m nq kg (gids, gcount) s seeds allow g group k ef width = do
+  ids <- VSM.new (nq * k); dist <- VSM.new (nq * k); cnt <- VSM.new nq
+  VS.unsafeWith gids (\pg -> VS.unsafeWith gcount (\pc -> VS.unsafeWith seeds (\ps -> withGroups allow group (\pa pgr ->
+    VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt (
+      c_graph_search_allow_group_host ctx ds qs (fromIntegral kg) pg pc (fromIntegral s) ps pa (fromIntegral g) pgr (fromIntegral k) (fromIntegral ef) (fromIntegral width) (metricFlag m) 0 a b))))))) >>= check
+  (,,) <$> VS.freeze ids <*> VS.freeze dist <*> VS.freeze cnt
+
+-- | The same on device arrays (rpt_graph_search_allow_group_dev): every pointer is device memory, nothing
+-- is validated (a group entry outside [-1, g) means no id is allowed), the call is enqueued only.
+graphSearchAllowGroupDevHIP :: Ptr Ctx -> Ptr Dataset -> Ptr Dataset -> Metric -> Int -> Ptr Int32 -> Ptr Int32 -> Int
+                            -> Ptr Int32 -> Ptr Word32 -> Int -> Ptr Int32 -> Int -> Int -> Int
+                            -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO ()
+graphSearchAllowGroupDevHIP ctx ds qs m kg pg pc s ps pa g pgr k ef width a b c =
+  c_graph_search_allow_group_dev ctx ds qs (fromIntegral kg) pg pc (fromIntegral s) ps pa (fromIntegral g) pgr (fromIntegral k) (fromIntegral ef) (fromIntegral width) (metricFlag m) 0 a b c >>= check
+
+-- | 'knnAllowHIP' with a bitmap per query group (rpt_knn_allow_group_host).
+knnAllowGroupHIP :: Metric -> Bool -> Int -> VS.Vector Word32 -> Int -> VS.Vector Int32 -> Ptr Ctx -> Ptr Forest
+                 -> Ptr Dataset -> Ptr Dataset -> Int -> Int -> IO (VS.Vector Int32, VS.Vector Double, VS.Vector Int32)
+knnAllowGroupHIP m refMetric dedup allow g group ctx f ds qd nq k = do
+  let flags = fromIntegral dedup + metricFlag m + (if refMetric then 16777216 else 0)   -- RPT_KNN_METRIC_REFERENCE
+  ids <- VSM.new (max 1 (nq * k)); dist <- VSM.new (max 1 (nq * k)); cnt <- VSM.new (max 1 nq)
+  withGroups allow group (\pa pgr -> VSM.unsafeWith ids (\a -> VSM.unsafeWith dist (\b -> VSM.unsafeWith cnt
+    (c_knn_allow_group_host ctx f ds qd pa (fromIntegral g) pgr (fromIntegral k) flags a b)))) >>= check
+  (,,) <$> (VS.take (nq * k) <$> VS.freeze ids) <*> (VS.take (nq * k) <$> VS.freeze dist)
+       <*> (VS.take nq <$> VS.freeze cnt)
+
+-- | The same on device arrays (rpt_knn_allow_group_dev); returns synchronised.
+knnAllowGroupDevHIP :: Metric -> Bool -> Int -> Ptr Word32 -> Int -> Ptr Int32 -> Ptr Ctx -> Ptr Forest -> Ptr Dataset
+                    -> Ptr Dataset -> Int -> Ptr Int32 -> Ptr Double -> Ptr Int32 -> IO ()
+knnAllowGroupDevHIP m refMetric dedup pa g pgr ctx f ds qd k a b c =
+  c_knn_allow_group_dev ctx f ds qd pa (fromIntegral g) pgr (fromIntegral k)
+    (fromIntegral dedup + metricFlag m + (if refMetric then 16777216 else 0)) a b c >>= check
+
+-- | The allowed lists themselves, every query under its own bitmap (rpt_allow_group_candidates_host):
+-- (off[nq+1], ids).
+allowGroupCandidatesHIP :: VS.Vector Word32 -> Int -> VS.Vector Int32 -> Ptr Ctx -> Ptr Forest -> Ptr Dataset -> Int
+                        -> IO (VS.Vector Int64, VS.Vector Int32)
+allowGroupCandidatesHIP allow g group _ctx f qd nq = do
+  off <- VSM.new (nq + 1)
+  total <- withGroups allow group (\pa pgr -> VSM.unsafeWith off (\po -> alloca (\pt -> do
+    c_allow_group_candidates_host _ctx f qd pa (fromIntegral g) pgr po nullPtr 0 pt >>= check
+    peek pt)))
+  ids <- VSM.new (max 1 (fromIntegral total))
+  withGroups allow group (\pa pgr -> VSM.unsafeWith off (\po -> VSM.unsafeWith ids (\pi -> alloca (\pt ->
+    c_allow_group_candidates_host _ctx f qd pa (fromIntegral g) pgr po pi total pt)))) >>= check
+  (,) <$> VS.freeze off <*> (VS.take (fromIntegral total) <$> VS.freeze ids)
+
+-- | 'bruteKnnAllowHIP' with a bitmap per query group (rpt_brute_knn_allow_group_host).
+bruteKnnAllowGroupHIP :: Metric -> Bool -> VS.Vector Word32 -> Int -> VS.Vector Int32 -> Ptr Ctx -> Ptr Dataset
+                      -> Ptr Dataset -> Int -> Int -> IO (VS.Vector Int32, VS.Vector Double)
+bruteKnnAllowGroupHIP m refMetric allow g group ctx ds qd nq k = do
+  let flags = metricFlag m + (if refMetric then 16777216 else 0)
+  ids <- VSM.new (max 1 (nq * k)); dist <- VSM.new (max 1 (nq * k))
+  withGroups allow group (\pa pgr -> VSM.unsafeWith ids (\a -> VSM.unsafeWith dist
+    (c_brute_knn_allow_group_host ctx ds qd pa (fromIntegral g) pgr (fromIntegral k) flags a))) >>= check
+  (,) <$> (VS.take (nq * k) <$> VS.freeze ids) <*> (VS.take (nq * k) <$> VS.freeze dist)
+
+-- | The same on device arrays (rpt_brute_knn_allow_group_dev); returns synchronised.
+bruteKnnAllowGroupDevHIP :: Metric -> Bool -> Ptr Word32 -> Int -> Ptr Int32 -> Ptr Ctx -> Ptr Dataset -> Ptr Dataset
+                         -> Int -> Ptr Int32 -> Ptr Double -> IO ()
+bruteKnnAllowGroupDevHIP m refMetric pa g pgr ctx ds qd k a b =
+  c_brute_knn_allow_group_dev ctx ds qd pa (fromIntegral g) pgr (fromIntegral k)
+    (metricFlag m + (if refMetric then 16777216 else 0)) a b >>= check
+
+-- | 'recallWithAllowHIP' with a bitmap per query group (rpt_recall_hits_allow_group_host).
+recallWithAllowGroupHIP :: Metric -> Bool -> VS.Vector Word32 -> Int -> VS.Vector Int32 -> Ptr Ctx -> Ptr Forest
+                        -> Ptr Dataset -> Ptr Dataset -> Int -> Int -> Int -> IO (V.Vector Double)
+recallWithAllowGroupHIP m refMetric allow g group ctx f ds qd nq ntrees k = do
+  let flags = metricFlag m + (if refMetric then 16777216 else 0)
+  hits <- VSM.new (max 1 (nq * ntrees)); truth <- VSM.new (max 1 (nq * k))
+  withGroups allow group (\pa pgr -> VSM.unsafeWith hits (\a -> VSM.unsafeWith truth
+    (c_recall_hits_allow_group_host ctx f ds qd pa (fromIntegral g) pgr (fromIntegral k) flags a))) >>= check
   hs <- VS.freeze hits
   let rec i = sum [ fromIntegral (hs VS.! (i * ntrees + t)) / fromIntegral k | t <- [0 .. ntrees - 1] ]
               / fromIntegral ntrees

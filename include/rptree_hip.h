@@ -173,6 +173,7 @@ int32_t rpt_ctx_stream(rpt_ctx* ctx, void** hip_stream);
  *                                  the answer does not depend on it
  *   knn_vote_slice (0 auto, n)     rpt_knn_vote_*: at most n queries per vote-select slice (auto: by a
  *                                  fixed scratch budget); the answer does not depend on it
+ *   knn_allow_group_budget (0 auto, n)  rpt_brute_knn_allow_group_*: at most n ids of group lists per pass
  *   knn_allow_slice (0 auto, n)    rpt_knn_allow_* / rpt_allow_candidates_host: at most n queries per
  *                                  compaction slice (auto: by the same fixed scratch budget); the answer
  *                                  does not depend on it
@@ -1418,7 +1419,8 @@ int32_t rpt_knn_last_voted(rpt_ctx* ctx, int64_t* total);
  * rpt_knn_allow_last: the candidate entries and the allowed entries (= distances evaluated) of the
  * last rpt_knn_allow_* / rpt_allow_candidates_host call, summed over its queries.
  * rpt_knn_last_uncertified serves these calls; rpt_knn_last_tier / _retries read 0.
- * Not built: a bitmap per query; the vote route (rpt_knn_vote_*, RPT_KNN_VOTE) under a filter; the
+ * Not built: a bitmap per query in THESE entry points (a bitmap per query or per tenant is the
+ * rpt_*_allow_group_* entry points below); the vote route (rpt_knn_vote_*, RPT_KNN_VOTE) under a filter; the
  * fused kernels under a filter (this route is the general path, as rpt_knn_vote_* is); sharded /
  * multi-GPU queries; rpt_knnh_host. */
 int32_t rpt_knn_allow_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
@@ -1441,6 +1443,75 @@ int32_t rpt_recall_hits_allow_host(rpt_ctx* ctx, rpt_forest* f, const rpt_datase
                                    int32_t flags, int32_t* hits_host /*[nq][T]*/,
                                    int32_t* truth_ids_host /*[nq][k], may be NULL*/);
 int32_t rpt_knn_allow_last(rpt_ctx* ctx, int64_t* candidates, int64_t* allowed);
+
+/* ---- allow-lists per query group: many tenants in one batch ----
+ * Every rpt_*_allow_* entry point above takes ONE bitmap for the whole batch.  The rpt_*_allow_group_*
+ * entry points take a GROUPED allow-list where `allow` stands there, three arguments:
+ *   allow   G bitmaps of words = ceil(n / 32) uint32 each, row g at allow + g * words (the row stride
+ *           is `words`, not n / 32).  The bit layout is the one above; bits at or behind n are ignored
+ *           in every row.  May be NULL only when G == 0.
+ *   G       >= 0.
+ *   group   [nq] int32: query q searches under bitmap group[q]; -1 = every id is allowed (the null
+ *           bitmap above).  NULL = every query is -1.
+ * G tenants with many queries each, a bitmap per query (G = nq, group = 0 .. nq - 1) and a mix with
+ * unfiltered queries are all this one shape.
+ * Definition: the answer for query q is the answer of the single-bitmap entry point for that query
+ * under bitmap allow[group[q]] (the null bitmap for -1), bit for bit: ids, distance bits, counts, the
+ * padding -1 / +inf, in every cell those entry points serve (row layouts, dtypes, distances, the CSR
+ * reference metric, batch and streamed forests, the duplicate rules, every k, ef and width).  The call
+ * statistics (rpt_graph_search_last, rpt_knn_allow_last, rpt_knn_last_uncertified) are the sums over
+ * the queries of what the per-bitmap calls report; `evaluated` under the lossy visited filter keeps
+ * its bounds and is equal under graph_search_nofilter = 1.
+ * Errors: every refusal of the single-bitmap entry point, with its code; G < 0, a NULL allow with
+ * G > 0: RPT_E_ARG.  The _host variants also check group[q] in [-1, G) before anything is uploaded
+ * (RPT_E_ARG), then upload G * words words and nq group entries.  The _dev variants borrow device
+ * pointers and do not validate; they stay in bounds whatever group holds: a value outside [-1, G) is
+ * DEFINED as "no id allowed" (count 0, padding only).  An error leaves the context usable.
+ * How: every wave of the graph search, every workgroup of the compaction kernel and every tile query
+ * of the CSR true-L2 kernel resolves its own bitmap row once.  The exhaustive kNN builds one ascending
+ * id list per group that a query names (popcount, scan and scatter over a second grid dimension; a
+ * group nobody names costs nothing), concatenated, and query q ranks the range of its group's list.
+ * The lists are sized from their popcounts against the fixed 1 GiB budget; lists that do not fit
+ * together are built and ranked in passes (option knn_allow_group_budget = ids per pass, for tests;
+ * the answer does not depend on it).  Slicing of the forest query stays by queries (knn_allow_slice);
+ * a slice may hold any mix of groups.
+ * Not built: the vote route under a filter, the fused kernels under a filter, sharded queries,
+ * rpt_knnh_host, a frontier beyond RPT_GRAPH_SEARCH_MAX_WIDTH. */
+int32_t rpt_graph_search_allow_group_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                         int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev,
+                                         int32_t s, const int32_t* seeds_dev, const uint32_t* allow_dev,
+                                         int32_t G, const int32_t* group_dev, int32_t k, int32_t ef,
+                                         int32_t width, int32_t metric, int32_t flags, int32_t* ids_dev,
+                                         double* dist_dev, int32_t* count_dev);
+int32_t rpt_graph_search_allow_group_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                          int32_t kg, const int32_t* gids_host, const int32_t* gcount_host,
+                                          int32_t s, const int32_t* seeds_host, const uint32_t* allow_host,
+                                          int32_t G, const int32_t* group_host, int32_t k, int32_t ef,
+                                          int32_t width, int32_t metric, int32_t flags, int32_t* ids_host,
+                                          double* dist_host, int32_t* count_host);
+int32_t rpt_knn_allow_group_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                                 const rpt_dataset* queries, const uint32_t* allow_host, int32_t G,
+                                 const int32_t* group_host, int32_t k, int32_t flags, int32_t* ids_host,
+                                 double* dist_host, int32_t* count_host);
+int32_t rpt_knn_allow_group_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                                const rpt_dataset* queries, const uint32_t* allow_dev, int32_t G,
+                                const int32_t* group_dev, int32_t k, int32_t flags, int32_t* ids_dev,
+                                double* dist_dev, int32_t* count_dev);
+int32_t rpt_allow_group_candidates_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* queries,
+                                        const uint32_t* allow_host, int32_t G, const int32_t* group_host,
+                                        int64_t* off_host /*[nq+1], may be NULL*/, int32_t* ids_host,
+                                        int64_t cap, int64_t* total);
+int32_t rpt_brute_knn_allow_group_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                       const uint32_t* allow_host, int32_t G, const int32_t* group_host,
+                                       int32_t k, int32_t flags, int32_t* ids_host, double* dist_host);
+int32_t rpt_brute_knn_allow_group_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                      const uint32_t* allow_dev, int32_t G, const int32_t* group_dev,
+                                      int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev);
+int32_t rpt_recall_hits_allow_group_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                                         const rpt_dataset* queries, const uint32_t* allow_host, int32_t G,
+                                         const int32_t* group_host, int32_t k, int32_t flags,
+                                         int32_t* hits_host /*[nq][T]*/,
+                                         int32_t* truth_ids_host /*[nq][k], may be NULL*/);
 
 #ifdef __cplusplus
 }

@@ -253,6 +253,7 @@ const OptDesc kOptions[] = {
     {"knn_vote_lds", &rpt_options::knn_vote_lds},
     {"knn_vote_slice", &rpt_options::knn_vote_slice},
     {"knn_allow_slice", &rpt_options::knn_allow_slice},
+    {"knn_allow_group_budget", &rpt_options::knn_allow_group_budget},
     {"graph_general", &rpt_options::graph_general},
     {"graph_refine_general", &rpt_options::graph_refine_general},
     {"graph_delete_general", &rpt_options::graph_delete_general},
@@ -1469,6 +1470,56 @@ int32_t rpt_knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* update
   });
 }
 
+// ---- the (allow, G, group) of the rpt_*_allow_group_* entry points ------------------------------
+extern "C++" {
+namespace {
+// the single bitmap of the rpt_*_allow_* entry points (null: every id)
+AllowGroups one_bitmap(const uint32_t* allow_dev) {
+  AllowGroups a;
+  a.bits = allow_dev;
+  return a;
+}
+
+int32_t check_group_args(const uint32_t* allow, int32_t G) {
+  RPT_ARG(G >= 0, "G (the number of bitmaps) must not be negative");
+  RPT_ARG(allow || G == 0, "allow is NULL with G > 0");
+  return RPT_OK;
+}
+
+// device arrays as they are: a null group is every query unfiltered, whatever allow holds
+AllowGroups groups_dev(const uint32_t* allow_dev, int32_t G, const int32_t* group_dev, int64_t n) {
+  AllowGroups a;
+  if (!group_dev) return a;
+  a.bits = allow_dev;
+  a.group = group_dev;
+  a.G = G;
+  a.stride = (n + 31) / 32;
+  return a;
+}
+
+// host arrays: group[q] in [-1, G) checked before anything is uploaded, then G * ceil(n / 32) words and
+// nq group entries on the device
+int32_t upload_groups(const uint32_t* allow_host, int32_t G, const int32_t* group_host, int64_t n, int64_t nq,
+                      DevBuf<uint32_t>& bitmap, DevBuf<int32_t>& grp, AllowGroups* out) {
+  *out = AllowGroups();
+  if (!group_host) return RPT_OK;
+  for (int64_t q = 0; q < nq; ++q)
+    if (group_host[q] < -1 || group_host[q] >= G)
+      return fail(RPT_E_ARG, "group[" + std::to_string(q) + "] = " + std::to_string(group_host[q]) +
+                                 " outside [-1, G)");
+  const size_t words = (size_t)G * (size_t)((n + 31) / 32);
+  if (words) {
+    RPT_TRY(bitmap.alloc(words));
+    RPT_HIP(hipMemcpy(bitmap.p, allow_host, words * 4, hipMemcpyHostToDevice));
+  }
+  RPT_TRY(grp.alloc((size_t)std::max<int64_t>(nq, 1)));
+  if (nq) RPT_HIP(hipMemcpy(grp.p, group_host, (size_t)nq * 4, hipMemcpyHostToDevice));
+  *out = groups_dev(words ? bitmap.p : nullptr, G, grp.p, n);
+  return RPT_OK;
+}
+}  // namespace
+}  // extern "C++"
+
 // ---- beam search over a kNN graph -------------------------------------------------------------
 namespace {
 // Rows::Csr: the rpt_graph_search_csr_* entry points (CSR data and queries, L2 only); Rows::CsrMetric:
@@ -1536,7 +1587,7 @@ int32_t search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* que
                    const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s, const int32_t* seeds_dev,
                    int32_t k, int32_t ef, int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
                    int32_t* count_dev, Rows rows, bool allow = false, int32_t width = 0,
-                   const uint32_t* allow_dev = nullptr) {
+                   const AllowGroups& allow_dev = AllowGroups()) {
   if (ctx) dev_set_stream(ctx->stream);
   if (allow && data) rows = data->csr ? Rows::CsrMetric : Rows::Dense;
   RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, rows, allow, width));
@@ -1554,15 +1605,21 @@ int32_t search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* qu
                     const int32_t* gids_host, const int32_t* gcount_host, int32_t s,
                     const int32_t* seeds_host, int32_t k, int32_t ef, int32_t metric, int32_t flags,
                     int32_t* ids_host, double* dist_host, int32_t* count_host, Rows rows, bool allow = false,
-                    int32_t width = 0, const uint32_t* allow_host = nullptr) {
+                    int32_t width = 0, const uint32_t* allow_host = nullptr, bool grouped = false, int32_t G = 0,
+                    const int32_t* group_host = nullptr) {
   if (ctx) dev_set_stream(ctx->stream);
   if (allow && data) rows = data->csr ? Rows::CsrMetric : Rows::Dense;
   RPT_TRY(check_search(ctx, data, queries, kg, s, k, ef, metric, flags, rows, allow, width));
+  if (grouped) RPT_TRY(check_group_args(allow_host, G));
   const int64_t n = data->n, nq = queries->n;
   RPT_ARG(n == 0 || (gids_host && gcount_host), "NULL graph arrays");
   RPT_ARG(nq == 0 || (seeds_host && ids_host && dist_host && count_host), "NULL seeds or output");
   RPT_TRY(check_search_arrays(n, nq, kg, gids_host, gcount_host, s, seeds_host));
   RPT_HIP(hipSetDevice(ctx->device));
+  DevBuf<uint32_t> gbits;
+  DevBuf<int32_t> ggrp;
+  AllowGroups ag;  // validated here, before anything is uploaded
+  if (grouped) RPT_TRY(upload_groups(allow_host, G, group_host, n, nq, gbits, ggrp, &ag));
   DevBuf<int32_t> gids, gcnt, seeds;
   Triple out;
   RPT_TRY(gids.alloc((size_t)n * kg));
@@ -1575,13 +1632,14 @@ int32_t search_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* qu
   }
   if (nq) RPT_HIP(hipMemcpy(seeds.p, seeds_host, (size_t)nq * s * 4, hipMemcpyHostToDevice));
   DevBuf<uint32_t> bitmap;  // the allow-list's ceil(n / 32) words
-  const size_t words = allow_host ? (size_t)((n + 31) / 32) : 0;
+  const size_t words = allow_host && !grouped ? (size_t)((n + 31) / 32) : 0;
   if (words) {
     RPT_TRY(bitmap.alloc(words));
     RPT_HIP(hipMemcpy(bitmap.p, allow_host, words * 4, hipMemcpyHostToDevice));
   }
+  if (!grouped) ag = one_bitmap(words ? bitmap.p : nullptr);
   RPT_TRY(search_dev(ctx, data, queries, kg, gids.p, gcnt.p, s, seeds.p, k, ef, metric, flags, out.ids.p,
-                     out.dist.p, out.cnt.p, rows, allow, width, words ? bitmap.p : nullptr));
+                     out.dist.p, out.cnt.p, rows, allow, width, ag));
   RPT_HIP(stream_sync(ctx->stream));
   return out.download(ids_host, dist_host, count_host);
 }
@@ -1658,7 +1716,33 @@ int32_t rpt_graph_search_allow_dev(rpt_ctx* ctx, const rpt_dataset* data, const 
                                    double* dist_dev, int32_t* count_dev) {
   return guarded([&]() -> int32_t {
     return search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric, flags,
-                      ids_dev, dist_dev, count_dev, Rows::Dense, true, width, allow_dev);
+                      ids_dev, dist_dev, count_dev, Rows::Dense, true, width, one_bitmap(allow_dev));
+  });
+}
+
+int32_t rpt_graph_search_allow_group_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                         int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
+                                         const int32_t* seeds_dev, const uint32_t* allow_dev, int32_t G,
+                                         const int32_t* group_dev, int32_t k, int32_t ef, int32_t width,
+                                         int32_t metric, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                                         int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    RPT_TRY(check_group_args(allow_dev, G));
+    return search_dev(ctx, data, queries, kg, gids_dev, gcount_dev, s, seeds_dev, k, ef, metric, flags,
+                      ids_dev, dist_dev, count_dev, Rows::Dense, true, width,
+                      groups_dev(allow_dev, G, group_dev, data ? data->n : 0));
+  });
+}
+
+int32_t rpt_graph_search_allow_group_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                          int32_t kg, const int32_t* gids_host, const int32_t* gcount_host,
+                                          int32_t s, const int32_t* seeds_host, const uint32_t* allow_host,
+                                          int32_t G, const int32_t* group_host, int32_t k, int32_t ef,
+                                          int32_t width, int32_t metric, int32_t flags, int32_t* ids_host,
+                                          double* dist_host, int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    return search_host(ctx, data, queries, kg, gids_host, gcount_host, s, seeds_host, k, ef, metric, flags,
+                       ids_host, dist_host, count_host, Rows::Dense, true, width, allow_host, true, G, group_host);
   });
 }
 
@@ -2378,7 +2462,7 @@ int32_t rpt_knn_allow_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, 
     if (ctx) dev_set_stream(ctx->stream);
     RPT_TRY(check_knn_allow(ctx, f, data, queries, k, flags));
     RPT_ARG(ids_dev && dist_dev && count_dev, "NULL output");
-    return knn_allow_dev(ctx, f, data, queries, allow_dev, k, flags, ids_dev, dist_dev, count_dev);
+    return knn_allow_dev(ctx, f, data, queries, one_bitmap(allow_dev), k, flags, ids_dev, dist_dev, count_dev);
   });
 }
 
@@ -2394,7 +2478,7 @@ int32_t rpt_knn_allow_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
     RPT_TRY(upload_allow(allow_host, data->n, bitmap, &allow_dev));
     Triple out;
     RPT_TRY(out.alloc(queries->n, k));
-    RPT_TRY(knn_allow_dev(ctx, f, data, queries, allow_dev, k, flags, out.ids.p, out.dist.p, out.cnt.p));
+    RPT_TRY(knn_allow_dev(ctx, f, data, queries, one_bitmap(allow_dev), k, flags, out.ids.p, out.dist.p, out.cnt.p));
     RPT_HIP(stream_sync(ctx->stream));
     return out.download(ids_host, dist_host, count_host);
   });
@@ -2410,7 +2494,7 @@ int32_t rpt_allow_candidates_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset
     DevBuf<uint32_t> bitmap;
     const uint32_t* allow_dev = nullptr;
     RPT_TRY(upload_allow(allow_host, f->n, bitmap, &allow_dev));
-    return allow_candidates(ctx, f, queries, allow_dev, off_host, ids_host, cap, total);
+    return allow_candidates(ctx, f, queries, one_bitmap(allow_dev), off_host, ids_host, cap, total);
   });
 }
 
@@ -2463,7 +2547,119 @@ int32_t rpt_recall_hits_allow_host(rpt_ctx* ctx, rpt_forest* f, const rpt_datase
     DevBuf<uint32_t> bitmap;
     const uint32_t* allow_dev = nullptr;
     RPT_TRY(upload_allow(allow_host, data->n, bitmap, &allow_dev));
-    return recall_hits_allow(ctx, f, data, queries, allow_dev, k, flags, hits_host, truth_ids_host);
+    return recall_hits_allow(ctx, f, data, queries, one_bitmap(allow_dev), k, flags, hits_host, truth_ids_host);
+  });
+}
+
+// ---- the same entry points under a grouped allow-list: (allow, G, group) where allow stands above ----
+int32_t rpt_knn_allow_group_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* queries,
+                                const uint32_t* allow_dev, int32_t G, const int32_t* group_dev, int32_t k,
+                                int32_t flags, int32_t* ids_dev, double* dist_dev, int32_t* count_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_knn_allow(ctx, f, data, queries, k, flags));
+    RPT_ARG(ids_dev && dist_dev && count_dev, "NULL output");
+    RPT_TRY(check_group_args(allow_dev, G));
+    return knn_allow_dev(ctx, f, data, queries, groups_dev(allow_dev, G, group_dev, data->n), k, flags, ids_dev,
+                         dist_dev, count_dev);
+  });
+}
+
+int32_t rpt_knn_allow_group_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* queries,
+                                 const uint32_t* allow_host, int32_t G, const int32_t* group_host, int32_t k,
+                                 int32_t flags, int32_t* ids_host, double* dist_host, int32_t* count_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_knn_allow(ctx, f, data, queries, k, flags));
+    RPT_ARG(ids_host && dist_host && count_host, "NULL output");
+    RPT_TRY(check_group_args(allow_host, G));
+    DevBuf<uint32_t> bitmap;
+    DevBuf<int32_t> grp;
+    AllowGroups ag;
+    RPT_TRY(upload_groups(allow_host, G, group_host, data->n, queries->n, bitmap, grp, &ag));
+    Triple out;
+    RPT_TRY(out.alloc(queries->n, k));
+    RPT_TRY(knn_allow_dev(ctx, f, data, queries, ag, k, flags, out.ids.p, out.dist.p, out.cnt.p));
+    RPT_HIP(stream_sync(ctx->stream));
+    return out.download(ids_host, dist_host, count_host);
+  });
+}
+
+int32_t rpt_allow_group_candidates_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* queries,
+                                        const uint32_t* allow_host, int32_t G, const int32_t* group_host,
+                                        int64_t* off_host, int32_t* ids_host, int64_t cap, int64_t* total) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_query(ctx, f, queries));
+    RPT_ARG(total, "total is NULL");
+    RPT_TRY(check_group_args(allow_host, G));
+    DevBuf<uint32_t> bitmap;
+    DevBuf<int32_t> grp;
+    AllowGroups ag;
+    RPT_TRY(upload_groups(allow_host, G, group_host, f->n, queries->n, bitmap, grp, &ag));
+    return allow_candidates(ctx, f, queries, ag, off_host, ids_host, cap, total);
+  });
+}
+
+int32_t rpt_brute_knn_allow_group_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                      const uint32_t* allow_dev, int32_t G, const int32_t* group_dev, int32_t k,
+                                      int32_t flags, int32_t* ids_dev, double* dist_dev) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ids_dev && dist_dev, "NULL output");
+    RPT_TRY(check_brute_allow(ctx, data, queries, k, flags));
+    RPT_TRY(check_group_args(allow_dev, G));
+    if (!group_dev) return brute_knn_allow_dev(ctx, data, queries, nullptr, k, flags, ids_dev, dist_dev);
+    return brute_knn_allow_group_dev(ctx, data, queries, groups_dev(allow_dev, G, group_dev, data->n), k, flags,
+                                     ids_dev, dist_dev);
+  });
+}
+
+int32_t rpt_brute_knn_allow_group_host(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries,
+                                       const uint32_t* allow_host, int32_t G, const int32_t* group_host, int32_t k,
+                                       int32_t flags, int32_t* ids_host, double* dist_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_ARG(ids_host && dist_host, "NULL output");
+    RPT_TRY(check_brute_allow(ctx, data, queries, k, flags));
+    RPT_TRY(check_group_args(allow_host, G));
+    const int64_t nq = queries->n;
+    DevBuf<uint32_t> bitmap;
+    DevBuf<int32_t> grp;
+    AllowGroups ag;
+    RPT_TRY(upload_groups(allow_host, G, group_host, data->n, nq, bitmap, grp, &ag));
+    if (nq == 0) return RPT_OK;
+    DevBuf<int32_t> ids;
+    DevBuf<double> dist;
+    RPT_TRY(ids.alloc((size_t)nq * k));
+    RPT_TRY(dist.alloc((size_t)nq * k));
+    if (!ag.group) RPT_TRY(brute_knn_allow_dev(ctx, data, queries, nullptr, k, flags, ids.p, dist.p));
+    else RPT_TRY(brute_knn_allow_group_dev(ctx, data, queries, ag, k, flags, ids.p, dist.p));
+    RPT_HIP(hipMemcpy(ids_host, ids.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    RPT_HIP(hipMemcpy(dist_host, dist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    return RPT_OK;
+  });
+}
+
+int32_t rpt_recall_hits_allow_group_host(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data,
+                                         const rpt_dataset* queries, const uint32_t* allow_host, int32_t G,
+                                         const int32_t* group_host, int32_t k, int32_t flags, int32_t* hits_host,
+                                         int32_t* truth_ids_host) {
+  return guarded([&]() -> int32_t {
+    if (ctx) dev_set_stream(ctx->stream);
+    RPT_TRY(check_query(ctx, f, queries));
+    RPT_ARG(hits_host, "NULL output");
+    RPT_TRY(check_brute_allow(ctx, data, queries, k, flags));
+    RPT_ARG(data->n == f->n && data->d == f->d, "data shape differs from the forest's");
+    RPT_ARG(proj_dtype(queries->dtype) == f->pdtype,
+            "query dtype must have the forest's projection type (f64 vs f32/bf16)");
+    RPT_ARG(queries->n * (int64_t)f->T <= 0x7fffffff, "too many (query, tree) pairs for one call");
+    RPT_TRY(check_group_args(allow_host, G));
+    DevBuf<uint32_t> bitmap;
+    DevBuf<int32_t> grp;
+    AllowGroups ag;
+    RPT_TRY(upload_groups(allow_host, G, group_host, data->n, queries->n, bitmap, grp, &ag));
+    return recall_hits_allow(ctx, f, data, queries, ag, k, flags, hits_host, truth_ids_host);
   });
 }
 

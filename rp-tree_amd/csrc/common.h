@@ -57,6 +57,31 @@ struct Seg {
   int32_t heap;   // heap index of the node (-1: none)
 };
 
+// ---- the grouped allow-list of the rpt_*_allow_group_* entry points ----------------------------
+// G bitmaps of `stride` words each at `bits`; query q searches under row group[q].  group[q] == -1:
+// every id is allowed; any other value outside [0, G): no id is.  A null `group` is the single
+// bitmap of the rpt_*_allow_* entry points: `bits` (null = every id) for every query.  Device memory.
+struct AllowGroups {
+  const uint32_t* bits = nullptr;
+  const int32_t* group = nullptr;
+  int32_t G = 0;
+  int64_t stride = 0;
+};
+
+// The bitmap of query q (null: every id) and, in `none`, whether no id is allowed.  Reads group[q]
+// only; the row pointer stays inside bits[0 .. G * stride) whatever group[q] holds.
+__device__ __forceinline__ const uint32_t* allow_row(const AllowGroups& a, int64_t q, bool& none) {
+  none = false;
+  if (!a.group) return a.bits;
+  const int32_t g = a.group[q];
+  if (g == -1) return nullptr;
+  if (g < 0 || g >= a.G) {
+    none = true;
+    return nullptr;
+  }
+  return a.bits + (int64_t)g * a.stride;
+}
+
 inline size_t dtype_size(int32_t dt) { return dt == RPT_F64 ? 8 : dt == RPT_F32 ? 4 : 2; }
 // compute/projection type: double for f64 data, float otherwise
 inline int32_t proj_dtype(int32_t dt) { return dt == RPT_F64 ? RPT_F64 : RPT_F32; }
@@ -188,6 +213,7 @@ struct rpt_options {
                                 // queries with more candidates sort in a global slab
   int64_t knn_vote_slice = 0;   // rpt_knn_vote_*: at most this many queries per vote-select slice (0 = by the budget)
   int64_t knn_allow_slice = 0;  // rpt_knn_allow_*: at most this many queries per compaction slice (0 = by the budget)
+  int64_t knn_allow_group_budget = 0;  // rpt_brute_knn_allow_group_*: ids of group lists one pass may hold (0 = the 1 GiB budget)
   int64_t graph_general = 0;    // kNN graph: every leaf on the tiled kernel (64-row blocks), not the one-workgroup leaf kernel
   int64_t graph_refine_general = 0;  // kNN graph refinement: one point per workgroup for every k and reverse
   int64_t graph_delete_general = 0;  // rpt_graph_delete_*: one touched row per workgroup for every kg
@@ -423,17 +449,23 @@ int32_t vote_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, int32
 // arguments checked by the caller; flags: the duplicate rule or-ed with 0 or one of
 // RPT_KNN_METRIC_COSINE / _INNER / _REFERENCE.  Returns synchronised.
 int32_t knn_allow_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
-                      const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                      const AllowGroups& allow, int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev,
                       int32_t* count_dev);
 // rpt_candidates' protocol for the allowed lists
-int32_t allow_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, const uint32_t* allow_dev,
+int32_t allow_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, const AllowGroups& allow,
                          int64_t* off_host, int32_t* ids_host, int64_t cap, int64_t* total);
 // exhaustive kNN among the allowed rows; flags: 0 or one of RPT_KNN_METRIC_COSINE / _INNER (any rows) /
 // _REFERENCE (CSR rows).  Returns synchronised.
 int32_t brute_knn_allow_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, const uint32_t* allow_dev,
                             int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev);
+// the same under a grouped allow-list with a non-null group array (one id list per referenced group,
+// in passes against knn_allow_group_budget).  Returns synchronised.
+int32_t brute_knn_allow_group_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
+                                  const AllowGroups& allow, int32_t k, int32_t flags, int32_t* ids_dev,
+                                  double* dist_dev);
+// allow.group null: the single bitmap allow.bits
 int32_t recall_hits_allow(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
-                          const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* hits_host,
+                          const AllowGroups& allow, int32_t k, int32_t flags, int32_t* hits_host,
                           int32_t* truth_ids_host);
 int32_t knn_merge_dev(rpt_ctx* ctx, const int32_t* ids_dev, const double* dist_dev,
                       const int32_t* count_dev, int64_t shard_stride, int32_t G, int64_t nq,
@@ -492,12 +524,13 @@ int32_t knn_graph_refine_last(rpt_ctx* ctx, int64_t* rounds, int64_t* updates, i
 // k <= ef <= RPT_GRAPH_SEARCH_MAX_EF; metric as knn_graph_dev's); the arrays are not validated:
 // entries out of range are skipped; enqueued on the ctx stream.  width == 0: rpt_graph_search_*.
 // width in [ef, RPT_GRAPH_SEARCH_MAX_WIDTH]: rpt_graph_search_allow_* with the allow-list allow_dev
-// (ceil(n / 32) words, null = every id), which launches whatever the shape
+// (single bitmap: ceil(n / 32) words, null = every id; or grouped, see AllowGroups), which launches
+// whatever the shape
 int32_t graph_search_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* queries, int32_t kg,
                          const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
                          const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
                          int32_t* ids_dev, double* dist_dev, int32_t* count_dev, int32_t width = 0,
-                         const uint32_t* allow_dev = nullptr);
+                         const AllowGroups& allow = AllowGroups());
 // the same on CSR rows (graph_search_csr.hip): CSR data and queries of one d and dtype (f64 or f32
 // values); metric as knn_graph_dev's, the cosine / inner-product distances from dotS (rptree_hip.h);
 // the statistics go where graph_search_dev's go
@@ -505,7 +538,7 @@ int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_da
                              int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
                              const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
                              int32_t* ids_dev, double* dist_dev, int32_t* count_dev, int32_t width = 0,
-                             const uint32_t* allow_dev = nullptr);
+                             const AllowGroups& allow = AllowGroups());
 // synchronises the stream
 int32_t graph_search_last(rpt_ctx* ctx, int64_t* expansions, int64_t* evaluated);
 // ---- a kNN graph made ready for the search (graph_prepare.hip) ---------------------------------

@@ -209,7 +209,8 @@ struct SearchArgs {
   const int32_t* gids;
   const int32_t* gcount;
   const int32_t* seeds;
-  const uint32_t* allow;  // the allow-list: bit i & 31 of word i >> 5; null = every id (F only)
+  AllowGroups allow;  // the allow-list: bit i & 31 of word i >> 5 of the query's row (F only); the group
+                      // array and the row stride of rpt_graph_search_allow_group_*, or one bitmap
   const double* rn;  // dot(x, x) of the data rows (cosine)
   const double* qn;  // ... of the queries
   int32_t* ids;
@@ -251,10 +252,29 @@ inline int search_waves(int wave_bytes, int lds) {
 
 __device__ inline int beam_id(int v) { return v < 0 ? ~v : v; }
 
+// The allow-list of the wave's query, resolved once before the seeds: `bits` is the query's bitmap
+// (null: every id), `none` says that no id is allowed (a group value outside [-1, G)).  group[qi] is
+// wave-uniform, so the row pointer is made from a scalar.
+struct BeamAllow {
+  const uint32_t* bits;
+  bool none;
+};
+
+__device__ __forceinline__ BeamAllow beam_allow_of(const SearchArgs& a, int64_t qi) {
+  BeamAllow r = {a.allow.bits, false};
+  if (a.allow.group) {
+    const int g = __builtin_amdgcn_readfirstlane(a.allow.group[qi]);
+    r.bits = nullptr;
+    if (g >= 0 && g < a.allow.G) r.bits = a.allow.bits + (int64_t)g * a.allow.stride;
+    else r.none = g != -1;
+  }
+  return r;
+}
+
 // whether id v (in [0, n), or -1 on an idle lane) is in the allow-list: one 32-bit load
-__device__ inline bool beam_allowed(const SearchArgs& a, int v) {
-  if (v < 0) return false;
-  return a.allow == nullptr || ((a.allow[v >> 5] >> (v & 31)) & 1u) != 0;
+__device__ inline bool beam_allowed(const BeamAllow& w, int v) {
+  if (v < 0 || w.none) return false;
+  return w.bits == nullptr || ((w.bits[v >> 5] >> (v & 31)) & 1u) != 0;
 }
 
 // The next offer, a candidate per lane (-1: none): a batch of R seeds, then the graph row of the

@@ -132,6 +132,8 @@ __device__ __forceinline__ void graph_search_csr_body(
     wave_sync();
     double qnorm = 0.0;
     if constexpr (M == kGraphCosine) qnorm = a.qn[qi];
+    BeamAllow aw = {nullptr, false};  // F: the query's own bitmap
+    if constexpr (F) aw = beam_allow_of(a, qi);
 
     int c = 0;   // entries of the beam
     int na = 0;  // F: the allowed ones among them
@@ -188,7 +190,7 @@ __device__ __forceinline__ void graph_search_csr_body(
 
       // ---- into the beam, one at a time, by the order of before()
       if constexpr (F)
-        beam_insert<true, J>(bd, bi, c, ef, nj, lane, nrows, cd, my, ba, a.width, &na, beam_allowed(a, my));
+        beam_insert<true, J>(bd, bi, c, ef, nj, lane, nrows, cd, my, ba, a.width, &na, beam_allowed(aw, my));
       else
         beam_insert(bd, bi, c, ef, nj, lane, nrows, cd, my);
     }
@@ -268,7 +270,7 @@ int32_t graph_search_csr_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_da
                              int32_t kg, const int32_t* gids_dev, const int32_t* gcount_dev, int32_t s,
                              const int32_t* seeds_dev, int32_t k, int32_t ef, int32_t metric,
                              int32_t* ids_dev, double* dist_dev, int32_t* count_dev, int32_t width,
-                             const uint32_t* allow_dev) {
+                             const AllowGroups& allow_dev) {
   const bool allow = width != 0;  // rpt_graph_search_allow_*
   const int m = graph_metric_of(metric);
   if (m == kGraphCosine) {  // the rows' dotS(x, x), cached on the two datasets

@@ -28,6 +28,8 @@
 #include <vector>
 
 #include "common.h"
+#include <unordered_map>
+
 #include "knn_allow.h"
 #include "knn_vote.h"
 
@@ -5092,7 +5094,7 @@ static int32_t allow_prepare(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, 
 }
 
 static int32_t allow_slice_compact(rpt_ctx* ctx, rpt_forest* f, AllowWork& w, const AllowSlice& sl,
-                                   const uint32_t* allow_dev) {
+                                   const AllowGroups& allow_dev) {
   ProfScope ps(ctx, RPT_PROF_KNN_VOTE);  // class 5: the candidate-list step
   return allow_compact(ctx, f->perm.p, reinterpret_cast<const VoteRange*>(w.pl.ranges.p), w.pl.rng_off.p,
                        w.pl.cand_off.p, f->T, sl, allow_dev, w.ids.p, reinterpret_cast<VoteRange*>(w.vranges.p),
@@ -5108,7 +5110,7 @@ static int32_t allow_read_total(rpt_ctx* ctx, AllowWork& w) {
 }
 
 int32_t knn_allow_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
-                      const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev,
+                      const AllowGroups& allow_dev, int32_t k, int32_t flags, int32_t* ids_dev, double* dist_dev,
                       int32_t* count_dev) {
   RPT_ARG(k <= kBuf / 2, "k too large for the LDS merge buffer");
   RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
@@ -5140,7 +5142,7 @@ int32_t knn_allow_dev(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, cons
   return allow_read_total(ctx, w);  // synchronises: the scratch is released on return
 }
 
-int32_t allow_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, const uint32_t* allow_dev,
+int32_t allow_candidates(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* q, const AllowGroups& allow_dev,
                          int64_t* off_host, int32_t* ids_host, int64_t cap, int64_t* total) {
   const bool fill = ids_host != nullptr;
   ctx->last_allowed = 0;
@@ -5478,23 +5480,35 @@ constexpr int kBcRows = kBcGroups * kBcU;            // rows per batch
 static_assert((kBcRows & (kBcRows - 1)) == 0 && kBcThreads % kBcRows == 0, "batch shape");
 
 // ALLOW: only the rows whose bit of `allow` is set are offered (rpt_brute_knn_allow_*); a compile-time
-// switch, off in the unfiltered instantiation, whose code it leaves as it was.
-template <class TD, int QT, bool ALLOW = false>
+// switch, off (0) in the unfiltered instantiation, whose code it leaves as it was.  1: one bitmap for
+// every query.  2 (rpt_brute_knn_allow_group_*): tile query i's own bitmap, resolved once per tile into
+// LDS (allow_row: a row of ag.bits, every id, or none).
+template <class TD, int QT, int ALLOW = 0>
 __global__ __launch_bounds__(kBcThreads) void brute_csr_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
     const TD* __restrict__ val, int64_t nnz, int64_t n, int d,
     const int64_t* __restrict__ qrowptr, const int32_t* __restrict__ qcol,
     const TD* __restrict__ qval, int64_t nq, int k, int cap, int64_t rows_per_block, int refm,
     int32_t* __restrict__ out_ids, double* __restrict__ out_dist, int32_t* __restrict__ out_cnt,
-    const uint32_t* __restrict__ allow /* ALLOW only: ceil(n / 32) words */) {
+    AllowGroups ag /* ALLOW only: ceil(n / 32) words per bitmap */) {
+  const uint32_t* __restrict__ allow = ag.bits;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* qs = reinterpret_cast<double*>(smem);                                   // [d][QT]
   Entry* bufs = reinterpret_cast<Entry*>(smem + (size_t)d * QT * sizeof(double));  // [QT][cap]
   __shared__ double s_qn2[QT], s_thr[QT];
   __shared__ int s_fill[QT], s_have[QT];
+  __shared__ const uint32_t* s_abits[ALLOW == 2 ? QT : 1];  // ALLOW == 2: query i's bitmap (null: every id)
+  __shared__ int s_anone[ALLOW == 2 ? QT : 1];              // ... 1: no id is allowed
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t q0 = (int64_t)blockIdx.x * QT;
   const int nqt = nq - q0 < QT ? (int)(nq - q0) : QT;
+  if constexpr (ALLOW == 2) {
+    if (tid < QT) {  // (read behind the first barrier below)
+      bool none = true;
+      s_abits[tid] = tid < nqt ? allow_row(ag, q0 + tid, none) : nullptr;
+      s_anone[tid] = none ? 1 : 0;
+    }
+  }
   const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
   const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
   for (int j = tid; j < d * QT; j += kBcThreads) qs[j] = 0.0;
@@ -5529,7 +5543,13 @@ __global__ __launch_bounds__(kBcThreads) void brute_csr_kernel(
     __syncthreads();
   }
   auto push = [&](int i, double dist, int row) {
-    if (ALLOW && !((allow[row >> 5] >> (row & 31)) & 1u)) return;
+    if constexpr (ALLOW == 1) {
+      if (!((allow[row >> 5] >> (row & 31)) & 1u)) return;
+    }
+    if constexpr (ALLOW == 2) {
+      const uint32_t* ab = s_abits[i];
+      if (s_anone[i] || (ab && !((ab[row >> 5] >> (row & 31)) & 1u))) return;
+    }
     if (!s_have[i] || (dist == dist && !(dist >= s_thr[i])))
       bufs[i * cap + atomicAdd(&s_fill[i], 1)] = Entry{dist, row, row};
   };
@@ -5686,10 +5706,12 @@ constexpr size_t kBcLds = 150 * 1024;  // the budget the other query kernels kee
 template <class TD, int QT>
 static int32_t launch_brute_csr_t(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k,
                                   int refm, int64_t rows_per_block, int nblk, int32_t* ids,
-                                  double* dist, int32_t* cnt, const uint32_t* allow) {
+                                  double* dist, int32_t* cnt, const AllowGroups& allow) {
   const size_t smem = brute_csr_smem(data->d, QT, k);
   const int64_t tiles = (q->n + QT - 1) / QT;
-  RPT_HIP(launch_dyn(allow ? brute_csr_kernel<TD, QT, true> : brute_csr_kernel<TD, QT, false>,
+  RPT_HIP(launch_dyn(allow.group  ? brute_csr_kernel<TD, QT, 2>
+                     : allow.bits ? brute_csr_kernel<TD, QT, 1>
+                                  : brute_csr_kernel<TD, QT, 0>,
                      dim3((unsigned)tiles, (unsigned)nblk),
                      dim3(kBcThreads), smem, ctx->stream, data->rowptr, data->col,
                      (const TD*)data->val, data->nnz, data->n, data->d, q->rowptr, q->col,
@@ -5701,7 +5723,7 @@ static int32_t launch_brute_csr_t(rpt_ctx* ctx, const rpt_dataset* data, const r
 template <class TD>
 static int32_t launch_brute_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k,
                                 int refm, int qt, int64_t rows_per_block, int nblk, int32_t* ids,
-                                double* dist, int32_t* cnt, const uint32_t* allow) {
+                                double* dist, int32_t* cnt, const AllowGroups& allow) {
   switch (qt) {
     case 8: return launch_brute_csr_t<TD, 8>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt, allow);
     case 4: return launch_brute_csr_t<TD, 4>(ctx, data, q, k, refm, rows_per_block, nblk, ids, dist, cnt, allow);
@@ -5728,10 +5750,12 @@ static int brute_csr_tile(const rpt_ctx* ctx, int d, int k, int64_t nq) {
 }
 
 // exhaustive kNN of CSR queries over CSR rows 0 .. n-1, k best by (distance, id), into device
-// arrays [nq][k]; cnt: [nq] ints of device scratch.  allow: null, or the bitmap of the rows offered.
+// arrays [nq][k]; cnt: [nq] ints of device scratch.  allow: empty, the one bitmap of the rows offered
+// (allow.bits), or with allow.group every query's own.
 // Enqueues only.
 static int32_t brute_csr(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q, int k, int refm,
-                         int32_t* ids_dev, double* dist_dev, int32_t* cnt_dev, const uint32_t* allow = nullptr) {
+                         int32_t* ids_dev, double* dist_dev, int32_t* cnt_dev,
+                         const AllowGroups& allow = AllowGroups()) {
   RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
   RPT_ARG(data->n <= 0x7fffffff, "too many rows");
   const int64_t nq = q->n, n = data->n;
@@ -6277,7 +6301,9 @@ int32_t brute_knn_allow_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dat
   DevBuf<Range> rg;
   if (data->csr && flags == 0) {
     RPT_TRY(cnt.alloc((size_t)nq));
-    RPT_TRY(brute_csr(ctx, data, q, k, 0, ids_dev, dist_dev, cnt.p, allow_dev));
+    AllowGroups one;
+    one.bits = allow_dev;
+    RPT_TRY(brute_csr(ctx, data, q, k, 0, ids_dev, dist_dev, cnt.p, one));
     RPT_HIP(stream_sync(ctx->stream));
     return RPT_OK;
   }
@@ -6297,10 +6323,178 @@ int32_t brute_knn_allow_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dat
   return RPT_OK;
 }
 
+namespace {
+// rows [q][k] of a pass's scratch answer into the call's, for the queries whose list slot[q] the pass
+// built (slots s0 .. s1 - 1); `none` also takes the queries without a list (slot -1: no id allowed)
+__global__ void allow_pass_copy_kernel(const int32_t* __restrict__ slot, int32_t s0, int32_t s1, int none, int64_t nq,
+                                       int k, const int32_t* __restrict__ si, const double* __restrict__ sd,
+                                       int32_t* __restrict__ oi, double* __restrict__ od) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nq * k) return;
+  const int32_t sl = slot[e / k];
+  if ((sl >= s0 && sl < s1) || (none && sl < 0)) {
+    oi[e] = si[e];
+    od[e] = sd[e];
+  }
+}
+}  // namespace
+
+// The exhaustive kNN under a grouped allow-list (allow.group non-null).  CSR rows under flags 0 stay on
+// brute_csr_kernel, whose tile queries test their own bitmaps.  Every other cell ranks lists: ONE
+// ascending id list per group that a query names (and one of all ids when a query is unfiltered),
+// concatenated in a slab; query q's single range is {start, length, 0} of its group's list.  The lists
+// are sized from their popcounts against a fixed budget of ids per pass (knn_allow_group_budget, else
+// the 1 GiB of the other list routes; a list above it is a pass of its own).  More than one pass: each
+// pass ranks every query, the queries of other passes over an empty range, into scratch, and its own
+// queries' rows are copied out; a query's answer is a function of its list alone, so the budget changes
+// no bit.  Returns synchronised.
+int32_t brute_knn_allow_group_dev(rpt_ctx* ctx, const rpt_dataset* data, const rpt_dataset* q,
+                                  const AllowGroups& allow, int32_t k, int32_t flags, int32_t* ids_dev,
+                                  double* dist_dev) {
+  RPT_ARG(k <= kBuf / 2, "k too large");
+  RPT_ARG((size_t)data->d * 8 + (sizeof(Entry) + 4) * kBuf <= 150 * 1024, "d too large");
+  RPT_ARG(data->n <= 0x7fffffff, "too many rows");
+  ctx->last_uncertified = 0;
+  ctx->metric_unc_pending = false;
+  const int64_t nq = q->n, n = data->n;
+  if (nq == 0) return RPT_OK;
+  DevBuf<int32_t> cnt;
+  RPT_TRY(cnt.alloc((size_t)nq));
+  if (data->csr && flags == 0) {
+    RPT_TRY(brute_csr(ctx, data, q, k, 0, ids_dev, dist_dev, cnt.p, allow));
+    RPT_HIP(stream_sync(ctx->stream));
+    return RPT_OK;
+  }
+  // the lists the batch names, in the order of their first query
+  // (the map holds at most nq groups whatever G is: the _dev entry point does not validate G)
+  std::vector<int32_t> hg((size_t)nq), slot((size_t)nq), sel;
+  std::unordered_map<int32_t, int32_t> slot_of;
+  RPT_HIP(hipMemcpyAsync(hg.data(), allow.group, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+  RPT_HIP(stream_sync(ctx->stream));
+  int32_t all_slot = -1;
+  for (int64_t i = 0; i < nq; ++i) {
+    const int32_t g = hg[(size_t)i];
+    int32_t* at = nullptr;
+    if (g == -1) at = &all_slot;
+    else if (g >= 0 && g < allow.G) at = &slot_of.emplace(g, -1).first->second;
+    if (at && *at < 0) {
+      *at = (int32_t)sel.size();
+      sel.push_back(g);
+    }
+    slot[(size_t)i] = at ? *at : -1;
+  }
+  const int64_t R = (int64_t)sel.size(), nblk = allow_list_blocks(n);
+  DevBuf<int32_t> sel_dev, slot_dev, list, unc, si;
+  DevBuf<int64_t> block_off, list_off_dev, ro;
+  DevBuf<double> sd;
+  DevBuf<Range> rg;
+  std::vector<int64_t> len((size_t)R, 0), list_off((size_t)R, 0);
+  if (R > 0) {
+    RPT_TRY(sel_dev.alloc((size_t)R));
+    RPT_TRY(block_off.alloc((size_t)(R * (nblk + 1))));
+    RPT_TRY(list_off_dev.alloc((size_t)R));
+    RPT_HIP(hipMemcpyAsync(sel_dev.p, sel.data(), (size_t)R * 4, hipMemcpyHostToDevice, ctx->stream));
+    {
+      ProfScope ps(ctx, RPT_PROF_KNN_VOTE);  // class 5: the candidate-list step
+      RPT_TRY(allow_group_count(ctx, allow.bits, allow.stride, n, sel_dev.p, R, block_off.p));
+    }
+    RPT_HIP(hipMemcpy2DAsync(len.data(), 8, block_off.p + nblk, (size_t)(nblk + 1) * 8, 8, (size_t)R,
+                             hipMemcpyDeviceToHost, ctx->stream));
+    RPT_HIP(stream_sync(ctx->stream));
+  }
+  // passes: consecutive lists while their ids fit the budget
+  const int64_t budget = ctx->opt.knn_allow_group_budget > 0 ? ctx->opt.knn_allow_group_budget : kVoteBudgetWords;
+  std::vector<int32_t> pass_end;  // one past the last list of each pass
+  int64_t fill = 0, slab = 1;
+  for (int64_t r = 0; r < R; ++r) {
+    if (r > 0 && fill > 0 && fill + len[(size_t)r] > budget) {
+      pass_end.push_back((int32_t)r);
+      fill = 0;
+    }
+    list_off[(size_t)r] = fill;
+    fill += len[(size_t)r];
+    slab = std::max(slab, fill);
+  }
+  pass_end.push_back((int32_t)R);  // (no list at all: one pass of empty ranges)
+  const bool multi = pass_end.size() > 1;
+  RPT_TRY(list.alloc((size_t)slab));
+  RPT_TRY(rg.alloc((size_t)nq));
+  RPT_TRY(ro.alloc((size_t)nq + 1));
+  RPT_TRY(unc.alloc((size_t)nq));
+  if (R > 0) RPT_HIP(hipMemcpyAsync(list_off_dev.p, list_off.data(), (size_t)R * 8, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<int64_t> hro((size_t)nq + 1);
+  for (int64_t i = 0; i <= nq; ++i) hro[(size_t)i] = i;
+  RPT_HIP(hipMemcpyAsync(ro.p, hro.data(), (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (multi) {
+    RPT_TRY(si.alloc((size_t)nq * k));
+    RPT_TRY(sd.alloc((size_t)nq * k));
+    RPT_TRY(slot_dev.alloc((size_t)nq));
+    RPT_HIP(hipMemcpyAsync(slot_dev.p, slot.data(), (size_t)nq * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
+  RPT_HIP(stream_sync(ctx->stream));  // (the host vectors above may go)
+  std::vector<Range> hr((size_t)nq);
+  int64_t uncertified = 0;
+  int32_t s0 = 0;
+  for (size_t p = 0; p < pass_end.size(); ++p) {
+    const int32_t s1 = pass_end[p];
+    if (s1 > s0) {
+      ProfScope ps(ctx, RPT_PROF_KNN_VOTE);
+      RPT_TRY(allow_group_scatter(ctx, allow.bits, allow.stride, n, sel_dev.p + s0, s1 - s0,
+                                  block_off.p + (int64_t)s0 * (nblk + 1), list_off_dev.p + s0, list.p));
+    }
+    for (int64_t i = 0; i < nq; ++i) {
+      const int32_t sl = slot[(size_t)i];
+      const bool mine = sl >= s0 && sl < s1;
+      hr[(size_t)i] = Range{mine ? list_off[(size_t)sl] : 0, mine ? (int32_t)len[(size_t)sl] : 0, 0};
+    }
+    RPT_HIP(hipMemcpyAsync(rg.p, hr.data(), (size_t)nq * sizeof(Range), hipMemcpyHostToDevice, ctx->stream));
+    RPT_HIP(stream_sync(ctx->stream));  // (hr is written again by the next pass)
+    RPT_TRY(launch_lists(ctx, data, q, list.p, rg.p, ro.p, k, 0, flags & (RPT_KNN_METRIC_COSINE | RPT_KNN_METRIC_INNER),
+                         (flags & RPT_KNN_METRIC_REFERENCE) ? 1 : 0, unc.p, multi ? si.p : ids_dev,
+                         multi ? sd.p : dist_dev, cnt.p));
+    if (multi) {
+      // The statistic is a sum over the queries, so a pass counts its OWN queries only (the others rank an
+      // empty range here and their real list in another pass): the launch's list of uncertified queries
+      // (unc[0 .. count), query numbers) is read back, or, where a launch reports every query (the
+      // *_exact options), the pass's own queries are taken for it.
+      const bool first = p == 0;
+      auto own = [&](int64_t i) {
+        const int32_t sl = slot[(size_t)i];
+        return (sl >= s0 && sl < s1) || (first && sl < 0);
+      };
+      if (ctx->metric_unc_pending) {
+        unsigned long long nu = 0;
+        RPT_HIP(hipMemcpyAsync(&nu, ctx->metric_unc_dev, 8, hipMemcpyDeviceToHost, ctx->stream));
+        RPT_HIP(stream_sync(ctx->stream));
+        nu = std::min<unsigned long long>(nu, (unsigned long long)nq);
+        std::vector<int32_t> hu((size_t)nu);
+        if (nu) RPT_HIP(hipMemcpy(hu.data(), unc.p, (size_t)nu * 4, hipMemcpyDeviceToHost));
+        for (const int32_t i : hu) uncertified += i >= 0 && i < nq && own(i) ? 1 : 0;
+      } else if (ctx->last_uncertified == nq) {
+        for (int64_t i = 0; i < nq; ++i) uncertified += own(i) ? 1 : 0;
+      } else {
+        uncertified += ctx->last_uncertified;
+      }
+      const int64_t el = nq * k;
+      hipLaunchKernelGGL(allow_pass_copy_kernel, dim3((unsigned)((el + 255) / 256)), dim3(256), 0, ctx->stream,
+                         slot_dev.p, s0, s1, p == 0 ? 1 : 0, nq, k, si.p, sd.p, ids_dev, dist_dev);
+      RPT_HIP(hipGetLastError());
+      RPT_HIP(stream_sync(ctx->stream));  // the slab and the ranges are written again by the next pass
+    }
+    s0 = s1;
+  }
+  if (multi) {
+    ctx->last_uncertified = uncertified;
+    ctx->metric_unc_pending = false;
+  }
+  RPT_HIP(stream_sync(ctx->stream));
+  return RPT_OK;
+}
+
 // recall_hits with the truth taken among the allowed rows (brute_knn_allow_dev).  The truth holds
 // allowed rows only, so the trees' unfiltered candidates intersect it as the allowed ones would.
 int32_t recall_hits_allow(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, const rpt_dataset* q,
-                          const uint32_t* allow_dev, int32_t k, int32_t flags, int32_t* hits_host,
+                          const AllowGroups& allow, int32_t k, int32_t flags, int32_t* hits_host,
                           int32_t* truth_ids_host) {
   const int64_t nq = q->n;
   if (nq == 0) return RPT_OK;
@@ -6309,7 +6503,8 @@ int32_t recall_hits_allow(rpt_ctx* ctx, rpt_forest* f, const rpt_dataset* data, 
   RPT_TRY(ids.alloc((size_t)nq * k));
   RPT_TRY(dist.alloc((size_t)nq * k));
   RPT_TRY(hits.alloc((size_t)nq * f->T));
-  RPT_TRY(brute_knn_allow_dev(ctx, data, q, allow_dev, k, flags, ids.p, dist.p));
+  if (allow.group) RPT_TRY(brute_knn_allow_group_dev(ctx, data, q, allow, k, flags, ids.p, dist.p));
+  else RPT_TRY(brute_knn_allow_dev(ctx, data, q, allow.bits, k, flags, ids.p, dist.p));
   QueryPlan pl;
   RPT_TRY(make_plan(ctx, f, q, pl));
   hipLaunchKernelGGL(recall_hits_kernel, dim3((unsigned)(nq * f->T)), dim3(256), 0, ctx->stream, ids.p, k,

@@ -1057,4 +1057,107 @@ inline std::vector<int32_t> recallHitsAllow(const RPForest& tts, const std::vect
   return hits;
 }
 
+// ---- allow-lists per query group (rpt_*_allow_group_host): many tenants in one batch ----
+// graphSearchAllowGroup, knnAllowGroup, allowGroupCandidates, bruteKnnAllowGroup and recallHitsAllowGroup
+// take (allow, G, group) where graphSearchAllow, knnAllow, ... take `allow`: G bitmaps of
+// ceil(n / 32) words each, one after the other (allowBitmaps packs masks), and one group entry per
+// query; query q is answered under bitmap group[q], -1 = every id.  The answer of query q is what the
+// single-bitmap function gives that query under its bitmap, bit for bit.  A group entry outside
+// [-1, G) is refused (RPT_E_ARG).
+inline std::vector<uint32_t> allowBitmaps(const std::vector<std::vector<bool>>& masks) {
+  std::vector<uint32_t> words;
+  for (const std::vector<bool>& m : masks) {
+    const std::vector<uint32_t> w = allowBitmap(m);
+    words.insert(words.end(), w.begin(), w.end());
+  }
+  return words;
+}
+inline const uint32_t* allowGroupWords(const std::vector<uint32_t>& allow, int G, const std::vector<int32_t>& group,
+                                       int64_t n, int64_t nq, const char* who) {
+  if (G < 0 || allow.size() != (size_t)G * (((size_t)n + 31) / 32))
+    throw RPTError(RPT_E_ARG, std::string(who) + ": allow must hold G rows of ceil(n / 32) words");
+  if (group.size() != (size_t)nq) throw RPTError(RPT_E_ARG, std::string(who) + ": group must hold one entry per query");
+  static const uint32_t no_rows = 0;  // G bitmaps of no words (n = 0) are still not a null allow
+  return G == 0 ? nullptr : allow.empty() ? &no_rows : allow.data();
+}
+inline KnnResult graphSearchAllowGroup(Context& ctx, const Dataset& data, const GraphResult& g, const Dataset& qs,
+                                  const std::vector<uint32_t>& allow, int G, const std::vector<int32_t>& group, int k,
+                                  int ef, int width, const std::vector<int32_t>& seeds, int s,
+                                  Metric metric = Metric::L2, SearchStats* stats = nullptr) {
+  const uint32_t* w = allowGroupWords(allow, G, group, data.n, qs.n, "graphSearchAllowGroup");
+  if (width == 0) width = std::min(RPT_GRAPH_SEARCH_MAX_WIDTH, 8 * ef);
+  return graphSearchVia(
+      [&](const int32_t* gids, const int32_t* gcount, const int32_t* sd, int32_t flags, int32_t* ids, double* dist,
+          int32_t* count) {
+        return rpt_graph_search_allow_group_host(ctx.get(), data.get(), qs.get(), g.k, gids, gcount, s, sd, w, G,
+                                                 group.data(), k, ef, width, metric_flags(metric), flags, ids, dist,
+                                                 count);
+      },
+      "graphSearchAllowGroup", ctx, data, g, qs, k, seeds, s, stats);
+}
+// ... the seeds taken from a forest under the same metric (unfiltered: seeds need not be allowed)
+inline KnnResult graphSearchAllowGroup(const RPForest& tts, const GraphResult& g, const Dataset& qs,
+                                  const std::vector<uint32_t>& allow, int G, const std::vector<int32_t>& group, int k,
+                                  int ef, int width = 0, Metric metric = Metric::L2, int seed_k = 8,
+                                  SearchStats* stats = nullptr) {
+  const bool csr_metric = tts.data->csr && metric != Metric::L2;
+  return graphSearchAllowGroup(*tts.ctx, *tts.data, g, qs, allow, G, group, k, ef, width,
+                          forestSeeds(tts, qs, seed_k, csr_metric ? rpt_knn_csr_metric_host : rpt_knn_host,
+                                      RPT_KNN_DEDUP | metric_flags(metric), "graphSearchAllowGroup"),
+                          seed_k, metric, stats);
+}
+inline KnnResult knnAllowGroup(const RPForest& tts, const std::vector<uint32_t>& allow, int G,
+                          const std::vector<int32_t>& group, int k, const Dataset& qs,
+                          int32_t dedup = RPT_KNN_KEEP_DUPLICATES, Metric metric = Metric::L2, int32_t flags = 0) {
+  KnnResult r{k, std::vector<int32_t>((size_t)qs.n * k + 1), std::vector<double>((size_t)qs.n * k + 1),
+              std::vector<int32_t>((size_t)qs.n + 1)};
+  check(rpt_knn_allow_group_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(),
+                                 allowGroupWords(allow, G, group, tts.data->n, qs.n, "knnAllowGroup"), G, group.data(), k,
+                                 dedup | metric_flags(metric) | flags, r.ids.data(), r.dist.data(), r.count.data()));
+  r.ids.resize((size_t)qs.n * k);
+  r.dist.resize((size_t)qs.n * k);
+  r.count.resize((size_t)qs.n);
+  return r;
+}
+inline std::vector<int32_t> allowGroupCandidates(const RPForest& tts, const std::vector<uint32_t>& allow, int G,
+                                            const std::vector<int32_t>& group, const Dataset& qs,
+                                            std::vector<int64_t>* off = nullptr) {
+  const uint32_t* w = allowGroupWords(allow, G, group, tts.data->n, qs.n, "allowGroupCandidates");
+  std::vector<int64_t> o((size_t)qs.n + 1);
+  int64_t total = 0;
+  check(rpt_allow_group_candidates_host(tts.ctx->get(), tts.get(), qs.get(), w, G, group.data(), o.data(), nullptr, 0,
+                                        &total));
+  std::vector<int32_t> ids((size_t)(total > 0 ? total : 1));
+  check(rpt_allow_group_candidates_host(tts.ctx->get(), tts.get(), qs.get(), w, G, group.data(), o.data(), ids.data(),
+                                        total, &total));
+  ids.resize((size_t)total);
+  if (off) *off = o;
+  return ids;
+}
+inline BruteResult bruteKnnAllowGroup(Context& ctx, const Dataset& data, const std::vector<uint32_t>& allow, int G,
+                                 const std::vector<int32_t>& group, const Dataset& qs, int k,
+                                 Metric metric = Metric::L2, int32_t flags = 0) {
+  BruteResult r{std::vector<int32_t>((size_t)qs.n * k + 1), std::vector<double>((size_t)qs.n * k + 1)};
+  check(rpt_brute_knn_allow_group_host(ctx.get(), data.get(), qs.get(),
+                                       allowGroupWords(allow, G, group, data.n, qs.n, "bruteKnnAllowGroup"), G,
+                                       group.data(), k, metric_flags(metric) | flags, r.ids.data(), r.dist.data()));
+  r.ids.resize((size_t)qs.n * k);
+  r.dist.resize((size_t)qs.n * k);
+  return r;
+}
+inline std::vector<int32_t> recallHitsAllowGroup(const RPForest& tts, const std::vector<uint32_t>& allow, int G,
+                                            const std::vector<int32_t>& group, int k, const Dataset& qs,
+                                            Metric metric = Metric::L2, int32_t flags = 0,
+                                            std::vector<int32_t>* truth = nullptr) {
+  std::vector<int32_t> hits((size_t)qs.n * tts.T + 1);
+  if (truth) truth->assign((size_t)qs.n * k + 1, -1);
+  check(rpt_recall_hits_allow_group_host(tts.ctx->get(), tts.get(), tts.data->get(), qs.get(),
+                                         allowGroupWords(allow, G, group, tts.data->n, qs.n, "recallHitsAllowGroup"), G,
+                                         group.data(), k, metric_flags(metric) | flags, hits.data(),
+                                         truth ? truth->data() : nullptr));
+  hits.resize((size_t)qs.n * tts.T);
+  if (truth) truth->resize((size_t)qs.n * k);
+  return hits;
+}
+
 }  // namespace rptree

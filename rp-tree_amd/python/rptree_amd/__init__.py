@@ -51,6 +51,9 @@ __all__ = [
     "knnVote", "knnVoteDev", "voteCandidates", "knnVoteLast",
     "knnAllow", "knnAllowDev", "allowCandidates", "knnAllowLast", "bruteKnnAllow", "bruteKnnAllowDev",
     "recallHitsAllow", "recallWithAllowBatch",
+    "allowBitmaps", "graphSearchAllowGroup", "graphSearchAllowGroupDev", "knnAllowGroup", "knnAllowGroupDev",
+    "allowGroupCandidates", "bruteKnnAllowGroup", "bruteKnnAllowGroupDev", "recallHitsAllowGroup",
+    "recallWithAllowGroupBatch",
 ]
 
 _DT = {np.dtype(np.float64): RPT_F64, np.dtype(np.float32): RPT_F32}
@@ -912,6 +915,18 @@ def _allow_words(allow, n):
     return words, _vp(words)
 
 
+def _allow_group_args(allow, group, n, nq):
+    """(allow, group) of a grouped call (graphSearchAllowGroup, knnAllowGroup, ...) -> (words[G][ceil(n / 32)], their address or None, G, group as
+    int32[nq], its address).  allow: what allowBitmaps takes, or its result; None or empty = no bitmap
+    (G = 0: every group entry must be -1).  group None is the C ABI's null group: every query unfiltered."""
+    g = None if group is None else np.ascontiguousarray(group, dtype=np.int32)
+    if g is not None and g.shape != (nq,):
+        raise ValueError("group must hold one int per query (nq = %d)" % nq)
+    words = allowBitmaps([] if allow is None else allow, n)
+    G = int(words.shape[0])
+    return words, (_vp(words) if G else None), G, g, _vp(g)
+
+
 def _dedup_flag(dedup):
     return (RPT_KNN_DEDUP_DISTANCE if dedup == RPT_KNN_DEDUP_DISTANCE
             else RPT_KNN_DEDUP if dedup else RPT_KNN_KEEP_DUPLICATES)
@@ -928,7 +943,7 @@ def knnAllow(allow, k, forest, qs, dedup=False, metric=None, reference_metric=Fa
     reference_metric: SVector rows by the reference's truncating metricSSL2), batch and streamed
     forests, k up to 1024.  With every id allowed the answer is knnBatch's bit for bit.  The seeds of
     graphSearchAllow under the same list: knnAllow(allow, seed_k, forest, qs, dedup=True, metric=metric)[0]
-    (unused slots are -1 already)."""
+    (unused slots are -1 already).  A bitmap per tenant or per query: knnAllowGroup."""
     ctx = forest.ctx
     flags = _dedup_flag(dedup) | _vote_flags(forest, metric, reference_metric)
     qd, nq = _query_dataset(ctx, forest.data, qs)
@@ -939,6 +954,35 @@ def knnAllow(allow, k, forest, qs, dedup=False, metric=None, reference_metric=Fa
     check(lib().rpt_knn_allow_host(ctx._h, forest._h, forest.data._h, qd._h, wp, int(k), flags, _vp(ids),
                                    _vp(dist), _vp(cnt)))
     return ids, dist, cnt
+
+
+def knnAllowGroup(allow, group, k, forest, qs, dedup=False, metric=None, reference_metric=False):
+    """knnAllow with a bitmap per query group (rpt_knn_allow_group_host) -> (ids[nq][k], dist[nq][k],
+    count[nq]).  allow: what allowBitmaps takes, or its result (G bitmaps); group: int[nq], query q is
+    answered under bitmap group[q], -1 = every id.  The answer of query q is what knnAllow(allow[group[q]],
+    ...) gives it, bit for bit; knnAllowLast's numbers are the sums over the queries."""
+    ctx = forest.ctx
+    flags = _dedup_flag(dedup) | _vote_flags(forest, metric, reference_metric)
+    qd, nq = _query_dataset(ctx, forest.data, qs)
+    words, wp, G, g, gp = _allow_group_args(allow, group, forest.data.n, nq)
+    ids = np.empty((nq, k), dtype=np.int32)
+    dist = np.empty((nq, k), dtype=np.float64)
+    cnt = np.empty(nq, dtype=np.int32)
+    check(lib().rpt_knn_allow_group_host(ctx._h, forest._h, forest.data._h, qd._h, wp, G, gp, int(k), flags,
+                                         _vp(ids), _vp(dist), _vp(cnt)))
+    return ids, dist, cnt
+
+
+def knnAllowGroupDev(allow_ptr, G, group_ptr, k, forest, queries, ids_ptr, dist_ptr, count_ptr, dedup=False,
+                     metric=None, reference_metric=False):
+    """knnAllowGroup on device arrays (rpt_knn_allow_group_dev): allow_ptr is the device address of
+    G rows of ceil(n / 32) uint32 words, group_ptr that of nq int32 (0 = every query unfiltered); the
+    rest as knnAllowDev.  Nothing is validated: a group value outside [-1, G) means no id is allowed."""
+    ctx = forest.ctx
+    flags = _dedup_flag(dedup) | _vote_flags(forest, metric, reference_metric)
+    check(lib().rpt_knn_allow_group_dev(ctx._h, forest._h, forest.data._h, queries._h, C.c_void_p(allow_ptr),
+                                        int(G), C.c_void_p(group_ptr), int(k), flags, C.c_void_p(ids_ptr),
+                                        C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
 def knnAllowDev(allow_ptr, k, forest, queries, ids_ptr, dist_ptr, count_ptr, dedup=False, metric=None,
@@ -966,6 +1010,22 @@ def allowCandidates(allow, forest, qs):
     ids = np.empty(max(total.value, 1), dtype=np.int32)
     check(lib().rpt_allow_candidates_host(ctx._h, forest._h, qd._h, wp, _vp(off), _vp(ids), total.value,
                                           C.byref(total)))
+    return off, ids[:total.value]
+
+
+def allowGroupCandidates(allow, group, forest, qs):
+    """allowCandidates with every query under its own bitmap (rpt_allow_group_candidates_host; allow and
+    group as knnAllowGroup's) -> (off[nq+1], ids)."""
+    ctx = forest.ctx
+    qd, nq = _query_dataset(ctx, forest.data, qs)
+    words, wp, G, g, gp = _allow_group_args(allow, group, forest.data.n, nq)
+    total = C.c_int64()
+    off = np.empty(nq + 1, dtype=np.int64)
+    check(lib().rpt_allow_group_candidates_host(ctx._h, forest._h, qd._h, wp, G, gp, _vp(off), None, 0,
+                                                C.byref(total)))
+    ids = np.empty(max(total.value, 1), dtype=np.int32)
+    check(lib().rpt_allow_group_candidates_host(ctx._h, forest._h, qd._h, wp, G, gp, _vp(off), _vp(ids), total.value,
+                                                C.byref(total)))
     return off, ids[:total.value]
 
 
@@ -1204,7 +1264,7 @@ def knnGraphRefineLast(ctx=None):
 
 
 def _graph_search(entry, who, graph, data, qs, k, ef, seeds, forest, seed_k, metric_flag, seed_metric, ctx,
-                  allow=None, width=None, filtered=False):
+                  allow=None, width=None, filtered=False, group=None, grouped=False):
     """graphSearch / graphSearchSV / graphSearchMetricSV / graphSearchAllow around their _host entry
     point; seed_metric: the metric of the knnBatch that takes seeds from `forest`; filtered: the entry
     point takes the allow-list's words behind the seeds and `width` behind ef"""
@@ -1230,9 +1290,13 @@ def _graph_search(entry, who, graph, data, qs, k, ef, seeds, forest, seed_k, met
     cnt = np.empty(nq, dtype=np.int32)
     head = (ctx._h, ds._h, qd._h, int(gids.shape[1]), _vp(gids), _vp(gcnt), int(seeds.shape[1]), _vp(seeds))
     beam = (int(k), int(ef))
-    if filtered:
+    if filtered and grouped:  # the entry point takes (allow, G, group) where allow stands
+        words, wp, G, g, gp = _allow_group_args(allow, group, ds.n, nq)
+        head += (wp, G, gp)
+    elif filtered:
         words = None if allow is None else allowBitmap(allow, ds.n)
         head += (None if words is None else _vp(words),)
+    if filtered:
         beam += (min(RPT_GRAPH_SEARCH_MAX_WIDTH, 8 * int(ef)) if width is None else int(width),)
     check(entry(*head, *beam, metric_flag, 0, _vp(ids), _vp(dist), _vp(cnt)))
     return ids, dist, cnt
@@ -1317,6 +1381,24 @@ def graphSearchMetricSVDev(distf, data, queries, kg, gids_ptr, gcount_ptr, s, se
                                                 C.c_void_p(count_ptr)))
 
 
+def allowBitmaps(masks, n):
+    """G allow-lists as uint32[G][ceil(n / 32)], row g being allowBitmap(masks[g], n): the bitmaps of a
+    grouped call (graphSearchAllow / knnAllow / bruteKnnAllow / ... with group=).  masks: a sequence
+    whose entries are each what allowBitmap takes (a bool mask of n, integer ids, or ceil(n / 32)
+    uint32 words), or the result of this function (returned as it is).  The row stride is
+    ceil(n / 32) words."""
+    n = int(n)
+    nw = (n + 31) // 32
+    if isinstance(masks, np.ndarray) and masks.dtype == np.uint32 and masks.ndim == 2:
+        if masks.shape[1] != nw:
+            raise ValueError("every allow-list row must hold ceil(n / 32) = %d uint32" % nw)
+        return np.ascontiguousarray(masks)
+    out = np.zeros((len(masks), nw), dtype=np.uint32)
+    for g, m in enumerate(masks):
+        out[g] = allowBitmap(m, n)
+    return out
+
+
 def allowBitmap(mask_or_ids, n):
     """The allow-list of graphSearchAllow as ceil(n / 32) uint32 words: id i is allowed when bit i & 31
     of word i >> 5 is set.  mask_or_ids: a bool array of n (True = allowed), an integer array of the
@@ -1359,9 +1441,36 @@ def graphSearchAllow(allow, graph, data, qs, k, ef=None, width=None, seeds=None,
     id).  With every id allowed it is graphSearch's / graphSearchSV's / graphSearchMetricSV's bit for
     bit, whatever the width; with width = ef it is the allowed entries of the unfiltered beam.  With
     `forest` the seeds are the ids of knnBatch(seed_k, forest, qs, dedup=True, metric=metric); seeds
-    need not be allowed."""
+    need not be allowed.  A bitmap per tenant or per query: graphSearchAllowGroup."""
     return _graph_search(lib().rpt_graph_search_allow_host, "graphSearchAllow", graph, data, qs, k, ef, seeds,
                          forest, seed_k, _metric_flag(metric), metric, ctx, allow, width, True)
+
+
+def graphSearchAllowGroup(allow, group, graph, data, qs, k, ef=None, width=None, seeds=None, forest=None, seed_k=8,
+                          metric=None, ctx=None):
+    """graphSearchAllow with a bitmap per query group (rpt_graph_search_allow_group_host) ->
+    (ids[nq][k], dist[nq][k], count[nq]).  allow: what allowBitmaps takes, or its result (G bitmaps);
+    group: int[nq], query q searches under bitmap group[q], -1 = every id (None: every query -1).  Many tenants in one batch, a
+    bitmap per query (group = arange(nq)) or a mix with unfiltered queries.  The answer of query q is
+    graphSearchAllow(allow[group[q]], ...)'s for that query, bit for bit, and graphSearchLast's
+    expansions are the sum over the queries.  A group entry outside [-1, G) is refused."""
+    return _graph_search(lib().rpt_graph_search_allow_group_host, "graphSearchAllowGroup", graph, data, qs, k, ef,
+                         seeds, forest, seed_k, _metric_flag(metric), metric, ctx, allow, width, True, group, True)
+
+
+def graphSearchAllowGroupDev(data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, allow_ptr, G, group_ptr, k, ef,
+                             width, ids_ptr, dist_ptr, count_ptr, metric=None):
+    """graphSearchAllowGroup on device arrays (rpt_graph_search_allow_group_dev): allow_ptr the
+    device address of G rows of ceil(n / 32) uint32 words, group_ptr that of nq int32 (0 = every query
+    unfiltered); the rest as graphSearchAllowDev.  Nothing is validated: a group value outside
+    [-1, G) means no id is allowed (count 0)."""
+    metric_flag = _metric_flag(metric)
+    ds = _refine_data(data)
+    check(lib().rpt_graph_search_allow_group_dev(ds.ctx._h, ds._h, queries._h, int(kg), C.c_void_p(gids_ptr),
+                                                 C.c_void_p(gcount_ptr), int(s), C.c_void_p(seeds_ptr),
+                                                 C.c_void_p(allow_ptr), int(G), C.c_void_p(group_ptr), int(k),
+                                                 int(ef), int(width), metric_flag, 0, C.c_void_p(ids_ptr),
+                                                 C.c_void_p(dist_ptr), C.c_void_p(count_ptr)))
 
 
 def graphSearchAllowDev(data, queries, kg, gids_ptr, gcount_ptr, s, seeds_ptr, allow_ptr, k, ef, width, ids_ptr,
@@ -1824,7 +1933,8 @@ def bruteKnnAllow(allow, forest_or_data, qs, k, ctx=None, metric=None, reference
     best allowed rows by (distance, id), NaN last, unused slots id -1 and distance +inf.  allow as
     knnAllow's.  Every row layout and distance; the answer is bruteKnn's over compactRows(data, allow)
     with the ids mapped back, bit for bit; the true Euclidean distance on SVector rows is bruteKnn's
-    tolerance-mode distance (rtol 1e-9, atol 1e-12), from the same tiled kernel."""
+    tolerance-mode distance (rtol 1e-9, atol 1e-12), from the same tiled kernel.  A bitmap per tenant
+    or per query: bruteKnnAllowGroup."""
     data = forest_or_data.data if isinstance(forest_or_data, RPForest) else forest_or_data
     ctx = ctx or data.ctx
     qd, nq = _query_dataset(ctx, data, qs)
@@ -1834,6 +1944,34 @@ def bruteKnnAllow(allow, forest_or_data, qs, k, ctx=None, metric=None, reference
     check(lib().rpt_brute_knn_allow_host(ctx._h, data._h, qd._h, wp, int(k),
                                          _brute_allow_flags(data, metric, reference_metric), _vp(ids), _vp(dist)))
     return ids, dist
+
+
+def bruteKnnAllowGroup(allow, group, forest_or_data, qs, k, ctx=None, metric=None, reference_metric=False):
+    """bruteKnnAllow with a bitmap per query group (rpt_brute_knn_allow_group_host; allow and group as
+    knnAllowGroup's) -> (ids[nq][k], dist[nq][k]): query q ranks the rows of bitmap group[q] (-1 = every
+    row); its answer is bruteKnnAllow(allow[group[q]], ...)'s, bit for bit.  One ascending id list is
+    built per group that a query names, never per query."""
+    data = forest_or_data.data if isinstance(forest_or_data, RPForest) else forest_or_data
+    ctx = ctx or data.ctx
+    qd, nq = _query_dataset(ctx, data, qs)
+    words, wp, G, g, gp = _allow_group_args(allow, group, data.n, nq)
+    ids = np.empty((nq, k), dtype=np.int32)
+    dist = np.empty((nq, k), dtype=np.float64)
+    check(lib().rpt_brute_knn_allow_group_host(ctx._h, data._h, qd._h, wp, G, gp, int(k),
+                                               _brute_allow_flags(data, metric, reference_metric), _vp(ids),
+                                               _vp(dist)))
+    return ids, dist
+
+
+def bruteKnnAllowGroupDev(allow_ptr, G, group_ptr, data, queries, k, ids_ptr, dist_ptr, metric=None,
+                          reference_metric=False):
+    """bruteKnnAllowGroup on device arrays (rpt_brute_knn_allow_group_dev): allow_ptr the device
+    address of G rows of ceil(n / 32) uint32 words, group_ptr that of nq int32 (0 = every query
+    unfiltered); the rest as bruteKnnAllowDev.  A group value outside [-1, G) means no row is allowed."""
+    check(lib().rpt_brute_knn_allow_group_dev(data.ctx._h, data._h, queries._h, C.c_void_p(allow_ptr), int(G),
+                                              C.c_void_p(group_ptr), int(k),
+                                              _brute_allow_flags(data, metric, reference_metric),
+                                              C.c_void_p(ids_ptr), C.c_void_p(dist_ptr)))
 
 
 def bruteKnnAllowDev(allow_ptr, data, queries, k, ids_ptr, dist_ptr, metric=None, reference_metric=False):
@@ -1861,10 +1999,33 @@ def recallHitsAllow(allow, distf, forest, k, qs, reference_metric=False):
     return hits, truth
 
 
+def recallHitsAllowGroup(allow, group, distf, forest, k, qs, reference_metric=False):
+    """recallHitsAllow with a bitmap per query group (rpt_recall_hits_allow_group_host; allow and group as
+    knnAllowGroup's) -> (hits[nq][T], truth[nq][k]), truth = bruteKnnAllowGroup's ids."""
+    ctx = forest.ctx
+    qd, nq = _query_dataset(ctx, forest.data, qs)
+    words, wp, G, g, gp = _allow_group_args(allow, group, forest.data.n, nq)
+    hits = np.empty((nq, forest.T), dtype=np.int32)
+    truth = np.empty((nq, k), dtype=np.int32)
+    check(lib().rpt_recall_hits_allow_group_host(ctx._h, forest._h, forest.data._h, qd._h, wp, G, gp, int(k),
+                                                 _brute_allow_flags(forest.data, distf, reference_metric),
+                                                 _vp(hits), _vp(truth)))
+    return hits, truth
+
+
 def recallWithAllowBatch(allow, distf, forest, k, qs, reference_metric=False):
     """recallWithBatch among the allowed rows -> recall[nq]: per query the mean over trees of
     |candidates(tree, q) ∩ the k nearest allowed rows| / k, summed in tree order."""
     hits, _ = recallHitsAllow(allow, distf, forest, k, qs, reference_metric)
+    out = np.empty(hits.shape[0], dtype=np.float64)
+    for i, row in enumerate(hits.tolist()):
+        out[i] = sum(h / k for h in row) / len(row)
+    return out
+
+
+def recallWithAllowGroupBatch(allow, group, distf, forest, k, qs, reference_metric=False):
+    """recallWithAllowBatch with a bitmap per query group -> recall[nq]."""
+    hits, _ = recallHitsAllowGroup(allow, group, distf, forest, k, qs, reference_metric)
     out = np.empty(hits.shape[0], dtype=np.float64)
     for i, row in enumerate(hits.tolist()):
         out[i] = sum(h / k for h in row) / len(row)

@@ -151,6 +151,16 @@ SYMBOLS = {
     "rpt_brute_knn_allow_dev": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
     "rpt_recall_hits_allow_host": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "rpt_knn_allow_last": (i32, [vp, p_i64, p_i64]),
+    "rpt_graph_search_allow_group_dev": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32,
+                                               vp, vp, vp]),
+    "rpt_graph_search_allow_group_host": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32,
+                                                vp, vp, vp]),
+    "rpt_knn_allow_group_host": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
+    "rpt_knn_allow_group_dev": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
+    "rpt_allow_group_candidates_host": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i64, p_i64]),
+    "rpt_brute_knn_allow_group_host": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, vp, vp]),
+    "rpt_brute_knn_allow_group_dev": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, vp, vp]),
+    "rpt_recall_hits_allow_group_host": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp]),
 }
 
 
