@@ -282,8 +282,12 @@ int32_t rpt_forest_import(rpt_ctx* ctx, const rpt_dataset* ds, const double* R_h
                           int32_t L, int32_t min_leaf, const int32_t* perm_host,
                           const double* thr_host, const double* mglo_host,
                           const double* mghi_host, rpt_forest** out);
-/* projection mode the forest's thresholds were computed with; queries project with the same
- * kernels.  A forest imported with rpt_forest_import starts as RPT_PROJ_AUTO: restore the
+/* projection mode the forest's thresholds were computed with; queries project in the same mode,
+ * with a kernel chosen by the batch's shape and the context's options at the time of the call (so a
+ * stored row sent back as a query gets the build's key bit for bit in RPT_PROJ_EXACT, and a key
+ * within twice the mode's tolerance of it otherwise: e.g. RPT_PROJ_MFMA on CSR rows builds on the
+ * dense-ified bf16 path from 65 536 rows on, while a small query batch stays on the segmented
+ * kernel; proj_bf16_terms, proj_bf16_f32 and proj_csr_nodense are not stored in the forest).  A forest imported with rpt_forest_import starts as RPT_PROJ_AUTO: restore the
  * builder's mode with rpt_forest_set_mode (the flat on-disk format stores it). */
 int32_t rpt_forest_get_mode(const rpt_forest* f, int32_t* mode);
 int32_t rpt_forest_set_mode(rpt_forest* f, int32_t mode);
